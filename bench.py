@@ -15,12 +15,15 @@ Both produce identical trajectories (tests/test_gpu_rollout.py).  `value`
 counts env-steps (envs x T x K in rollout mode, envs x K in step mode) over
 the timed wall time.
 
-    python bench.py --gpus N --steps K --warmup W [--mode rollout|step]
-    (N > 1: one rank per GPU; run under torch.distributed.run, or plain
+    python bench.py --gpus N --steps K --warmup W [--mode rollout|step] [--dump-outputs DIR] [--full]
+    (a plain run sets up, warms up, times the K steps and prints the line; --dump-outputs DIR also
+     writes what the last timed step returned as DIR/<name>.npy; --full adds the legs below that take
+     runs of their own: the CPU baselines on one GPU, the `dp_update` leg on N > 1.
+     N > 1: one rank per GPU; run under torch.distributed.run, or plain
      `python bench.py --gpus N`, which starts torch.distributed.run itself as a
      child process before any GPU call and exits with its code.  Envs are
      independent shards, no collective on the data path -> weak scaling.
-     After the env timing every rank also runs the `dp_update` leg: PPO
+     With --full, after the env timing every rank also runs the `dp_update` leg: PPO
      optimizer steps on its own 2,048-sample minibatches (BASELINE configs 4
      fp32 and 5 bf16, minibatch_scope per_gpu) with the RCCL gradient
      all-reduce of /root/reference/src/agents/ppo.py:395-401's optimizer step,
@@ -30,8 +33,9 @@ Prints ONE JSON line on rank 0.  `roofline` prices the dominant kernel
 against HBM with the algorithmic bytes of SURVEY.md 8(d) (194 B per env-step)
 x the env-steps of one launch, over its average launch duration measured here
 with HIP events on the launch stream (the rocprofv3 kernel-trace average
-agrees, profiles/); `cpu_baseline` times the CPU port of the reference's
-64-env vectorised path (oracle/bb_game.py, one core) on a bounded sample.
+agrees, profiles/); with --full, `cpu_baseline` times the CPU port of the
+reference's 64-env vectorised path (oracle/bb_game.py, one core) on a bounded
+sample.
 """
 from __future__ import annotations
 
@@ -304,6 +308,60 @@ def dp_update_leg(dev, rank: int, world: int, steps: int, warmup: int, bf16: boo
     }
 
 
+DUMP_BUDGET_BYTES = 48 << 20  # of --dump-outputs' 64 MB in all
+DUMP_SAMPLE_SEED = 0xD0
+
+
+def dump_outputs(path: str, shards, mode: str, T: int, rank: int, min_outputs: bool) -> None:
+    """--dump-outputs: what the last timed launch handed back, as <name>.npy under ``path`` (rank r > 0:
+    <name>_rank<r>.npy).  rollout mode: reward / terminated / lines / actions [T, E] float32, mask_words
+    [T, E, 6] float64 (the three 64-bit legal-action words of every env-step as little-endian 32-bit halves,
+    exact in float64) and next_action [E] float32, the action of the next launch's first step; step mode:
+    reward / terminated / next_action [E] float32.  E is every env of the rank (shards in order), or, where
+    that would pass the byte budget, a fixed seeded sample of them, listed in env_index [E] float64."""
+    import numpy as np
+    import torch
+
+    n = sum(e.num_envs for e, _, _, _ in shards)
+    per_env = (T * (4 * 4 + 6 * 8) if mode == "rollout" else 2 * 4) + 4 + 8
+    keep = np.arange(n)
+    if n * per_env > DUMP_BUDGET_BYTES:
+        k = DUMP_BUDGET_BYTES // per_env
+        keep = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=k, replace=False))
+    parts = {}
+    base = 0
+    for e, _, a, outs in shards:
+        sel = keep[(keep >= base) & (keep < base + e.num_envs)] - base
+        base += e.num_envs
+        idx = torch.from_numpy(sel).to(e.device)
+
+        def take(t, dim):
+            return t.index_select(dim, idx).cpu().numpy()
+
+        got = {"next_action": take(a[0], 0).astype(np.float32)}  # a[0]: written by the last launch, then flipped
+        if mode == "step":
+            got["reward"] = take(e.reward, 0)
+            got["terminated"] = take(e.terminated, 0).astype(np.float32)
+        else:
+            o_rew, o_term, o_lines, o_act, o_mask = outs
+            got["reward"] = take(o_rew, 1)
+            got["terminated"] = take(o_term, 1).astype(np.float32)
+            if not min_outputs:
+                got["lines"] = take(o_lines, 1).astype(np.float32)
+                got["actions"] = take(o_act, 1).astype(np.float32)
+                words = np.ascontiguousarray(take(o_mask, 1)).view("<u4")  # [T, E, 3] int64 -> [T, E, 6] u32
+                got["mask_words"] = words.astype(np.float64)
+        for name, arr in got.items():
+            parts.setdefault(name, []).append(arr)
+    os.makedirs(path, exist_ok=True)
+    suffix = f"_rank{rank}" if rank else ""
+    out = {name: np.concatenate(arrs, axis=0 if arrs[0].ndim == 1 else 1) for name, arrs in parts.items()}  # env axis
+    out["env_index"] = keep.astype(np.float64)
+    assert sum(v.nbytes for v in out.values()) <= 64 << 20
+    for name, arr in out.items():
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), arr)
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -314,6 +372,12 @@ def main() -> None:
                     help="timed bench steps: bb_rollout launches of T env-steps (rollout) or bb_step launches (step)")
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--envs", type=int, default=65536, help="envs per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs that take runs of their own: the CPU baselines (one GPU), the "
+                         "dp_update leg (N > 1); off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / float64; a fixed "
+                         "seeded sample of the envs when all of them would exceed 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-native-baseline", action="store_true")
@@ -448,6 +512,8 @@ def main() -> None:
 
     total_env_steps = n * world * args.steps * per_launch
     value = total_env_steps / el
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, shards, args.mode, T, rank, diag_min_out)
     for e, _, _, _ in shards:  # the env shards' memory is not needed by the update leg
         e.close()
     shards = []
@@ -508,7 +574,7 @@ def main() -> None:
         return out
 
     dp = None
-    if world > 1 and args.dp_steps > 0:
+    if args.full and world > 1 and args.dp_steps > 0:
         # the env line is already measured: a dp_update leg that fails or hangs (a collective that never
         # completes) must not cost it.  A watchdog per rank prints rank 0's line with the error and ends
         # every rank with status 0 after --dp-timeout seconds; an exception is recorded likewise.
@@ -535,7 +601,7 @@ def main() -> None:
         dog.cancel()
     if rank == 0:
         out = line(dp)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cb = cpu_baseline(args.cpu_seconds)
             out["cpu_baseline"] = cb
             if not args.no_native_baseline:

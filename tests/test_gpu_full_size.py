@@ -137,13 +137,13 @@ def test_bench_two_ranks_shared_gpu(tmp_path):
 
 
 def test_bench_gpus_flag_launches_ranks(tmp_path):
-    """`python bench.py --gpus 2` with no launcher starts its own two ranks (the driver's plain form) and adds
-    the dp_update leg: per-rank optimizer steps with the gradient all-reduce, both precisions (share mode:
-    both ranks on cuda:0 over gloo -- the RCCL world is the driver's 8-GPU run)."""
+    """`python bench.py --gpus 2 --full` with no launcher starts its own two ranks (the driver's plain form) and,
+    under --full, adds the dp_update leg: per-rank optimizer steps with the gradient all-reduce, both precisions
+    (share mode: both ranks on cuda:0 over gloo -- the RCCL world is the driver's 8-GPU run)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["BB_BENCH_SHARE_GPU"] = "1"
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2",
-           "--envs", "4096", "--dp-steps", "3", "--dp-warmup", "1"]
+           "--envs", "4096", "--dp-steps", "3", "--dp-warmup", "1", "--full"]
     r = subprocess.run(cmd, env=env, cwd=str(tmp_path), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [x for x in r.stdout.splitlines() if x.startswith("{")]
@@ -155,3 +155,51 @@ def test_bench_gpus_flag_launches_ranks(tmp_path):
         assert dp["rccl_world_size"] == 2 and dp["step_ms"] > 0 and dp["local_step_ms"] > 0
         assert dp["ranks_weights_equal"], dp  # the all-reduced updates left both ranks on the same weights
         assert dp["grad_floats"] >= 5_290_113
+
+
+def test_bench_plain_run_dumps_last_step(cuda, tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: K timed steps, `ms_per_step`, no
+    CPU baselines (those need --full), and under DIR the outputs of the last timed bb_rollout launch, equal to
+    the same W + K launches made here through DeviceEnvBatch."""
+    from runtime.device_env import DeviceEnvBatch
+
+    n, T, W, K = 4096, 32, 2, 3
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", str(W),
+           "--envs", str(n), "--rollout-len", str(T), "--dump-outputs", str(out)]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    r = subprocess.run(cmd, env=env, cwd=str(tmp_path), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    lines = [x for x in r.stdout.splitlines() if x.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == K and d["warmup"] == W and d["n_gpus"] == 1 and d["higher_is_better"] is True
+    assert d["ms_per_step"] > 0 and d["unit"] == "env-steps/s" and d["dtype"] == "u64"
+    # value = env-steps of one step over ms_per_step, which the line rounds to 1e-4 ms
+    assert abs(d["value"] - n * T / (d["ms_per_step"] * 1e-3)) <= (1e-4 / d["ms_per_step"] + 1e-6) * d["value"]
+    assert "cpu_baseline" not in d and "cpu_baseline_native" not in d and "dp_update" not in d
+
+    e = DeviceEnvBatch(n, seeds=[42 + i for i in range(n)], device=cuda)
+    e.reset()
+    mb = torch.zeros((n, 3), dtype=torch.int64, device=cuda)
+    e.obs(mask_bits=mb)
+    a = [torch.zeros(n, dtype=torch.int32, device=cuda) for _ in range(2)]
+    e.random_actions(mb, a[0], seed=0xB10C, step=0)
+    rew = torch.zeros((T, n), dtype=torch.float32, device=cuda)
+    term, lin = (torch.zeros((T, n), dtype=torch.uint8, device=cuda) for _ in range(2))
+    act = torch.zeros((T, n), dtype=torch.int32, device=cuda)
+    mask = torch.zeros((T, n, 3), dtype=torch.int64, device=cuda)
+    for j in range(W + K):
+        e.rollout(T, a[0], rew, term, lines=lin, actions_out=act, mask_out=mask, next_action=a[1],
+                  policy_seed=0xB10C, policy_step0=j * T)
+        a.reverse()
+    torch.cuda.synchronize()
+    got = {f[:-4]: np.load(out / f) for f in os.listdir(out)}
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+    assert sum(v.nbytes for v in got.values()) <= 64 << 20
+    assert np.array_equal(got["env_index"], np.arange(n))
+    for name, t in (("reward", rew), ("terminated", term), ("lines", lin), ("actions", act), ("next_action", a[0])):
+        assert np.array_equal(got[name], t.cpu().numpy().astype(np.float32)), name
+    w = got["mask_words"].astype(np.uint64)
+    assert np.array_equal((w[..., 0::2] | (w[..., 1::2] << np.uint64(32))).view(np.int64), mask.cpu().numpy())
+    e.close()

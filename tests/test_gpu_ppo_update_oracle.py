@@ -31,7 +31,8 @@ gradient elements are differences of large partial sums and carry fp32
 summation-order errors of a few percent of their own size (MIOpen's /
 hipBLASLt's order vs the CPU's); Adam's first steps normalise every gradient
 element to about +-lr, so such an element's update differs by that same
-fraction of lr (measured: up to 1.1e-5); for the tensors whose gradient went to
+fraction of lr (measured: up to 1.5e-5 on the trajectory that ``_fixed_trajectory`` pins, at the first step,
+where the CPU oracle's own distance from the fp64 update is 1.5e-5 and the GPU's 0.3e-5); for the tensors whose gradient went to
 the fp64 check the update's relative L2 bound is 3e-2 instead of 1e-2 (measured
 up to 1.2e-2 on the first convolution's weight: MIOpen's fp32 weight gradient
 accumulates with atomics, so its order changes run to run).  Free-running, these differences
@@ -182,6 +183,21 @@ def _oracle_forced(net, buf, last, cfg, perm, snaps, per_gpu):
 
     means, per, adv, ret = OP.ppo_update(ref, opt, buf, last, cfg, perm, before_step=before, after_step=after)
     return means, per, adv, ret, worst
+
+
+@pytest.fixture(autouse=True)
+def _fixed_trajectory():
+    """MIOpen's default fp32 weight gradients add with atomics, so two updates from the same state leave weights
+    that differ by a whole Adam step (3e-4) after eight steps: every run of these tests walked another
+    trajectory, and its worst per-element figure was a fresh draw (1.1e-5 ... 3.1e-5 seen against the 3e-5
+    bound; the first step alone, the same in every run, gives 1.5e-5, of which the CPU oracle's own fp32 error
+    against the fp64 update is 1.5e-5 and the GPU's 0.6e-5).  With MIOpen's deterministic algorithms
+    (training.deterministic) the GPU's eight steps repeat bit for bit, so the bounds are checked on one
+    trajectory; the kernels of this repository run the same either way."""
+    was = torch.backends.cudnn.deterministic
+    torch.backends.cudnn.deterministic = True
+    yield
+    torch.backends.cudnn.deterministic = was
 
 
 def _check_means(means_gpu, means_ref):

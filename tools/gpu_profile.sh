@@ -1,5 +1,5 @@
 #!/bin/bash
-# Round profile set for the default bench: full bench line (with CPU baseline),
+# Round profile set for the default bench: the bench line (ARGS with --full: with the CPU baselines),
 # rocprofv3 kernel stats, and two separate PMC passes (FETCH_SIZE, WRITE_SIZE).
 set -o pipefail
 cd "$GRAFT_REPO_ROOT" || exit 1
