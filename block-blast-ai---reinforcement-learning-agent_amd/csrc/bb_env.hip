@@ -848,6 +848,9 @@ __global__ void __launch_bounds__(kStepRollBlock, 1) step_fused_kernel(EnvDev e,
 // A workgroup (one per CU at 65,536 envs) holds kAEW = 4 env waves of 64 envs,
 // one lane per env, whose state stays in VGPRs for the whole launch, and
 // kASW search waves (one env wave and one search wave per SIMD).  An env whose
+// move used its hand's last piece waits until its wave opens the draw block
+// (the draw gate, BB_ASYNC_DGATE: the envs of a wave draw together, so the wave
+// walks the draw and the quick test in about a third of its iterations).  An env whose
 // new hand the in-lane quick test (two fixed slots) leaves open posts its
 // post-move board and rolled-back stream to an LDS record and is blocked; its
 // wave goes on stepping its other envs (each env keeps its own step counter,
@@ -884,6 +887,23 @@ __global__ void __launch_bounds__(kStepRollBlock, 1) step_fused_kernel(EnvDev e,
 // 1: the one in-lane slot starts from the hand's fewest-anchor piece (quick_rank_bf), 1.308e10 vs 1.280e10
 // env-steps/s for slot 0 (0; profiles/r04/ab/q1_*)
 #define BB_ASYNC_QPICK 1
+#endif
+#ifndef BB_ASYNC_DGATE
+// draw gate of the env waves: the draw block (draw3, quick test, accept or post) runs only in iterations in
+// which at least BB_ASYNC_DGATE eighths of the wave's runnable envs want a new hand, or the gate stayed closed
+// for BB_ASYNC_DGATE_WAIT iterations with an env waiting, or no env moved.  Envs that draw together want their
+// next hand three moves later together, so a wave aligns its hand phases and walks the block in about a third
+// of its iterations.  0: no gate, the draw follows its move in the same iteration (the schedule up to round 6).
+// 4: 1.470e10 env-steps/s against 1.395e10 without the gate (three interleaved repeats; 0: 1.388e10, 3: 1.467e10,
+// 5: 1.470e10); the draw block runs in 0.325 of the iterations with 35 lanes active, an iteration costs 5,980
+// cycles instead of 7,659, a wave runs 1.63 iterations per step instead of 1.38 (tools/draw_gate_model.c predicted
+// 0.917 of the env wave's cycles, the diagnostic build measured 0.923; profiles/r07/)
+#define BB_ASYNC_DGATE 4
+#endif
+#ifndef BB_ASYNC_DGATE_WAIT
+// closed iterations with an env waiting after which the gate opens regardless (the model: 1 loses the gain, the
+// wave never aligns; 3 and 4 equal 2)
+#define BB_ASYNC_DGATE_WAIT 2
 #endif
 #ifndef BB_ASYNC_DIAG
 #define BB_ASYNC_DIAG 0  // per-wave counters into dbg_out (tools/diag_async.py, BB_DEBUG_MODE=16); 2: + env-wave
@@ -1100,19 +1120,23 @@ __global__ void __launch_bounds__(kABlock, 1) rollout_async_kernel(EnvDev e, con
   const size_t N = (size_t)e.n;
   const int T = r.steps;
   int st = 0;   // this env's completed steps
-  int ph = 0;   // 0 ready to move, 1 posted (blocked), 2 hand known (finalize)
-  // Bounds (never reached by a correct run): an iteration that moves or finalizes some env advances one of the
-  // wave's 2 * kAE * T phases, so there are at most 2 * kAE * T of them; a run of iterations in which every
+  int ph = 0;   // 0 ready to move, 1 posted (blocked), 2 hand known (finalize), 3 moved, wants a draw
+  // Bounds (never reached by a correct run): an iteration that moves, draws for or finalizes some env advances one
+  // of the wave's 3 * kAE * T phases, so there are at most 3 * kAE * T of them; a run of iterations in which every
   // unfinished env waits on a search lasts as long as that search (at most 100 attempts), so 2^24 of them in a
   // row (seconds) means a lost record.  Either cap ends the wave instead of hanging the GPU, and the wave then
   // raises the handle's status word (kStatusAsyncCap): the host fails the next call with BB_ERR_DEVICE.
-  const int64_t cap = r.work_cap > 0 ? r.work_cap : 2 * (int64_t)kAE * T + 4096;
+  const int64_t cap = r.work_cap > 0 ? r.work_cap : 3 * (int64_t)kAE * T + 4096;
   int64_t work_it = 0, idle_it = 0;  // idle_it: the current run of all-blocked iterations
+#if BB_ASYNC_DGATE
+  int gate_closed = 0;  // consecutive iterations the draw gate stayed closed with an env waiting (wave-uniform)
+#endif
 #if BB_ASYNC_DIAG  // iterations, cycles, blocked env-iterations, iterations that moved no env | their cycles << 32
   uint64_t dit = 0, dblk = 0, didle = 0, didle_cyc = 0;
+  uint64_t ddraw = 0, dgwait = 0, ddlanes = 0;  // draw-block runs, env-iterations waiting at the gate, its lanes
   const uint64_t dt0 = __builtin_amdgcn_s_memtime();
 #endif
-#if BB_ASYNC_DIAG >= 2  // env-wave phases: move+draw, quick test+post, poll, Philox, masks, reward, outputs+reset, policy
+#if BB_ASYNC_DIAG >= 2  // env-wave phases: move+gate, draw+quick+post, poll, Philox, masks, reward, outputs+reset, policy
   uint64_t dph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   uint64_t dlast = 0;
 #endif
@@ -1128,58 +1152,70 @@ __global__ void __launch_bounds__(kABlock, 1) rollout_async_kernel(EnvDev e, con
 #if BB_ASYNC_DIAG >= 2
     dlast = __builtin_amdgcn_s_memtime();
 #endif
-    // 1. the move of every ready env and attempt 1's draws when it used the last slot
-    //    (block_blast_env.py:237-245, engine.py:326-437)
+    // 1. the move of every ready env (block_blast_env.py:237-245, engine.py:326-437); one that used its hand's
+    //    last slot wants a draw (its step's valid / lines / gained stay in s, as they do for a blocked env)
     const bool mv = live && ph == 0 && st < T;
 #if BB_ASYNC_PHILOX_EARLY
     // this step's policy uniform depends only on the env's step counter: its ten dependent Philox rounds
     // overlap the move's LDS round trips (one lane per env: no copy to share it with)
     const uint32_t u_next = policy_uniform(a.policy_seed, a.env_offset + (uint64_t)i, r.policy_step0 + st + 1);
 #endif
-    Pcg after = s.rng;
-    bool drew = false;
-    if (mv) {
-      drew = apply_move_bf(t, s, act);
+    if (mv) ph = apply_move_bf(t, s, act) ? 3 : 2;  // 2: no draw (or an invalid action), the hand is known
+    // the draw gate: one wave-uniform decision (ballots and a scalar counter), so that a closed gate skips the
+    // whole draw block.  No env moved: nothing of this iteration would be lost by drawing now (liveness)
+    bool drew = live && ph == 3;
+#if BB_ASYNC_DGATE
+    {
+      const int n_want = __popcll(__ballot(drew));
+      const int n_run = __popcll(__ballot(live && ph != 1 && st < T));
+      const bool open = BB_ASYNC_DGATE * n_run <= 8 * n_want || gate_closed >= BB_ASYNC_DGATE_WAIT || !__ballot(mv);
+      gate_closed = (n_want && !open) ? gate_closed + 1 : 0;
+      if (!open) drew = false;
+    }
+#endif
+    const bool draws = __ballot(drew) != 0ull;
+#if BB_ASYNC_DIAG
+    ddraw += draws ? 1u : 0u;
+    ddlanes += (uint64_t)__popcll(__ballot(drew));
+    dgwait += (uint64_t)__popcll(__ballot(live && ph == 3 && !drew));
+#endif
+    BB_ENV_STAMP(0)
+    // 2. attempt 1's draws and its in-lane quick test: fixed level-1 slots 0 .. BB_ASYNC_SLOTS - 1 (an accept is
+    //    an exact success; anything else goes to a search wave, which redraws the attempt)
+    if (draws) {
       if (drew) {
         const Pcg save = s.rng;
         uint32_t x0, x1, x2;
         draw3(s.rng, x0, x1, x2);
-        after = s.rng;
+        const Pcg after = s.rng;
         s.rng = save;
         s.hand = x0 | (x1 << 6) | (x2 << 12);
-      }
-    }
-    BB_ENV_STAMP(0)
-    // 2. in-lane quick test of attempt 1: fixed level-1 slots 0 .. BB_ASYNC_SLOTS - 1 (an accept is an exact
-    //    success; anything else goes to a search wave, which redraws the attempt)
-    if (drew) {
-      const uint32_t q0 = s.hand & 63u, q1 = (s.hand >> 6) & 63u, q2 = (s.hand >> 12) & 63u;
-      bool ok = false;
+        const uint32_t q0 = s.hand & 63u, q1 = (s.hand >> 6) & 63u, q2 = (s.hand >> 12) & 63u;
+        bool ok = false;
 #if BB_ASYNC_QPICK
-      ok = quick_rank_bf(s.B, q0, q1, q2, t.row, t.d, 0);
+        ok = quick_rank_bf(s.B, q0, q1, q2, t.row, t.d, 0);
 #else
 #pragma unroll
-      for (int k = 0; k < BB_ASYNC_SLOTS; ++k) ok = quick_slot_bf(s.B, q0, q1, q2, t.row, t.d, k) || ok;
+        for (int k = 0; k < BB_ASYNC_SLOTS; ++k) ok = quick_slot_bf(s.B, q0, q1, q2, t.row, t.d, k) || ok;
 #endif
-      if (ok) s.rng = after;
-      s.hand = (s.hand & 0x3FFFFu) | ((uint32_t)s.rng.has << 22);
-      if (ok) {
-        ph = 2;
-      } else {  // post the env: post-move board, stream rolled back to attempt 1
-        arec.B[rid] = s.B;
-        arec.hi[rid] = s.rng.hi;
-        arec.lo[rid] = s.rng.lo;
-        arec.buf[rid] = s.rng.buf;
-        arec.has_ids[rid] = s.rng.has ? 1u : 0u;
-        arec.inc_hi[rid] = s.rng.inc_hi;
-        arec.inc_lo[rid] = s.rng.inc_lo;
-        lds_flag_store_release(&astat[rid], 1u);
-        ph = 1;
+        if (ok) s.rng = after;
+        s.hand = (s.hand & 0x3FFFFu) | ((uint32_t)s.rng.has << 22);
+        if (ok) {
+          ph = 2;
+        } else {  // post the env: post-move board, stream rolled back to attempt 1
+          arec.B[rid] = s.B;
+          arec.hi[rid] = s.rng.hi;
+          arec.lo[rid] = s.rng.lo;
+          arec.buf[rid] = s.rng.buf;
+          arec.has_ids[rid] = s.rng.has ? 1u : 0u;
+          arec.inc_hi[rid] = s.rng.inc_hi;
+          arec.inc_lo[rid] = s.rng.inc_lo;
+          lds_flag_store_release(&astat[rid], 1u);
+          ph = 1;
+        }
       }
-    } else if (mv) {
-      ph = 2;  // no draw (or an invalid action): the hand is known
+      BB_ENV_STAMP(1)
     }
-    BB_ENV_STAMP(1)
     // 3. answered searches (polled after the moves, so that answers which arrived meanwhile finalize in this
     //    iteration: 1.017e10 vs 9.89e9 polled before them, r03): the stream after the accepted attempt, the hand
     if (live && ph == 1 && lds_flag_load_acquire(&astat[rid]) == 2u) {
@@ -1256,7 +1292,7 @@ __global__ void __launch_bounds__(kABlock, 1) rollout_async_kernel(EnvDev e, con
       ph = 0;
       BB_ENV_STAMP(7)
     }
-    if (!__ballot(mv || fin)) {  // every env blocked: leave the SIMD to the searches
+    if (!__ballot(mv || fin) && !draws) {  // every env blocked: leave the SIMD to the searches
       ++idle_it;
       __builtin_amdgcn_s_sleep(1);
 #if BB_ASYNC_DIAG
@@ -1277,6 +1313,9 @@ __global__ void __launch_bounds__(kABlock, 1) rollout_async_kernel(EnvDev e, con
     o[1] = __builtin_amdgcn_s_memtime() - dt0;
     o[2] = dblk;
     o[3] = didle | (didle_cyc << 32);
+    o[12] = ddraw;
+    o[13] = dgwait;
+    o[14] = ddlanes;
 #if BB_ASYNC_DIAG >= 2
     for (int q = 0; q < 8; ++q) o[4 + q] = dph[q];
 #endif

@@ -81,7 +81,7 @@ struct RollArgs {
   double* reward_f64;           // [T][N] optional: the fp64 reward
   int64_t* final_score;         // [T][N] optional: written where the env terminated at step t (pre-reset score)
   int32_t* final_moves;         // [T][N] optional: likewise its moves
-  int64_t work_cap;             // rollout_async_kernel: working iterations per env wave (0: 2 * 64 * T + 4096;
+  int64_t work_cap;             // rollout_async_kernel: working iterations per env wave (0: 3 * 64 * T + 4096;
                                 // smaller only to test the cap's error path, BB_DEBUG_ASYNC_CAP)
 };
 

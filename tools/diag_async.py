@@ -3,8 +3,9 @@
 Needs a build with -DBB_ASYNC_DIAG=1 (python tools/variants.py build adiag, loaded with
 BBVEC_LIB=tools/variants/libbbvec_adiag.so); sets BB_DEBUG_MODE=16.  Reports per env wave:
 iterations per step (T plus blocked iterations), cycles per iteration, blocked env-iterations
-and iterations that moved no env (and, with -DBB_ASYNC_DIAG=2, the cycles of each phase of an
-iteration); per search wave: calls, envs per call, cycles per call, polls, gen_hands_multi phases.
+and iterations that moved no env, the draw gate's counters (draw-block runs, env-iterations spent
+waiting at the gate, lanes active in the draw block when it runs; and, with -DBB_ASYNC_DIAG=2, the
+cycles of each phase of an iteration); per search wave: calls, envs per call, cycles per call, polls, gen_hands_multi phases.
 """
 import ctypes as C
 import json
@@ -63,8 +64,13 @@ def main():
             "blocked_envs_per_iter_per_wave": round(we[:, 2].sum() / we[:, 0].sum(), 3),
             "idle_iters_per_wave": round((wex[:, 3] & 0xFFFFFFFF).astype(np.float64).mean(), 2),
             "idle_cyc_frac": round((wex[:, 3] >> 32).astype(np.float64).sum() / we[:, 1].sum(), 4),
+            "draw_runs_per_wave": round(float(wex[:, 12].astype(np.float64).mean()), 2),
+            "draw_runs_per_iter": round(float(wex[:, 12].astype(np.float64).sum() / we[:, 0].sum()), 4),
+            "gate_wait_env_iters_per_wave": round(float(wex[:, 13].astype(np.float64).mean()), 1),
+            "draw_lanes_per_run": round(float(wex[:, 14].astype(np.float64).sum()
+                                              / max(wex[:, 12].astype(np.float64).sum(), 1)), 2),
             "env_phase_cyc_per_iter": {k: round(float(v), 0) for k, v in zip(
-                ("move_draw", "quick_post", "poll", "philox", "masks", "reward", "outputs_reset", "policy"), env_ph)},
+                ("move_gate", "draw_quick_post", "poll", "philox", "masks", "reward", "outputs_reset", "policy"), env_ph)},
             "search_calls_per_wave": round(ws[:, 0].mean(), 1),
             "envs_per_call": round(ws[:, 1].sum() / max(ws[:, 0].sum(), 1), 2),
             "cyc_per_call": round(ws[:, 2].sum() / max(ws[:, 0].sum(), 1), 0),

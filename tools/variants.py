@@ -75,6 +75,15 @@ VARIANTS = {
     "asl4": ["-DBB_ASYNC_SLEEP=4"],
     # the one in-lane slot starts from the fewest-anchor piece (quick_least_bf)
     "aqp0": ["-DBB_ASYNC_QPICK=0"],
+    # the env waves' draw gate: off (the round-6 schedule), the share threshold's neighbours (shipped 4 eighths),
+    # the closed-streak limit's (shipped 2).  A bound on the records a search wave claims per call lost 31-39%
+    # (tools/patches/r07_claim_max.diff)
+    "adg0": ["-DBB_ASYNC_DGATE=0"],
+    "adg3": ["-DBB_ASYNC_DGATE=3"],
+    "adg5": ["-DBB_ASYNC_DGATE=5"],
+    "adgw1": ["-DBB_ASYNC_DGATE_WAIT=1"],
+    "adgw3": ["-DBB_ASYNC_DGATE_WAIT=3"],
+    "adg0diag": ["-DBB_ASYNC_DGATE=0", "-DBB_ASYNC_DIAG=1"],
     # diagnostics: every search call run a second time, results dropped (search waves' share of the SQ counts)
     "adup": ["-DBB_ASYNC_DIAG_DUPSEARCH=1"],
     "adupdiag": ["-DBB_ASYNC_DIAG_DUPSEARCH=1", "-DBB_ASYNC_DIAG=1"],
