@@ -1,0 +1,130 @@
+"""Baseline agents that need no training: a one-ply greedy heuristic and random legal play.
+
+The reference has no baseline players; these give a checkpoint's evaluation something to be compared with
+(``evaluate.py --agent greedy`` / ``--agent random`` on the same seeds).  Both choose their actions on the
+device the envs live on: ``GreedyAgent`` through the fused ``bb_greedy_actions`` kernel (the arg-max of an
+integer value over the afterstates of the 192 actions, csrc/bb_lookahead.hip), ``RandomAgent`` through the
+Philox random-legal policy ``bb_random_actions``.  ``device="cpu"`` runs them on the host backend.
+"""
+from __future__ import annotations
+
+import json
+from typing import Any, Dict, Optional, Tuple
+
+import numpy as np
+import torch
+
+from runtime import lib as L
+
+from .base import BaseAgent
+
+# Chosen by reasoning, not tuned: a cleared line is worth far more than anything else a single move does, new
+# holes are the main lasting damage, a fuller board is worse, more placements left for the remaining pieces is
+# better, and a move after which the remaining pieces cannot be placed ends the game.
+DEFAULT_WEIGHTS = {"lines": 100, "score": 0, "holes": -30, "filled": -2, "centre": 0, "mobility": 1,
+                   "dead": -100000, "refill": 0}
+
+
+def _position_of(observation: Dict[str, Any]):
+    """(board bits, packed hand word) of a Gym observation: the board plane and the unused pieces' shapes
+    (a used slot's plane is all zeros)."""
+    from game.pieces import PIECE_MASKS
+
+    board = np.asarray(observation["board"]).reshape(64) != 0
+    bits = int(sum(1 << i for i in np.nonzero(board)[0]))
+    hand = 0
+    for s, plane in enumerate(np.asarray(observation["pieces"])):
+        match = np.nonzero((PIECE_MASKS == plane).all(axis=(1, 2)))[0]
+        if match.size:
+            hand |= int(match[0]) << (6 * s)
+        else:
+            hand |= 1 << (18 + s)
+    return bits, hand
+
+
+class GreedyAgent(BaseAgent):
+    """Plays the legal action with the largest one-ply greedy value (ties: the lowest action)."""
+
+    def __init__(self, weights: Optional[Dict[str, int]] = None, device=None):
+        from runtime.device_env import resolve_device
+
+        super().__init__(resolve_device(device))
+        self.weights = dict(DEFAULT_WEIGHTS)
+        if weights:
+            L.greedy_weights(weights)  # rejects unknown names
+            self.weights.update({k: int(v) for k, v in weights.items()})
+
+    def act_env(self, env_batch, out: torch.Tensor) -> torch.Tensor:
+        """The action of every env of a ``DeviceEnvBatch`` into out (int32 [N]), in one fused launch."""
+        return env_batch.greedy_actions(out, self.weights)
+
+    def select_action(self, observation: Dict[str, Any], deterministic: bool = True) -> Tuple[int, Dict[str, Any]]:
+        """From a Gym observation.  The observation does not carry the combo count, so the ``score`` weight (0
+        by default) sees every move as the first of a streak here; ``act_env`` reads the real count."""
+        from runtime import kernels as K
+
+        bits, hand = _position_of(observation)
+        board = torch.tensor([bits - (1 << 64) if bits >= 1 << 63 else bits], dtype=torch.int64, device=self.device)
+        hand_t = torch.tensor([hand], dtype=torch.int32, device=self.device)
+        action, value = K.greedy_actions(board, hand_t, self.weights)
+        return int(action.cpu().item()), {"value": int(value.cpu().item())}
+
+    def update(self, *args, **kwargs) -> Dict[str, float]:
+        return {}
+
+    def save(self, path: str) -> None:
+        with open(path, "w") as f:
+            json.dump({"agent": "greedy", "weights": self.weights}, f, indent=2)
+
+    def load(self, path: str) -> None:
+        with open(path) as f:
+            data = json.load(f)
+        L.greedy_weights(data["weights"])
+        self.weights = dict(DEFAULT_WEIGHTS)
+        self.weights.update({k: int(v) for k, v in data["weights"].items()})
+
+
+class RandomAgent(BaseAgent):
+    """Uniform random legal play: the Philox policy of ``bb_random_actions`` (bb_step_out.next_action), keyed
+    by ``seed`` and counting one step per call."""
+
+    def __init__(self, seed: int = 0xB10C, device=None):
+        from runtime.device_env import resolve_device
+
+        super().__init__(resolve_device(device))
+        self.seed = int(seed)
+        self.step = 0
+        self._mask_bits = None
+
+    def act_env(self, env_batch, out: torch.Tensor) -> torch.Tensor:
+        n = env_batch.num_envs
+        if self._mask_bits is None or self._mask_bits.shape[0] != n or self._mask_bits.device != env_batch.device:
+            self._mask_bits = torch.zeros((n, 3), dtype=torch.int64, device=env_batch.device)
+        env_batch.obs(mask_bits=self._mask_bits)
+        env_batch.random_actions(self._mask_bits, out, seed=self.seed, step=self.step)
+        self.step += 1
+        return out
+
+    def select_action(self, observation: Dict[str, Any], deterministic: bool = False) -> Tuple[int, Dict[str, Any]]:
+        from runtime import kernels as K
+        from runtime.device_env import _ptr, _stream
+
+        mask = torch.as_tensor(np.asarray(observation["action_mask"]).reshape(1, 3, 64) != 0)
+        bits = (mask.to(torch.int64) << torch.arange(64)).sum(-1).to(self.device).contiguous()
+        out = torch.zeros(1, dtype=torch.int32, device=self.device)
+        lib, _ = K._look_lib(self.device)
+        L.check(lib.bb_random_actions(_ptr(bits), 1, self.seed, self.step, 0, _ptr(out), _stream(self.device)),
+                "bb_random_actions", lib=lib)
+        self.step += 1
+        return int(out.cpu().item()), {}
+
+    def update(self, *args, **kwargs) -> Dict[str, float]:
+        return {}
+
+    def save(self, path: str) -> None:
+        with open(path, "w") as f:
+            json.dump({"agent": "random", "seed": self.seed}, f, indent=2)
+
+    def load(self, path: str) -> None:
+        with open(path) as f:
+            self.seed = int(json.load(f)["seed"])

@@ -567,6 +567,52 @@ int bb_random_actions(const uint64_t* d_mask_bits, int32_t n, uint64_t seed, uin
   return BB_OK;
 }
 
+// One-ply lookahead (csrc/bb_lookahead.hip).  The _pos forms are stateless and run on the current device.
+int bb_afterstates_pos(const bb_positions* pos, int32_t n, const bb_reward_cfg* cfg, const bb_afterstate_out* out,
+                       void* stream) {
+  if (!pos || !pos->board || !pos->hand || n <= 0 || !cfg || !out)
+    return fail(nullptr, BB_ERR_ARG, "bb_afterstates_pos: positions (board, hand), n > 0, cfg and out are required");
+  hipError_t st = launch_afterstates(pos->board, pos->hand, pos->combo, pos->prev, n, *cfg, *out, (hipStream_t)stream);
+  if (st != hipSuccess) return fail(nullptr, BB_ERR_HIP, std::string("bb_afterstates_pos: ") + hipGetErrorString(st));
+  return BB_OK;
+}
+
+int bb_afterstates(bb_env* env, const bb_afterstate_out* out, void* stream) {
+  if (!env) return BB_ERR_ARG;
+  if (!out) return fail(env, BB_ERR_ARG, "bb_afterstates: out is NULL");
+  if (status_fail(env, "bb_afterstates") != BB_OK) return BB_ERR_DEVICE;  // the state an incomplete launch left
+  if (env->broken) return broken_fail(env, "bb_afterstates");
+  DeviceGuard g(env->device);
+  hipError_t st = launch_afterstates(env->d.board, env->d.hand, env->d.combo, env->d.prev, env->n, env->cfg, *out,
+                                     (hipStream_t)stream);
+  if (st != hipSuccess) return hip_fail(env, st, "bb_afterstates");
+  return BB_OK;
+}
+
+int bb_greedy_actions_pos(const bb_positions* pos, int32_t n, const bb_greedy_weights* w, int32_t* d_action,
+                          int64_t* d_value, void* stream) {
+  if (!pos || !pos->board || !pos->hand || n <= 0 || !w || !d_action)
+    return fail(nullptr, BB_ERR_ARG,
+                "bb_greedy_actions_pos: positions (board, hand), n > 0, weights and d_action are required");
+  hipError_t st = launch_greedy(pos->board, pos->hand, pos->combo, pos->prev, n, *w, d_action, d_value,
+                                (hipStream_t)stream);
+  if (st != hipSuccess)
+    return fail(nullptr, BB_ERR_HIP, std::string("bb_greedy_actions_pos: ") + hipGetErrorString(st));
+  return BB_OK;
+}
+
+int bb_greedy_actions(bb_env* env, const bb_greedy_weights* w, int32_t* d_action, int64_t* d_value, void* stream) {
+  if (!env) return BB_ERR_ARG;
+  if (!w || !d_action) return fail(env, BB_ERR_ARG, "bb_greedy_actions: weights and d_action are required");
+  if (status_fail(env, "bb_greedy_actions") != BB_OK) return BB_ERR_DEVICE;
+  if (env->broken) return broken_fail(env, "bb_greedy_actions");
+  DeviceGuard g(env->device);
+  hipError_t st = launch_greedy(env->d.board, env->d.hand, env->d.combo, env->d.prev, env->n, *w, d_action, d_value,
+                                (hipStream_t)stream);
+  if (st != hipSuccess) return hip_fail(env, st, "bb_greedy_actions");
+  return BB_OK;
+}
+
 int bb_masked_sample(const float* d_logits, const uint64_t* d_mask_bits, int32_t n, const float* d_uniform,
                      uint64_t seed, uint64_t step, uint64_t env_offset, int32_t deterministic,
                      const int64_t* d_action_in, int64_t* d_action, float* d_logp, float* d_entropy,

@@ -345,6 +345,105 @@ Out step_env(bb_env* e, int i, int act, bb_info* info, int64_t* final_score, int
   return o;
 }
 
+// ---------------------------------------------------------------------------
+// one-ply lookahead (bbvec.h bb_afterstates / bb_greedy_actions): the host twin of csrc/bb_lookahead.hip
+// ---------------------------------------------------------------------------
+struct After {
+  bool legal, dead, refill;
+  uint64_t board;
+  int ncells, lines, holes, centre, filled, mobility;
+  int64_t gained;
+};
+
+// engine.py:326-346 (legal), 390-431 (place, clear, combo, score) and the mobility of the slots that stay
+// unused on the new board (engine.py:348-362)
+After eval_action(uint64_t B, uint32_t hand, int combo, int act) {
+  After a{};
+  const int p = act >> 6, cell = act & 63;
+  const uint32_t used0 = (hand >> 18) & 7u, id = hand_id(hand, p);
+  if (id >= (uint32_t)kPieces || ((hand >> 21) & 1u) || ((used0 >> p) & 1u)) return a;
+  const Piece& pc = T().p[id];
+  if (!((pc.anchors >> cell) & 1ull) || ((pc.shape << cell) & B)) return a;
+  a.legal = true;
+  a.ncells = pc.n;
+  int rows, cols;
+  a.board = clear_full(B | (pc.shape << cell), rows, cols);
+  a.lines = rows + cols;
+  const int combo1 = a.lines > 0 ? combo + 1 : 0;
+  const int cm = a.lines < 4 ? a.lines : 4;
+  const int streak = combo1 + 1 < 8 ? combo1 + 1 : 8;
+  a.gained = a.lines > 0 ? a.ncells + (int64_t)(a.lines * 8 * 10) * cm * streak : (int64_t)a.ncells;
+  const uint32_t used = used0 | (1u << p);
+  a.refill = used == 7u;
+  for (int q = 0; q < 3; ++q)
+    if (!((used >> q) & 1u) && hand_id(hand, q) < (uint32_t)kPieces)
+      a.mobility += __builtin_popcountll(anchors_of((int)hand_id(hand, q), a.board));
+  a.dead = !a.refill && a.mobility == 0;
+  a.holes = count_holes(a.board);
+  a.centre = __builtin_popcountll(a.board & kCenter);
+  a.filled = __builtin_popcountll(a.board);
+  return a;
+}
+
+// _calculate_reward (block_blast_env.py:158-193) with game_over = dead, fp64 in the reference's order (the
+// library is built with -ffp-contract=off), as step_env above
+double after_reward(const After& a, const bb_reward_cfg& c, uint32_t prev) {
+  const int cm = a.lines > 0 ? (a.lines < 4 ? a.lines : 4) : 1;
+  double R = 0.0;
+  R += (double)a.ncells * c.block_placed;
+  R += c.survival_bonus;
+  if (a.lines > 0) {
+    double lr = (double)a.lines * c.line_clear_base;
+    lr *= (double)cm;
+    R += lr;
+    if (cm > 1) R += (double)(cm - 1) * c.combo_multiplier_bonus;
+  }
+  if (a.dead) R += c.game_over_penalty;
+  const int dh = a.holes - (int)(prev & 0xFFu);
+  if (dh > 0) R += (double)dh * c.hole_penalty;
+  if (a.centre <= (int)(prev >> 8)) R += c.center_bonus * 0.1;
+  return R;
+}
+
+void afterstates_host(const uint64_t* board, const uint32_t* hand, const int32_t* combo, const uint16_t* prev,
+                      int32_t n, const bb_reward_cfg& cfg, const bb_afterstate_out& out) {
+#pragma omp parallel for schedule(static)
+  for (int32_t i = 0; i < n; ++i) {
+    for (int act = 0; act < 192; ++act) {
+      const After a = eval_action(board[i], hand[i], combo ? combo[i] : 0, act);
+      const size_t o = (size_t)i * 192 + (size_t)act;
+      if (out.board) out.board[o] = a.legal ? a.board : board[i];
+      if (out.reward_f64) out.reward_f64[o] = a.legal ? after_reward(a, cfg, prev ? prev[i] : 0u) : -10.0;
+      if (out.score_gained) out.score_gained[o] = a.legal ? (int32_t)a.gained : 0;
+      if (out.aux)
+        out.aux[o] = a.legal ? 1u | ((uint32_t)a.dead << 1) | ((uint32_t)a.refill << 2) | ((uint32_t)a.lines << 8) |
+                                   ((uint32_t)a.holes << 12) | ((uint32_t)a.centre << 19) |
+                                   ((uint32_t)a.mobility << 24)
+                             : 0u;
+    }
+  }
+}
+
+void greedy_host(const uint64_t* board, const uint32_t* hand, const int32_t* combo, int32_t n,
+                 const bb_greedy_weights& w, int32_t* action, int64_t* value) {
+#pragma omp parallel for schedule(static)
+  for (int32_t i = 0; i < n; ++i) {
+    int64_t best = INT64_MIN;
+    int32_t best_a = 0;
+    for (int act = 0; act < 192; ++act) {  // ascending: a later action must be strictly better
+      const After a = eval_action(board[i], hand[i], combo ? combo[i] : 0, act);
+      if (!a.legal) continue;
+      const int64_t v = (int64_t)w.lines * a.lines + (int64_t)w.score * a.gained + (int64_t)w.holes * a.holes +
+                        (int64_t)w.filled * a.filled + (int64_t)w.centre * a.centre +
+                        (int64_t)w.mobility * a.mobility + (int64_t)w.dead * (int)a.dead +
+                        (int64_t)w.refill * (int)a.refill;
+      if (v > best) best = v, best_a = act;
+    }
+    action[i] = best_a;
+    if (value) value[i] = best;
+  }
+}
+
 }  // namespace
 
 #ifndef BB_BUILD_ID
@@ -585,6 +684,41 @@ int bb_random_actions(const uint64_t* d_mask_bits, int32_t n, uint64_t seed, uin
   if (!d_mask_bits || !d_actions || n < 0) return fail(nullptr, BB_ERR_ARG, "bb_random_actions: bad arguments");
   for (int32_t i = 0; i < n; ++i)
     d_actions[i] = policy_action(&d_mask_bits[3 * (size_t)i], philox_w0(seed, env_offset + (uint64_t)i, step));
+  return BB_OK;
+}
+
+int bb_afterstates_pos(const bb_positions* pos, int32_t n, const bb_reward_cfg* cfg, const bb_afterstate_out* out,
+                       void* stream) {
+  (void)stream;
+  if (!pos || !pos->board || !pos->hand || n <= 0 || !cfg || !out)
+    return fail(nullptr, BB_ERR_ARG, "bb_afterstates_pos: positions (board, hand), n > 0, cfg and out are required");
+  afterstates_host(pos->board, pos->hand, pos->combo, pos->prev, n, *cfg, *out);
+  return BB_OK;
+}
+
+int bb_afterstates(bb_env* env, const bb_afterstate_out* out, void* stream) {
+  (void)stream;
+  if (!env) return BB_ERR_ARG;
+  if (!out) return fail(env, BB_ERR_ARG, "bb_afterstates: out is NULL");
+  afterstates_host(env->board.data(), env->hand.data(), env->combo.data(), env->prev.data(), env->n, env->cfg, *out);
+  return BB_OK;
+}
+
+int bb_greedy_actions_pos(const bb_positions* pos, int32_t n, const bb_greedy_weights* w, int32_t* d_action,
+                          int64_t* d_value, void* stream) {
+  (void)stream;
+  if (!pos || !pos->board || !pos->hand || n <= 0 || !w || !d_action)
+    return fail(nullptr, BB_ERR_ARG,
+                "bb_greedy_actions_pos: positions (board, hand), n > 0, weights and d_action are required");
+  greedy_host(pos->board, pos->hand, pos->combo, n, *w, d_action, d_value);
+  return BB_OK;
+}
+
+int bb_greedy_actions(bb_env* env, const bb_greedy_weights* w, int32_t* d_action, int64_t* d_value, void* stream) {
+  (void)stream;
+  if (!env) return BB_ERR_ARG;
+  if (!w || !d_action) return fail(env, BB_ERR_ARG, "bb_greedy_actions: weights and d_action are required");
+  greedy_host(env->board.data(), env->hand.data(), env->combo.data(), env->n, *w, d_action, d_value);
   return BB_OK;
 }
 

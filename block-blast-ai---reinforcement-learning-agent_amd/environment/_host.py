@@ -78,6 +78,21 @@ def info_dict(rec, with_last_move: bool) -> dict:
     return info
 
 
+def afterstates_dict(out: dict) -> dict:
+    """Device outputs of bb_afterstates ([N, 192] tensors) -> numpy arrays with the aux word unpacked:
+    board u64, reward f64, score_gained i32, legal / dead / refill bool, lines / holes / centre / mobility i32."""
+    from runtime.kernels import unpack_aux
+
+    res = {
+        "board": out["board"].cpu().numpy().view(np.uint64),
+        "reward": out["reward"].cpu().numpy(),
+        "score_gained": out["score_gained"].cpu().numpy(),
+    }
+    for k, v in unpack_aux(out["aux"].cpu().numpy()).items():
+        res[k] = v if v.dtype == bool else v.astype(np.int32)
+    return res
+
+
 def reset_info() -> dict:
     """Info right after a reset (empty board, zero counters)."""
     return {

@@ -108,6 +108,13 @@ class BlockBlastEnv(Env):
     def get_valid_actions(self) -> List[int]:
         return np.where(self.get_action_mask())[0].tolist()
 
+    def afterstates(self) -> Dict[str, np.ndarray]:
+        """What each of the 192 actions would lead to from the current state, without playing it (bb_afterstates;
+        the reference has no counterpart): arrays of shape (192,) -- board (u64 bits), reward (fp64, as step
+        would return it when no new hand is drawn), score_gained, legal, dead, refill, lines, holes, centre,
+        mobility.  The state and the piece stream are not touched."""
+        return {k: v[0] for k, v in _host.afterstates_dict(self._dev.afterstates()).items()}
+
     def sample_valid_action(self) -> int:
         valid = self.get_valid_actions()
         if not valid:

@@ -121,6 +121,12 @@ class VectorizedBlockBlastEnv:
         self.dev.obs(mask_i8=self._mask)
         return self._mask.cpu().numpy().astype(bool)
 
+    def afterstates(self) -> Dict[str, np.ndarray]:
+        """What each of the 192 actions of every env would lead to, without playing it (bb_afterstates, one
+        launch; the reference has no counterpart): arrays of shape (num_envs, 192) -- board (u64 bits), reward
+        (fp64), score_gained, legal, dead, refill, lines, holes, centre, mobility."""
+        return _host.afterstates_dict(self.dev.afterstates())
+
     def sample_valid_actions(self) -> np.ndarray:
         """Per-env uniform choice among legal actions with numpy's global RNG,
         like BlockBlastEnv.sample_valid_action (block_blast_env.py:318-323)."""

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""CLI: python evaluate.py --checkpoint checkpoints/best.pt [--episodes 100] [--deterministic] [--seed 42]"""
+"""CLI: python evaluate.py --checkpoint checkpoints/best.pt [--episodes 100] [--deterministic] [--seed 42]
+        python evaluate.py --agent greedy|random [--episodes 100] [--max-moves 150]   (baselines, no checkpoint)"""
 import sys
 from pathlib import Path
 

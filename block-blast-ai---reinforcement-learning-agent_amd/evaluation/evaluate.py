@@ -9,6 +9,11 @@ for all unfinished games in one forward pass, each game's statistics latched
 at its termination.  With ``deterministic=True`` (argmax) and the agent in
 eval mode this gives the same per-episode results as the sequential loop.
 ``render=True`` uses the sequential single-env path so games can be shown.
+
+Beyond the reference: ``--agent greedy`` / ``--agent random`` evaluate the untrained baselines of
+``agents/greedy.py`` on the same seeds (no checkpoint needed), so a checkpoint's scores have something to be
+compared with.  An agent with ``act_env(env_batch, out)`` picks its actions from the device env itself (the
+fused one-ply kernel); every other agent goes through ``act_device`` as before.
 """
 from __future__ import annotations
 
@@ -66,7 +71,8 @@ def _evaluate_sequential(agent, num_episodes: int, deterministic: bool, render: 
 def evaluate_agent(agent, num_episodes: int = 100, deterministic: bool = True, render: bool = False,
                    seed: int = 42, max_moves: int = 100_000, record_actions: bool = False) -> Dict[str, Any]:
     """evaluate.py:23-90 (same keys in the returned dict).  record_actions: also return every episode's
-    action sequence under "actions" (for replaying the games elsewhere, e.g. through the oracle)."""
+    action sequence under "actions" (for replaying the games elsewhere, e.g. through the oracle).  A game still
+    running after max_moves moves is cut off there and reports its score, lines and max combo so far."""
     agent.eval()
     if render:
         return _evaluate_sequential(agent, num_episodes, deterministic, render, seed, record_actions)
@@ -85,10 +91,14 @@ def evaluate_agent(agent, num_episodes: int = 100, deterministic: bool = True, r
     info64 = env.info.view(torch.int64).view(n, 7)
     info32 = env.info.view(torch.int32).view(n, 14)
     log = []
+    act_env = getattr(agent, "act_env", None)
     for step in range(max_moves):
-        env.obs(x=x, mask_bits=mb)
-        a, _, _ = agent.act_device(x, mb, deterministic=deterministic)
-        act.copy_(a)
+        if act_env is not None:
+            act_env(env, act)
+        else:
+            env.obs(x=x, mask_bits=mb)
+            a, _, _ = agent.act_device(x, mb, deterministic=deterministic)
+            act.copy_(a)
         if record_actions:
             log.append(act.clone())
         env.step(act, want_info=True)
@@ -100,6 +110,10 @@ def evaluate_agent(agent, num_episodes: int = 100, deterministic: bool = True, r
         alive &= ~term
         if step % 16 == 15 and not bool(alive.any()):
             break
+    if bool(alive.any()):  # games cut off by max_moves: their statistics so far (a finished game latched its own)
+        st = env.state()
+        for col, key in enumerate(("score", "lines", "max_combo")):
+            rec[:, col] = torch.where(alive, torch.from_numpy(st[key].astype(np.int64)).to(dev), rec[:, col])
     out = rec.cpu().numpy()
     lengths = length.cpu().numpy()
     env.close()
@@ -136,24 +150,39 @@ def print_results(results: Dict[str, Any]) -> None:
 def main() -> None:
     """evaluate.py:119-184 (same flags)."""
     ap = argparse.ArgumentParser(description="Evaluate Block Blast AI")
-    ap.add_argument("--checkpoint", type=str, required=True)
+    ap.add_argument("--agent", choices=("ppo", "greedy", "random"), default="ppo",
+                    help="ppo: the checkpoint's policy; greedy / random: the untrained baselines")
+    ap.add_argument("--checkpoint", type=str, default=None, help="required for --agent ppo")
     ap.add_argument("--episodes", type=int, default=100)
     ap.add_argument("--deterministic", action="store_true")
     ap.add_argument("--render", action="store_true")
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--output", type=str, default=None)
+    ap.add_argument("--max-moves", type=int, default=100_000, help="cut every game off after this many moves")
+    ap.add_argument("--weights", type=str, default=None, help="--agent greedy: a JSON file GreedyAgent.save wrote")
+    ap.add_argument("--device", type=str, default=None, help="baselines only: cpu = the host backend")
     args = ap.parse_args()
-    if not os.path.exists(args.checkpoint):
-        print(f"Checkpoint not found: {args.checkpoint}")
-        sys.exit(1)
-    from agents.ppo import PPOAgent
-    from utils.device import get_device
+    if args.agent == "ppo":
+        if args.checkpoint is None:
+            ap.error("--checkpoint is required for --agent ppo")
+        if not os.path.exists(args.checkpoint):
+            print(f"Checkpoint not found: {args.checkpoint}")
+            sys.exit(1)
+        from agents.ppo import PPOAgent
+        from utils.device import get_device
 
-    agent = PPOAgent(device=get_device())
-    agent.load(args.checkpoint)
-    print(f"Loaded model from {args.checkpoint}")
+        agent = PPOAgent(device=get_device())
+        agent.load(args.checkpoint)
+        print(f"Loaded model from {args.checkpoint}")
+    else:
+        from agents.greedy import GreedyAgent, RandomAgent
+
+        agent = GreedyAgent(device=args.device) if args.agent == "greedy" else RandomAgent(device=args.device)
+        if args.weights:
+            agent.load(args.weights)
+        print(f"Baseline agent: {args.agent}")
     res = evaluate_agent(agent, num_episodes=args.episodes, deterministic=args.deterministic, render=args.render,
-                         seed=args.seed)
+                         seed=args.seed, max_moves=args.max_moves)
     print_results(res)
     if args.output:
         with open(args.output, "w") as f:

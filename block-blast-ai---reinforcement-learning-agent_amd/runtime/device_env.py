@@ -239,6 +239,32 @@ class DeviceEnvBatch:
             "bb_random_actions", None, self.lib,
         )
 
+    # ------------------------------------------------------------ lookahead
+    def afterstates(self, out: Optional[dict] = None) -> dict:
+        """bb_afterstates on the live state: for each of the 192 actions of every env the board it leads to,
+        its fp64 reward, its score and the packed aux word (bbvec.h), [N, 192] each.  ``out``: a dict with any
+        of "board" i64, "reward" f64, "score_gained" i32, "aux" i32 tensors to write (missing = not computed);
+        None = all four, freshly allocated.  Reads the state and changes nothing, the piece stream included."""
+        from . import kernels as K
+
+        out = K.afterstate_outputs(self.num_envs, self.device) if out is None else out
+        o = K._afterstate_out(out, self.num_envs, self.device)
+        L.check(self.lib.bb_afterstates(self.handle, C.byref(o), _stream(self.device)), "bb_afterstates",
+                self.handle, self.lib)
+        return out
+
+    def greedy_actions(self, out: torch.Tensor, weights, value: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """bb_greedy_actions on the live state: out (int32 [N]) receives every env's best legal action under
+        the one-ply greedy value of ``weights`` (a dict of bb_greedy_weights fields or an L.GreedyWeights), ties
+        to the lowest action, 0 where nothing is legal; value (int64 [N], optional) that value."""
+        n = self.num_envs
+        for t, dt in ((out, torch.int32), (value, torch.int64)):
+            assert t is None or (t.dtype == dt and t.device == self.device and t.is_contiguous() and t.numel() == n)
+        w = weights if isinstance(weights, L.GreedyWeights) else L.greedy_weights(weights)
+        L.check(self.lib.bb_greedy_actions(self.handle, C.byref(w), _ptr(out), _ptr(value), _stream(self.device)),
+                "bb_greedy_actions", self.handle, self.lib)
+        return out
+
     # ------------------------------------------------------------ host copies
     def state(self) -> dict:
         n = self.num_envs

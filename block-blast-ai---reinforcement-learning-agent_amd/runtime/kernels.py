@@ -1,6 +1,8 @@
 """torch-facing wrappers of the rollout-side HIP kernels (csrc/bb_ppo.hip,
-csrc/bb_env.hip expand).  Inputs/outputs are device tensors; launches go on
-torch's current stream; nothing here falls back to CPU."""
+csrc/bb_env.hip expand, csrc/bb_lookahead.hip).  Inputs/outputs are device
+tensors; launches go on torch's current stream; nothing here falls back to
+CPU (the lookahead wrappers run on the host backend only for tensors the
+caller put on the CPU)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -131,6 +133,100 @@ def gather_obs(board: torch.Tensor, hand: torch.Tensor, mask_bits: torch.Tensor,
         "bb_gather_obs",
     )
     return x, mf
+
+
+# ---------------------------------------------------------------------------
+# One-ply lookahead (csrc/bb_lookahead.hip; csrc/bb_host.cpp for CPU tensors)
+# ---------------------------------------------------------------------------
+AFTERSTATE_DTYPES = {"board": torch.int64, "reward": torch.float64, "score_gained": torch.int32, "aux": torch.int32}
+
+
+def _look_lib(dev: torch.device):
+    """(library, stream) of the lookahead entry points for tensors on ``dev``: libbbvec.so for a HIP device, the
+    host backend for CPU tensors (chosen by where the caller's tensors live, never as a fallback)."""
+    if dev.type == "cpu":
+        return L.load_host(), None
+    return L.load(), _s(dev)
+
+
+def _positions(board, hand, combo, prev):
+    n, dev = board.numel(), board.device
+    for t, dt, name in ((board, torch.int64, "board"), (hand, torch.int32, "hand"), (combo, torch.int32, "combo"),
+                        (prev, torch.int16, "prev")):
+        if t is not None and not (t.dtype == dt and t.device == dev and t.is_contiguous() and t.numel() == n):
+            raise L.BBNativeError(f"lookahead: {name} must be a contiguous {dt} tensor of {n} elements on {dev}")
+    if n <= 0:
+        raise L.BBNativeError("lookahead: at least one position is required")
+    return L.Positions(board=board.data_ptr(), hand=hand.data_ptr(),
+                       combo=combo.data_ptr() if combo is not None else None,
+                       prev=prev.data_ptr() if prev is not None else None), n, dev
+
+
+def afterstate_outputs(n: int, dev, want=("board", "reward", "score_gained", "aux")) -> dict:
+    """Fresh [n, 192] output tensors for ``afterstates`` (the bit patterns of the u64 boards and u32 aux words
+    in torch's signed types)."""
+    return {k: torch.empty((n, 192), dtype=AFTERSTATE_DTYPES[k], device=dev) for k in want}
+
+
+def _afterstate_out(out: dict, n: int, dev) -> L.AfterstateOut:
+    o = L.AfterstateOut()
+    for k, field in (("board", "board"), ("reward", "reward_f64"), ("score_gained", "score_gained"), ("aux", "aux")):
+        t = out.get(k)
+        if t is None:
+            continue
+        if not (t.dtype == AFTERSTATE_DTYPES[k] and t.device == dev and t.is_contiguous() and t.numel() == n * 192):
+            raise L.BBNativeError(f"afterstates: {k} must be a contiguous {AFTERSTATE_DTYPES[k]} [{n}, 192] on {dev}")
+        setattr(o, field, t.data_ptr())
+    return o
+
+
+def afterstates(board: torch.Tensor, hand: torch.Tensor, combo: Optional[torch.Tensor] = None,
+                prev: Optional[torch.Tensor] = None, reward_config: Optional[dict] = None,
+                out: Optional[dict] = None) -> dict:
+    """bb_afterstates_pos: the result of each of the 192 actions of every position, in one launch.  board int64
+    [n] (bit r*8+c), hand int32 [n] (packed hand word), combo int32 [n] or None (0), prev int16 [n] or None
+    (prev_holes | centre cells << 8).  ``out``: a dict with any of "board" i64, "reward" f64, "score_gained" i32,
+    "aux" i32 [n, 192] tensors to write (missing = not computed); None = all four, freshly allocated.  Returns
+    the dict.  ``unpack_aux`` splits the aux word."""
+    pos, n, dev = _positions(board, hand, combo, prev)
+    from .device_env import DEFAULT_REWARDS
+
+    rw = dict(DEFAULT_REWARDS)
+    if reward_config:
+        rw.update(reward_config)
+    out = afterstate_outputs(n, dev) if out is None else out
+    o = _afterstate_out(out, n, dev)
+    lib, stream = _look_lib(dev)
+    L.check(lib.bb_afterstates_pos(C.byref(pos), n, C.byref(L.reward_cfg(rw)), C.byref(o), stream),
+            "bb_afterstates_pos", lib=lib)
+    return out
+
+
+def greedy_actions(board: torch.Tensor, hand: torch.Tensor, weights, combo: Optional[torch.Tensor] = None,
+                   action: Optional[torch.Tensor] = None, value: Optional[torch.Tensor] = None,
+                   want_value: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """bb_greedy_actions_pos: per position the legal action with the largest one-ply greedy value (ties to the
+    lowest action; no legal action: 0 and INT64_MIN), fused.  weights: a dict of bb_greedy_weights fields or an
+    ``L.GreedyWeights``.  Returns (action int32 [n], value int64 [n] or None)."""
+    pos, n, dev = _positions(board, hand, combo, None)
+    w = weights if isinstance(weights, L.GreedyWeights) else L.greedy_weights(weights)
+    action = torch.empty(n, dtype=torch.int32, device=dev) if action is None else action
+    if value is None and want_value:
+        value = torch.empty(n, dtype=torch.int64, device=dev)
+    for t, dt in ((action, torch.int32), (value, torch.int64)):
+        if t is not None and not (t.dtype == dt and t.device == dev and t.is_contiguous() and t.numel() == n):
+            raise L.BBNativeError(f"greedy_actions: outputs must be contiguous {dt} tensors of {n} elements on {dev}")
+    lib, stream = _look_lib(dev)
+    L.check(lib.bb_greedy_actions_pos(C.byref(pos), n, C.byref(w), _p(action), _p(value), stream),
+            "bb_greedy_actions_pos", lib=lib)
+    return action, value
+
+
+def unpack_aux(aux) -> dict:
+    """The fields of the afterstate aux word (bbvec.h): works on a torch tensor or a numpy array."""
+    a = aux.to(torch.int64) & 0xFFFFFFFF if isinstance(aux, torch.Tensor) else (aux.astype("int64") & 0xFFFFFFFF)
+    return {"legal": (a & 1) != 0, "dead": (a & 2) != 0, "refill": (a & 4) != 0, "lines": (a >> 8) & 15,
+            "holes": (a >> 12) & 127, "centre": (a >> 19) & 31, "mobility": (a >> 24) & 255}
 
 
 # ---------------------------------------------------------------------------

@@ -111,6 +111,31 @@ class StateView(C.Structure):
     ]
 
 
+class Positions(C.Structure):
+    """bb_positions: device columns [n]; combo / prev may be NULL (= 0)."""
+    _fields_ = [("board", C.c_void_p), ("hand", C.c_void_p), ("combo", C.c_void_p), ("prev", C.c_void_p)]
+
+
+class AfterstateOut(C.Structure):
+    """bb_afterstate_out: device arrays [n][192], any may be NULL."""
+    _fields_ = [("board", C.c_void_p), ("reward_f64", C.c_void_p), ("score_gained", C.c_void_p), ("aux", C.c_void_p)]
+
+
+GREEDY_FIELDS = ("lines", "score", "holes", "filled", "centre", "mobility", "dead", "refill")
+
+
+class GreedyWeights(C.Structure):
+    """bb_greedy_weights: the eight int32 weights of the one-ply greedy value."""
+    _fields_ = [(k, C.c_int32) for k in GREEDY_FIELDS]
+
+
+def greedy_weights(weights: dict) -> GreedyWeights:
+    unknown = set(weights) - set(GREEDY_FIELDS)
+    if unknown:
+        raise ValueError(f"unknown greedy weights {sorted(unknown)}; the fields are {GREEDY_FIELDS}")
+    return GreedyWeights(**{k: int(weights.get(k, 0)) for k in GREEDY_FIELDS})
+
+
 _P = C.c_void_p
 _I32 = C.c_int32
 _U64 = C.c_uint64
@@ -137,6 +162,10 @@ SIGNATURES = {
     "bb_set_state": (C.c_int, [_P, C.POINTER(StateView)]),
     "bb_debug_counters": (C.c_int, [_P, _P]),
     "bb_random_actions": (C.c_int, [_P, _I32, _U64, _U64, _U64, _P, _P]),
+    "bb_afterstates_pos": (C.c_int, [C.POINTER(Positions), _I32, C.POINTER(RewardCfg), C.POINTER(AfterstateOut), _P]),
+    "bb_afterstates": (C.c_int, [_P, C.POINTER(AfterstateOut), _P]),
+    "bb_greedy_actions_pos": (C.c_int, [C.POINTER(Positions), _I32, C.POINTER(GreedyWeights), _P, _P, _P]),
+    "bb_greedy_actions": (C.c_int, [_P, C.POINTER(GreedyWeights), _P, _P, _P]),
     "bb_masked_sample": (C.c_int, [_P, _P, _I32, _P, _U64, _U64, _U64, _I32, _P, _P, _P, _P, _P]),
     "bb_masked_sample_dstep": (C.c_int, [_P, _P, _I32, _U64, _P, _U64, _U64, _I32, _P, _P, _P, _P]),
     "bb_gae": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _F, _F, _P, _P, _P]),
@@ -202,7 +231,8 @@ SIGNATURES = {
 # the env entry points, which the host backend (libbbvec_host.so) exports too
 HOST_SYMBOLS = ("bb_abi_version", "bb_build_id", "bb_create", "bb_destroy", "bb_last_error", "bb_num_envs", "bb_pcg64_seed",
                 "bb_seed", "bb_reset", "bb_step", "bb_rollout", "bb_sync", "bb_obs", "bb_device_ptrs", "bb_snapshot",
-                "bb_get_state", "bb_set_state", "bb_random_actions")
+                "bb_get_state", "bb_set_state", "bb_random_actions", "bb_afterstates_pos", "bb_afterstates",
+                "bb_greedy_actions_pos", "bb_greedy_actions")
 
 _lib = None
 _host = None

@@ -44,7 +44,10 @@ extern "C" {
                                  bb_conv3x3_wgrad_partial / _reduce / _chunks, bb_bn_backward_red,
                                  bb_conv_in_forward_prep, bb_linear_bgrad2, bb_conv3x3_forward_stats,
                                  bb_conv3x3_stats_blocks, bb_bn_forward_part, bb_conv3x3_forward_bstats,
-                                 bb_bn_backward_part */
+                                 bb_bn_backward_part;
+                                 (additive, still 8) bb_positions / bb_afterstate_out / bb_greedy_weights with
+                                 bb_afterstates(_pos) and bb_greedy_actions(_pos): one-ply lookahead
+                                 (engine.py:326-346, 390-454; block_blast_env.py:148-193) */
 
 #define BB_OK 0
 #define BB_ERR_ARG (-1)
@@ -250,6 +253,79 @@ int bb_debug_counters(bb_env* env, uint64_t* h_out);
 int bb_random_actions(const uint64_t* d_mask_bits, int32_t n, uint64_t seed,
                       uint64_t step, uint64_t env_offset, int32_t* d_actions,
                       void* stream);
+
+/* ---- one-ply lookahead ------------------------------------------------------
+ * The deterministic half of a step, for all 192 actions of a position at once
+ * and without touching any env: what GameEngine.can_place_piece (engine.py:
+ * 326-346) accepts, what GameEngine.make_move (engine.py:390-454) does to the
+ * board, combo and score before it draws a new hand, and the reward
+ * BlockBlastEnv._calculate_reward (block_blast_env.py:148-193) gives for it.
+ * The reference has no such call (it would be copy.deepcopy(env).step(a) for
+ * every a); afterstate learning, one-ply policy improvement and tree search
+ * start from it.
+ *
+ * A position is (board, packed hand word as in bb_state_view, combo, prev =
+ * prev_holes | filled centre cells << 8).  Action a = p*64 + r*8 + c is legal
+ * iff the hand's game-over bit is clear, slot p is unused and the piece fits
+ * at (r,c): exactly the actions bb_step accepts.
+ *   illegal a: board = the position's board, reward_f64 = -10.0 (block_blast_
+ *     env.py:240-245), score_gained = 0, aux = 0.
+ *   legal a: board = the board after the piece is placed and every full row
+ *     and column (found on the same board) is cleared; lines = rows + cols;
+ *     combo' = lines > 0 ? combo + 1 : 0; score_gained = cells + (lines > 0 ?
+ *     lines*8*10 * min(lines,4) * min(combo'+1,8) : 0) (engine.py:274-312, 427).
+ *     refill = all three slots used after the move: the next hand is a chance
+ *     outcome, so whether the game then ends is not reported.  mobility = the
+ *     number of legal (slot, r, c) placements of the still-unused slots on the
+ *     new board (0 when refill); dead = !refill && mobility == 0, which for a
+ *     non-refill move is bb_step's `terminated`.  reward_f64 = _calculate_
+ *     reward with game_over = dead, the new board's holes against prev_holes
+ *     and its centre cells against prev's, in fp64 in the reference's
+ *     operation order with no FMA contraction: bit-equal to bb_step's
+ *     reward_f64 for a non-refill move, and for a refill move whenever that
+ *     step does not terminate.
+ *     aux: bit 0 legal, bit 1 dead, bit 2 refill, bits 8-11 lines, 12-18 holes
+ *     of the new board (board.py:195-216), 19-23 its filled centre cells
+ *     (rows / cols 2-5, board.py:236-243), 24-31 mobility.
+ *     (A position reachable in play clears at most 6 lines with one piece; a
+ *     crafted board with more than 15 full lines would not fit the lines
+ *     field.  A slot whose piece id is not below BB_NUM_PIECES fits nowhere.)
+ * Outputs are [n][192], action-major per position; any may be NULL.  The
+ * handle forms read the handle's live columns and reward config and change
+ * nothing, the RNG included; like bb_step they refuse a handle in
+ * BB_ERR_DEVICE / BB_ERR_STATE.  Asynchronous on `stream`, no allocation, no
+ * sync (graph-capturable); indexing is 64-bit. */
+typedef struct bb_positions {
+  const uint64_t* board;  /* [n] bit r*8+c                                     */
+  const uint32_t* hand;   /* [n] packed hand word (bb_state_view)              */
+  const int32_t* combo;   /* [n] combo_count, NULL = 0                         */
+  const uint16_t* prev;   /* [n] prev_holes | centre cells << 8, NULL = 0      */
+} bb_positions;           /* device pointers */
+
+typedef struct bb_afterstate_out {
+  uint64_t* board;        /* [n][192] */
+  double* reward_f64;     /* [n][192] */
+  int32_t* score_gained;  /* [n][192] */
+  uint32_t* aux;          /* [n][192] */
+} bb_afterstate_out;      /* device pointers, any may be NULL */
+
+/* Weights of the one-ply greedy value, an exact int64 sum (no floats):
+ * lines*lines' + score*score_gained + holes*holes' + filled*popcount(board') +
+ * centre*centre' + mobility*mobility + dead*dead + refill*refill. */
+typedef struct bb_greedy_weights {
+  int32_t lines, score, holes, filled, centre, mobility, dead, refill;
+} bb_greedy_weights;
+
+int bb_afterstates_pos(const bb_positions* pos, int32_t n, const bb_reward_cfg* cfg, const bb_afterstate_out* out,
+                       void* stream);
+int bb_afterstates(bb_env* env, const bb_afterstate_out* out, void* stream);
+/* The fused consumer: d_action[i] = the legal action of position i with the
+ * largest greedy value, ties to the lowest flat action; d_value[i] (NULL ok) =
+ * that value.  No legal action: action 0, value INT64_MIN.  One launch, 4 (+8)
+ * bytes written per position; the [n][192] arrays are never materialised. */
+int bb_greedy_actions_pos(const bb_positions* pos, int32_t n, const bb_greedy_weights* w, int32_t* d_action,
+                          int64_t* d_value, void* stream);
+int bb_greedy_actions(bb_env* env, const bb_greedy_weights* w, int32_t* d_action, int64_t* d_value, void* stream);
 
 /* Fused masked-categorical tail of BlockBlastNetwork.get_action_and_value
  * (network.py:173-180, 210-262; Categorical clamp semantics of torch 2.10):
