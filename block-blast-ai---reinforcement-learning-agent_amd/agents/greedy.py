@@ -1,10 +1,12 @@
-"""Baseline agents that need no training: a one-ply greedy heuristic and random legal play.
+"""Baseline agents that need no training: a one-ply greedy heuristic, a full-hand plan search and random legal play.
 
 The reference has no baseline players; these give a checkpoint's evaluation something to be compared with
 (``evaluate.py --agent greedy`` / ``--agent random`` on the same seeds).  Both choose their actions on the
 device the envs live on: ``GreedyAgent`` through the fused ``bb_greedy_actions`` kernel (the arg-max of an
 integer value over the afterstates of the 192 actions, csrc/bb_lookahead.hip), ``RandomAgent`` through the
-Philox random-legal policy ``bb_random_actions``.  ``device="cpu"`` runs them on the host backend.
+Philox random-legal policy ``bb_random_actions``.  ``HandPlanAgent`` searches every way to play out the hand
+(``bb_plan_actions``, the fused search kernel of the same file; ``evaluate.py --agent plan``).  ``device="cpu"``
+runs them on the host backend.
 """
 from __future__ import annotations
 
@@ -82,6 +84,45 @@ class GreedyAgent(BaseAgent):
         L.greedy_weights(data["weights"])
         self.weights = dict(DEFAULT_WEIGHTS)
         self.weights.update({k: int(v) for k, v in data["weights"].items()})
+
+
+class HandPlanAgent(GreedyAgent):
+    """Plays the first move of the best way to play out the whole hand: the exhaustive search of
+    ``bb_plan_actions`` over every order and placement of the unused pieces, up to ``depth`` (1..3) moves, under
+    the same integer weights (move terms summed along the sequence, state terms of its last afterstate; ties:
+    the lexicographically lowest sequence).  ``depth=1`` is ``GreedyAgent``.  One fused launch per move."""
+
+    def __init__(self, weights: Optional[Dict[str, int]] = None, depth: int = 3, device=None):
+        super().__init__(weights, device)
+        if int(depth) not in (1, 2, 3):
+            raise ValueError(f"depth must be 1, 2 or 3, not {depth}")
+        self.depth = int(depth)
+
+    def act_env(self, env_batch, out: torch.Tensor) -> torch.Tensor:
+        return env_batch.plan_actions(out, self.weights, self.depth)
+
+    def select_action(self, observation: Dict[str, Any], deterministic: bool = True) -> Tuple[int, Dict[str, Any]]:
+        """From a Gym observation (no combo count in it: see ``GreedyAgent.select_action``)."""
+        from runtime import kernels as K
+
+        bits, hand = _position_of(observation)
+        board = torch.tensor([bits - (1 << 64) if bits >= 1 << 63 else bits], dtype=torch.int64, device=self.device)
+        hand_t = torch.tensor([hand], dtype=torch.int32, device=self.device)
+        res = K.plan_actions(board, hand_t, self.weights, self.depth, want_plan=True)
+        return int(res["action"].cpu().item()), {"value": int(res["value"].cpu().item()),
+                                                 "plan": res["plan"].cpu().view(3).tolist()}
+
+    def save(self, path: str) -> None:
+        with open(path, "w") as f:
+            json.dump({"agent": "plan", "depth": self.depth, "weights": self.weights}, f, indent=2)
+
+    def load(self, path: str) -> None:
+        super().load(path)
+        with open(path) as f:
+            depth = int(json.load(f).get("depth", self.depth))
+        if depth not in (1, 2, 3):
+            raise ValueError(f"depth must be 1, 2 or 3, not {depth}")
+        self.depth = depth
 
 
 class RandomAgent(BaseAgent):

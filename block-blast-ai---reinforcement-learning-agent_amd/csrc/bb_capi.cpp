@@ -613,6 +613,30 @@ int bb_greedy_actions(bb_env* env, const bb_greedy_weights* w, int32_t* d_action
   return BB_OK;
 }
 
+// Full-hand lookahead (plan_kernel in csrc/bb_lookahead.hip).
+int bb_plan_actions_pos(const bb_positions* pos, int32_t n, const bb_greedy_weights* w, int32_t depth,
+                        const bb_plan_out* out, void* stream) {
+  if (!pos || !pos->board || !pos->hand || n <= 0 || !w || !out || !out->action || depth < 1 || depth > 3)
+    return fail(nullptr, BB_ERR_ARG,
+                "bb_plan_actions_pos: positions (board, hand), n > 0, weights, depth in 1..3 and out->action are "
+                "required");
+  hipError_t st = launch_plan(pos->board, pos->hand, pos->combo, n, *w, depth, *out, (hipStream_t)stream);
+  if (st != hipSuccess) return fail(nullptr, BB_ERR_HIP, std::string("bb_plan_actions_pos: ") + hipGetErrorString(st));
+  return BB_OK;
+}
+
+int bb_plan_actions(bb_env* env, const bb_greedy_weights* w, int32_t depth, const bb_plan_out* out, void* stream) {
+  if (!env) return BB_ERR_ARG;
+  if (!w || !out || !out->action || depth < 1 || depth > 3)
+    return fail(env, BB_ERR_ARG, "bb_plan_actions: weights, depth in 1..3 and out->action are required");
+  if (status_fail(env, "bb_plan_actions") != BB_OK) return BB_ERR_DEVICE;
+  if (env->broken) return broken_fail(env, "bb_plan_actions");
+  DeviceGuard g(env->device);
+  hipError_t st = launch_plan(env->d.board, env->d.hand, env->d.combo, env->n, *w, depth, *out, (hipStream_t)stream);
+  if (st != hipSuccess) return hip_fail(env, st, "bb_plan_actions");
+  return BB_OK;
+}
+
 int bb_masked_sample(const float* d_logits, const uint64_t* d_mask_bits, int32_t n, const float* d_uniform,
                      uint64_t seed, uint64_t step, uint64_t env_offset, int32_t deterministic,
                      const int64_t* d_action_in, int64_t* d_action, float* d_logp, float* d_entropy,

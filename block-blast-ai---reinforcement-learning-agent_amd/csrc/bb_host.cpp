@@ -444,6 +444,58 @@ void greedy_host(const uint64_t* board, const uint32_t* hand, const int32_t* com
   }
 }
 
+// ---------------------------------------------------------------------------
+// full-hand lookahead (bbvec.h bb_plan_actions): the host twin of plan_kernel in csrc/bb_lookahead.hip, a
+// plain depth-first search.  The actions are visited in ascending order at every ply and no maximal sequence
+// is a prefix of another, so the leaves come in lexicographic order and a later one must be strictly better.
+// ---------------------------------------------------------------------------
+struct PlanBest {
+  int64_t value;
+  int32_t plan[3];
+  int32_t leaves;
+};
+
+void plan_dfs(uint64_t B, uint32_t hand, int combo, int depth, int ply, int64_t sum, int32_t* seq,
+              const bb_greedy_weights& w, PlanBest& best) {
+  if ((hand >> 21) & 1u) return;  // game over: nothing is legal
+  for (int p = 0; p < 3; ++p) {
+    const uint32_t id = hand_id(hand, p);
+    if (((hand >> (18 + p)) & 1u) || id >= (uint32_t)kPieces) continue;
+    for (uint64_t m = anchors_of((int)id, B); m; m &= m - 1) {
+      const int act = p * 64 + __builtin_ctzll(m);
+      const After a = eval_action(B, hand, combo, act);
+      const int64_t s = sum + (int64_t)w.lines * a.lines + (int64_t)w.score * a.gained;
+      seq[ply] = act;
+      if (depth == 1 || a.refill || a.dead) {
+        const int64_t v = s + (int64_t)w.holes * a.holes + (int64_t)w.filled * a.filled +
+                          (int64_t)w.centre * a.centre + (int64_t)w.mobility * a.mobility +
+                          (int64_t)w.dead * (int)a.dead + (int64_t)w.refill * (int)a.refill;
+        if (best.leaves++ == 0 || v > best.value) {
+          best.value = v;
+          for (int k = 0; k < 3; ++k) best.plan[k] = k <= ply ? seq[k] : -1;
+        }
+      } else {
+        plan_dfs(a.board, hand | (1u << (18 + p)), a.lines > 0 ? combo + 1 : 0, depth - 1, ply + 1, s, seq, w, best);
+      }
+    }
+  }
+}
+
+void plan_host(const uint64_t* board, const uint32_t* hand, const int32_t* combo, int32_t n,
+               const bb_greedy_weights& w, int depth, const bb_plan_out& out) {
+#pragma omp parallel for schedule(dynamic, 1)  // the trees differ by orders of magnitude
+  for (int32_t i = 0; i < n; ++i) {
+    PlanBest best{INT64_MIN, {-1, -1, -1}, 0};
+    int32_t seq[3];
+    plan_dfs(board[i], hand[i], combo ? combo[i] : 0, depth, 0, 0, seq, w, best);
+    out.action[i] = best.leaves ? best.plan[0] : 0;
+    if (out.value) out.value[i] = best.value;
+    if (out.plan)
+      for (int k = 0; k < 3; ++k) out.plan[3 * (size_t)i + k] = best.plan[k];
+    if (out.leaves) out.leaves[i] = best.leaves;
+  }
+}
+
 }  // namespace
 
 #ifndef BB_BUILD_ID
@@ -719,6 +771,26 @@ int bb_greedy_actions(bb_env* env, const bb_greedy_weights* w, int32_t* d_action
   if (!env) return BB_ERR_ARG;
   if (!w || !d_action) return fail(env, BB_ERR_ARG, "bb_greedy_actions: weights and d_action are required");
   greedy_host(env->board.data(), env->hand.data(), env->combo.data(), env->n, *w, d_action, d_value);
+  return BB_OK;
+}
+
+int bb_plan_actions_pos(const bb_positions* pos, int32_t n, const bb_greedy_weights* w, int32_t depth,
+                        const bb_plan_out* out, void* stream) {
+  (void)stream;
+  if (!pos || !pos->board || !pos->hand || n <= 0 || !w || !out || !out->action || depth < 1 || depth > 3)
+    return fail(nullptr, BB_ERR_ARG,
+                "bb_plan_actions_pos: positions (board, hand), n > 0, weights, depth in 1..3 and out->action are "
+                "required");
+  plan_host(pos->board, pos->hand, pos->combo, n, *w, depth, *out);
+  return BB_OK;
+}
+
+int bb_plan_actions(bb_env* env, const bb_greedy_weights* w, int32_t depth, const bb_plan_out* out, void* stream) {
+  (void)stream;
+  if (!env) return BB_ERR_ARG;
+  if (!w || !out || !out->action || depth < 1 || depth > 3)
+    return fail(env, BB_ERR_ARG, "bb_plan_actions: weights, depth in 1..3 and out->action are required");
+  plan_host(env->board.data(), env->hand.data(), env->combo.data(), env->n, *w, depth, *out);
   return BB_OK;
 }
 

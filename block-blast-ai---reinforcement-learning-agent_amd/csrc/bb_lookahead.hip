@@ -173,6 +173,172 @@ greedy_kernel(LookTable t, LookPos pos, int n, bb_greedy_weights w, int32_t* __r
   }
 }
 
+// ---------------------------------------------------------------------------
+// Full-hand lookahead (bbvec.h bb_plan_actions): the exhaustive search over every order and placement of the
+// hand's unused pieces, up to `depth` plies, fused into one launch.
+//
+// One workgroup of four waves per position.
+//   ply 1: wave p < 3 takes hand slot p, lane = anchor cell (as the one-ply kernels).  A legal afterstate that
+//          ends its sequence (depth 1, refill or dead) is scored on the spot; the others are compacted by ballot
+//          / prefix popcount into an LDS list of at most 192 records.
+//   ply 2: the four waves take the records round-robin.  A record is wave-uniform (read back through
+//          readfirstlane into scalar registers); for each slot still unused, lane = ply-2 cell.
+//   ply 3: every legal, unfinished ply-2 lane loops over the set bits of its own anchor mask for the last piece
+//          (board, partial sum and combo stay in the lane's registers).  The alternative -- walk those lanes
+//          with a ballot, broadcast each one's board with readlane and evaluate the third piece for all 64 cells
+//          at once, position in scalar registers -- was 26-36% slower at depth 3 (profiles/r08/plan/ab;
+//          tools/patches/r08_plan_ply3_broadcast.diff).  The ply-2 list of a position (up to 24,576 entries)
+//          never exists.
+// Every lane keeps the best (value, key) it has seen, key = a1 << 16 | a2 << 8 | a3 with 0xFF for a ply not
+// played: the larger value wins, then the lower key, which is the lexicographic order of (a1, a2, a3) because
+// no maximal sequence is a prefix of another.  The lanes are joined by shuffles and the waves through four LDS
+// records.  Trip bounds: <= 192 records, 3 slots, 64 mask bits.  No atomics, no inline assembly.
+// ---------------------------------------------------------------------------
+constexpr int kPlanWaves = 4;
+constexpr int kPlanBlock = 64 * kPlanWaves;
+constexpr int kPlanRecords = 192;            // the legal ply-1 afterstates of one position
+constexpr int64_t kPlanMaxGrid = 1 << 14;    // more positions than this: the workgroups stride over them
+constexpr uint32_t kPlanNoKey = 0xFFFFFFFFu;  // no maximal sequence seen
+
+struct PlanRecord {
+  uint64_t board;  // B' of the ply-1 move
+  int64_t sum;     // w.lines * lines + w.score * score_gained so far
+  int32_t combo;   // combo'
+  int32_t action;  // a1
+};
+
+__device__ __forceinline__ int64_t move_terms(const bb_greedy_weights& w, const After& a) {
+  return (int64_t)w.lines * a.lines + (int64_t)w.score * a.gained;
+}
+
+__device__ __forceinline__ int64_t state_terms(const bb_greedy_weights& w, const After& a) {
+  return (int64_t)w.holes * a.holes + (int64_t)w.filled * a.filled + (int64_t)w.centre * a.centre +
+         (int64_t)w.mobility * a.mobility + (int64_t)w.dead * (int)a.dead + (int64_t)w.refill * (int)a.refill;
+}
+
+// (value, key) order of the plan choice: the larger value, then the lower key
+__device__ __forceinline__ void take_plan(int64_t& v, uint32_t& key, int64_t v2, uint32_t key2) {
+  const bool better = v2 > v || (v2 == v && key2 < key);
+  v = better ? v2 : v;
+  key = better ? key2 : key;
+}
+
+__global__ void __launch_bounds__(kPlanBlock)
+plan_kernel(LookTable t, LookPos pos, int n, bb_greedy_weights w, int depth, bb_plan_out out) {
+  __shared__ PlanRecord s_rec[kPlanRecords];
+  __shared__ int s_cnt[kHand];
+  __shared__ int64_t s_v[kPlanWaves];
+  __shared__ uint32_t s_key[kPlanWaves];
+  __shared__ int s_leaves[kPlanWaves];
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int cell = (int)(threadIdx.x & 63u);
+  for (int64_t i = blockIdx.x; i < (int64_t)n; i += gridDim.x) {
+    const uint64_t B = uniform64(pos.board[i]);
+    const uint32_t hand = uniform32(pos.hand[i]);
+    const int combo = (int)uniform32(pos.combo ? (uint32_t)pos.combo[i] : 0u);
+    int64_t best = INT64_MIN;  // below every legal value (see greedy_kernel)
+    uint32_t best_key = kPlanNoKey;
+    int leaves = 0;
+
+    // ---- ply 1
+    bool open1 = false;  // legal and not the end of its sequence
+    After a1;
+    if (wave < kHand) {
+      a1 = eval_action(t, B, hand, combo, wave, cell);
+      const bool end1 = depth == 1 || a1.refill || a1.dead;
+      open1 = a1.legal && !end1;
+      if (a1.legal && end1) {
+        best = move_terms(w, a1) + state_terms(w, a1);
+        best_key = ((uint32_t)(wave * 64 + cell) << 16) | 0xFFFFu;
+        leaves = 1;
+      }
+    }
+    const uint64_t open1_mask = __ballot(open1);
+    if (wave < kHand && cell == 0) s_cnt[wave] = __popcll(open1_mask);
+    __syncthreads();
+    const int c0 = s_cnt[0], c1 = s_cnt[1], c2 = s_cnt[2];
+    const int total = __builtin_amdgcn_readfirstlane(c0 + c1 + c2);  // <= 192
+    if (open1) {
+      const int before = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(open1_mask >> 32),
+                                                        __builtin_amdgcn_mbcnt_lo((uint32_t)open1_mask, 0u));
+      const int slot = (wave > 0 ? c0 : 0) + (wave > 1 ? c1 : 0) + before;  // < total <= kPlanRecords
+      s_rec[slot] = PlanRecord{a1.board, move_terms(w, a1), a1.combo1, wave * 64 + cell};
+    }
+    __syncthreads();
+
+    // ---- ply 2 (and 3): one record per wave and turn
+    for (int r = wave; r < total; r += kPlanWaves) {
+      const uint64_t B1 = uniform64(s_rec[r].board);
+      const int64_t sum1 = (int64_t)uniform64((uint64_t)s_rec[r].sum);
+      const int combo1 = (int)uniform32((uint32_t)s_rec[r].combo);
+      const int act1 = (int)uniform32((uint32_t)s_rec[r].action);
+      const uint32_t hand1 = hand | (1u << (18 + (act1 >> 6)));
+#pragma unroll 1
+      for (int q = 0; q < kHand; ++q) {
+        if ((hand_used(hand1) >> q) & 1u) continue;  // wave-uniform
+        const After a2 = eval_action(t, B1, hand1, combo1, q, cell);
+        const bool end2 = depth == 2 || a2.refill || a2.dead;
+        const int64_t sum2 = sum1 + move_terms(w, a2);
+        const uint32_t key2 = ((uint32_t)act1 << 16) | ((uint32_t)(q * 64 + cell) << 8);
+        if (a2.legal && end2) {
+          take_plan(best, best_key, sum2 + state_terms(w, a2), key2 | 0xFFu);
+          ++leaves;
+        }
+        // ply 3.  An unfinished ply-2 afterstate means the hand was whole: one slot is left, its piece fits
+        // somewhere and placing it ends the sequence (refill).  Each such lane walks the set bits of its own
+        // ply-3 anchor mask; the lanes' trip counts differ, the bound is the 64 bits.
+        if (a2.legal && !end2) {
+          const uint32_t hand2 = hand1 | (1u << (18 + q));
+          const int q3 = __ffs((int)(~hand_used(hand2) & 7u)) - 1;  // wave-uniform; >= 0 here
+          const uint32_t id3 = hand_id(hand2, q3);
+          uint64_t m3 = anchors_of(t.row[id3 < (uint32_t)kPieces ? id3 : 0u], a2.board);  // != 0: not dead
+          for (int it = 0; it < 64 && m3 != 0ull; ++it) {
+            const int c3 = __ffsll((unsigned long long)m3) - 1;
+            m3 &= m3 - 1ull;
+            const After a3 = eval_action(t, a2.board, hand2, a2.combo1, q3, c3);  // legal by construction
+            take_plan(best, best_key, sum2 + move_terms(w, a3) + state_terms(w, a3), key2 | (uint32_t)(q3 * 64 + c3));
+            ++leaves;
+          }
+        }
+      }
+    }
+
+    // ---- join the lanes, then the waves
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+      const int64_t v2 = __shfl_xor(best, d, 64);
+      const uint32_t k2 = (uint32_t)__shfl_xor((int)best_key, d, 64);
+      take_plan(best, best_key, v2, k2);
+      leaves += __shfl_xor(leaves, d, 64);
+    }
+    if (cell == 0) {
+      s_v[wave] = best;
+      s_key[wave] = best_key;
+      s_leaves[wave] = leaves;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+      for (int k = 1; k < kPlanWaves; ++k) {
+        take_plan(best, best_key, s_v[k], s_key[k]);
+        leaves += s_leaves[k];
+      }
+      const bool found = best_key != kPlanNoKey;
+      const int p1 = (int)(best_key >> 16), p2 = (int)((best_key >> 8) & 0xFFu), p3 = (int)(best_key & 0xFFu);
+      out.action[i] = found ? p1 : 0;
+      if (out.value) out.value[i] = best;
+      if (out.plan) {
+        out.plan[i * 3 + 0] = found ? p1 : -1;
+        out.plan[i * 3 + 1] = found && p2 != 0xFF ? p2 : -1;
+        out.plan[i * 3 + 2] = found && p3 != 0xFF ? p3 : -1;
+      }
+      if (out.leaves) out.leaves[i] = leaves;
+    }
+    // no barrier here: the next position's first LDS writes (s_cnt, s_rec) touch nothing thread 0 still reads,
+    // and its s_v / s_key / s_leaves writes come after two more barriers that thread 0 has to reach first
+  }
+}
+
 const LookTable& look_table() {
   static const LookTable t = [] {
     LookTable x;
@@ -199,6 +365,14 @@ hipError_t launch_greedy(const uint64_t* board, const uint32_t* hand, const int3
                          int n, const bb_greedy_weights& w, int32_t* action, int64_t* value, hipStream_t s) {
   const LookPos pos{board, hand, combo, prev};
   hipLaunchKernelGGL(greedy_kernel, look_grid(n), dim3(kLookBlock), 0, s, look_table(), pos, n, w, action, value);
+  return hipGetLastError();
+}
+
+hipError_t launch_plan(const uint64_t* board, const uint32_t* hand, const int32_t* combo, int n,
+                       const bb_greedy_weights& w, int depth, const bb_plan_out& out, hipStream_t s) {
+  const LookPos pos{board, hand, combo, nullptr};
+  const dim3 grid((unsigned)((int64_t)n < kPlanMaxGrid ? (int64_t)n : kPlanMaxGrid));
+  hipLaunchKernelGGL(plan_kernel, grid, dim3(kPlanBlock), 0, s, look_table(), pos, n, w, depth, out);
   return hipGetLastError();
 }
 

@@ -10,7 +10,7 @@ at its termination.  With ``deterministic=True`` (argmax) and the agent in
 eval mode this gives the same per-episode results as the sequential loop.
 ``render=True`` uses the sequential single-env path so games can be shown.
 
-Beyond the reference: ``--agent greedy`` / ``--agent random`` evaluate the untrained baselines of
+Beyond the reference: ``--agent greedy`` / ``--agent plan`` / ``--agent random`` evaluate the untrained baselines of
 ``agents/greedy.py`` on the same seeds (no checkpoint needed), so a checkpoint's scores have something to be
 compared with.  An agent with ``act_env(env_batch, out)`` picks its actions from the device env itself (the
 fused one-ply kernel); every other agent goes through ``act_device`` as before.
@@ -150,8 +150,10 @@ def print_results(results: Dict[str, Any]) -> None:
 def main() -> None:
     """evaluate.py:119-184 (same flags)."""
     ap = argparse.ArgumentParser(description="Evaluate Block Blast AI")
-    ap.add_argument("--agent", choices=("ppo", "greedy", "random"), default="ppo",
-                    help="ppo: the checkpoint's policy; greedy / random: the untrained baselines")
+    ap.add_argument("--agent", choices=("ppo", "greedy", "plan", "random"), default="ppo",
+                    help="ppo: the checkpoint's policy; greedy / plan / random: the untrained baselines "
+                         "(plan: exhaustive search over the whole hand)")
+    ap.add_argument("--depth", type=int, choices=(1, 2, 3), default=3, help="--agent plan: moves searched ahead")
     ap.add_argument("--checkpoint", type=str, default=None, help="required for --agent ppo")
     ap.add_argument("--episodes", type=int, default=100)
     ap.add_argument("--deterministic", action="store_true")
@@ -159,7 +161,8 @@ def main() -> None:
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--output", type=str, default=None)
     ap.add_argument("--max-moves", type=int, default=100_000, help="cut every game off after this many moves")
-    ap.add_argument("--weights", type=str, default=None, help="--agent greedy: a JSON file GreedyAgent.save wrote")
+    ap.add_argument("--weights", type=str, default=None,
+                    help="--agent greedy / plan: a JSON file the agent's save wrote")
     ap.add_argument("--device", type=str, default=None, help="baselines only: cpu = the host backend")
     args = ap.parse_args()
     if args.agent == "ppo":
@@ -175,11 +178,16 @@ def main() -> None:
         agent.load(args.checkpoint)
         print(f"Loaded model from {args.checkpoint}")
     else:
-        from agents.greedy import GreedyAgent, RandomAgent
+        from agents.greedy import GreedyAgent, HandPlanAgent, RandomAgent
 
-        agent = GreedyAgent(device=args.device) if args.agent == "greedy" else RandomAgent(device=args.device)
+        if args.agent == "plan":
+            agent = HandPlanAgent(device=args.device)
+        else:
+            agent = GreedyAgent(device=args.device) if args.agent == "greedy" else RandomAgent(device=args.device)
         if args.weights:
             agent.load(args.weights)
+        if args.agent == "plan":
+            agent.depth = args.depth
         print(f"Baseline agent: {args.agent}")
     res = evaluate_agent(agent, num_episodes=args.episodes, deterministic=args.deterministic, render=args.render,
                          seed=args.seed, max_moves=args.max_moves)

@@ -265,6 +265,20 @@ class DeviceEnvBatch:
                 "bb_greedy_actions", self.handle, self.lib)
         return out
 
+    def plan_actions(self, out: torch.Tensor, weights, depth: int = 3, value: Optional[torch.Tensor] = None,
+                     plan: Optional[torch.Tensor] = None, leaves: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """bb_plan_actions on the live state: out (int32 [N]) receives the first move of every env's best way
+        to play out its hand, searched exhaustively up to ``depth`` (1..3) moves in one fused launch; value
+        (int64 [N]), plan (int32 [N, 3], -1 for plies not played) and leaves (int32 [N], the number of maximal
+        sequences) are optional.  Reads the state and changes nothing, the piece stream included."""
+        from . import kernels as K
+
+        o = K._plan_out({"action": out, "value": value, "plan": plan, "leaves": leaves}, self.num_envs, self.device)
+        w = weights if isinstance(weights, L.GreedyWeights) else L.greedy_weights(weights)
+        L.check(self.lib.bb_plan_actions(self.handle, C.byref(w), int(depth), C.byref(o), _stream(self.device)),
+                "bb_plan_actions", self.handle, self.lib)
+        return out
+
     # ------------------------------------------------------------ host copies
     def state(self) -> dict:
         n = self.num_envs

@@ -222,6 +222,51 @@ def greedy_actions(board: torch.Tensor, hand: torch.Tensor, weights, combo: Opti
     return action, value
 
 
+PLAN_OUTPUTS = {"action": (torch.int32, 1), "value": (torch.int64, 1), "plan": (torch.int32, 3),
+                "leaves": (torch.int32, 1)}
+
+
+def _plan_out(tensors: dict, n: int, dev) -> L.PlanOut:
+    """bb_plan_out from {"action", "value", "plan", "leaves"} tensors (None = NULL; action is required)."""
+    o = L.PlanOut()
+    for k, (dt, width) in PLAN_OUTPUTS.items():
+        t = tensors.get(k)
+        if t is None:
+            if k == "action":
+                raise L.BBNativeError("plan_actions: the action output is required")
+            continue
+        if not (t.dtype == dt and t.device == dev and t.is_contiguous() and t.numel() == n * width):
+            raise L.BBNativeError(f"plan_actions: {k} must be a contiguous {dt} tensor of {n * width} elements on {dev}")
+        setattr(o, k, t.data_ptr())
+    return o
+
+
+def plan_actions(board: torch.Tensor, hand: torch.Tensor, weights, depth: int = 3,
+                 combo: Optional[torch.Tensor] = None, action: Optional[torch.Tensor] = None,
+                 value: Optional[torch.Tensor] = None, plan: Optional[torch.Tensor] = None,
+                 leaves: Optional[torch.Tensor] = None, want_value: bool = True, want_plan: bool = False,
+                 want_leaves: bool = False) -> dict:
+    """bb_plan_actions_pos: per position the best way to play out the hand's unused pieces, up to ``depth`` (1..3)
+    moves, by exhaustive search in one fused launch (bbvec.h "full-hand lookahead").  The value of a move sequence
+    is the greedy weights' move terms (lines, score) summed along it plus the state terms of its last afterstate;
+    ties go to the lexicographically lowest (a1, a2, a3).  Returns a dict: "action" int32 [n] (a1; 0 without a
+    legal action), and when asked for or passed in "value" int64 [n] (INT64_MIN without a legal action), "plan"
+    int32 [n, 3] (-1 for plies not played) and "leaves" int32 [n] (the number of maximal sequences)."""
+    pos, n, dev = _positions(board, hand, combo, None)
+    w = weights if isinstance(weights, L.GreedyWeights) else L.greedy_weights(weights)
+    res = {"action": torch.empty(n, dtype=torch.int32, device=dev) if action is None else action}
+    for k, given, want in (("value", value, want_value), ("plan", plan, want_plan), ("leaves", leaves, want_leaves)):
+        if given is not None:
+            res[k] = given
+        elif want:
+            res[k] = torch.empty((n, 3) if k == "plan" else n, dtype=PLAN_OUTPUTS[k][0], device=dev)
+    o = _plan_out(res, n, dev)
+    lib, stream = _look_lib(dev)
+    L.check(lib.bb_plan_actions_pos(C.byref(pos), n, C.byref(w), int(depth), C.byref(o), stream),
+            "bb_plan_actions_pos", lib=lib)
+    return res
+
+
 def unpack_aux(aux) -> dict:
     """The fields of the afterstate aux word (bbvec.h): works on a torch tensor or a numpy array."""
     a = aux.to(torch.int64) & 0xFFFFFFFF if isinstance(aux, torch.Tensor) else (aux.astype("int64") & 0xFFFFFFFF)

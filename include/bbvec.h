@@ -47,7 +47,8 @@ extern "C" {
                                  bb_bn_backward_part;
                                  (additive, still 8) bb_positions / bb_afterstate_out / bb_greedy_weights with
                                  bb_afterstates(_pos) and bb_greedy_actions(_pos): one-ply lookahead
-                                 (engine.py:326-346, 390-454; block_blast_env.py:148-193) */
+                                 (engine.py:326-346, 390-454; block_blast_env.py:148-193);
+                                 (additive, still 8) bb_plan_out with bb_plan_actions(_pos): full-hand lookahead */
 
 #define BB_OK 0
 #define BB_ERR_ARG (-1)
@@ -326,6 +327,47 @@ int bb_afterstates(bb_env* env, const bb_afterstate_out* out, void* stream);
 int bb_greedy_actions_pos(const bb_positions* pos, int32_t n, const bb_greedy_weights* w, int32_t* d_action,
                           int64_t* d_value, void* stream);
 int bb_greedy_actions(bb_env* env, const bb_greedy_weights* w, int32_t* d_action, int64_t* d_value, void* stream);
+
+/* ---- full-hand lookahead ----------------------------------------------------
+ * The exhaustive search over the deterministic part of a decision: the up to
+ * three pieces of the hand (engine.py:155-172 deals them together) may be
+ * played in any order and nothing random happens until the third one is placed
+ * (engine.py:432-437 draws the next hand only then), so the best way to play
+ * the hand out is a plain maximum over move sequences.  The reference has no
+ * such call.  Every move is the one-ply move above: legality (engine.py:
+ * 326-346), B', lines, combo', score_gained (engine.py:390-431), refill,
+ * mobility, dead (engine.py:348-362), holes', centre', filled'.
+ *
+ * search(P, d), d >= 1: for every legal action a of P with afterstate S, S is
+ * terminal if d == 1 or S.refill or S.dead and ends a maximal sequence;
+ * otherwise search((S.board, hand with slot p marked used, combo'), d - 1).
+ * dead means no unused slot fits anywhere, so a search never meets a position
+ * without a move below the root.  The value of a maximal sequence a_1..a_k
+ * (k <= depth) under bb_greedy_weights w is the int64 sum
+ *   w.lines * sum_j lines_j + w.score * sum_j score_gained_j (combo carried)
+ *   + w.holes*holes_k + w.filled*filled_k + w.centre*centre_k
+ *   + w.mobility*mobility_k + w.dead*dead_k + w.refill*refill_k
+ * with the state terms taken from the last afterstate: at depth 1 the greedy
+ * value, term for term.  Per position the maximal sequence with the largest
+ * value is returned, ties to the lexicographically lowest (a_1, a_2, a_3).
+ *   action [n]    a_1; 0 when the position has no legal action
+ *   value  [n]    the best value; INT64_MIN when there is no legal action
+ *   plan   [n][3] a_1, a_2, a_3, -1 for plies not played (all -1: no action)
+ *   leaves [n]    the number of maximal sequences (<= 192*128*64 = 1,572,864)
+ * action is required, the others may be NULL.  depth is 1..3.  The handle form
+ * reads the live columns and changes nothing, the RNG included, and refuses a
+ * handle in BB_ERR_DEVICE / BB_ERR_STATE.  Asynchronous on `stream`, no
+ * allocation, no sync (graph-capturable); indexing is 64-bit. */
+typedef struct bb_plan_out {
+  int32_t* action;  /* [n]    required */
+  int64_t* value;   /* [n]    NULL ok  */
+  int32_t* plan;    /* [n][3] NULL ok  */
+  int32_t* leaves;  /* [n]    NULL ok  */
+} bb_plan_out;      /* device pointers */
+
+int bb_plan_actions_pos(const bb_positions* pos, int32_t n, const bb_greedy_weights* w, int32_t depth,
+                        const bb_plan_out* out, void* stream);
+int bb_plan_actions(bb_env* env, const bb_greedy_weights* w, int32_t depth, const bb_plan_out* out, void* stream);
 
 /* Fused masked-categorical tail of BlockBlastNetwork.get_action_and_value
  * (network.py:173-180, 210-262; Categorical clamp semantics of torch 2.10):
