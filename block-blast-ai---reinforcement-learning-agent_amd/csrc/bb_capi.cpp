@@ -594,8 +594,7 @@ int bb_greedy_actions_pos(const bb_positions* pos, int32_t n, const bb_greedy_we
   if (!pos || !pos->board || !pos->hand || n <= 0 || !w || !d_action)
     return fail(nullptr, BB_ERR_ARG,
                 "bb_greedy_actions_pos: positions (board, hand), n > 0, weights and d_action are required");
-  hipError_t st = launch_greedy(pos->board, pos->hand, pos->combo, pos->prev, n, *w, d_action, d_value,
-                                (hipStream_t)stream);
+  hipError_t st = launch_greedy(pos->board, pos->hand, pos->combo, n, *w, d_action, d_value, (hipStream_t)stream);
   if (st != hipSuccess)
     return fail(nullptr, BB_ERR_HIP, std::string("bb_greedy_actions_pos: ") + hipGetErrorString(st));
   return BB_OK;
@@ -607,7 +606,7 @@ int bb_greedy_actions(bb_env* env, const bb_greedy_weights* w, int32_t* d_action
   if (status_fail(env, "bb_greedy_actions") != BB_OK) return BB_ERR_DEVICE;
   if (env->broken) return broken_fail(env, "bb_greedy_actions");
   DeviceGuard g(env->device);
-  hipError_t st = launch_greedy(env->d.board, env->d.hand, env->d.combo, env->d.prev, env->n, *w, d_action, d_value,
+  hipError_t st = launch_greedy(env->d.board, env->d.hand, env->d.combo, env->n, *w, d_action, d_value,
                                 (hipStream_t)stream);
   if (st != hipSuccess) return hip_fail(env, st, "bb_greedy_actions");
   return BB_OK;

@@ -7,17 +7,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bb_rules.h"  // board constants, hand word, count_holes, score and reward
+
 namespace bb {
 
-constexpr int kPieces = 37;
-constexpr int kHand = 3;
 constexpr int kMaxAttempts = 100;  // engine.py:161
-
-constexpr uint64_t kRow0 = 0x00000000000000FFull;
-constexpr uint64_t kRow7 = 0xFF00000000000000ull;
-constexpr uint64_t kCol0 = 0x0101010101010101ull;
-constexpr uint64_t kCol7 = 0x8080808080808080ull;
-constexpr uint64_t kCenter = 0x00003C3C3C3C0000ull;  // rows 2-5 x cols 2-5 (board.py:242)
 
 // One row of the piece table, staged into LDS by every kernel.
 //   shape   : cells of the piece anchored at (0,0)
@@ -76,16 +70,6 @@ __host__ __device__ inline uint64_t dilate(const PieceRow& p, uint64_t B) {
   return x;
 }
 
-// Packed hand word (also the host-visible layout, see bbvec.h bb_state_view).
-__host__ __device__ inline uint32_t hand_id(uint32_t h, int slot) { return (h >> (6 * slot)) & 63u; }
-__host__ __device__ inline uint32_t hand_used(uint32_t h) { return (h >> 18) & 7u; }
-__host__ __device__ inline bool hand_over(uint32_t h) { return (h >> 21) & 1u; }
-__host__ __device__ inline bool hand_has32(uint32_t h) { return (h >> 22) & 1u; }
-__host__ __device__ inline uint32_t hand_pack(uint32_t a, uint32_t b, uint32_t c, uint32_t used,
-                                              bool over, bool has32) {
-  return a | (b << 6) | (c << 12) | (used << 18) | ((uint32_t)over << 21) | ((uint32_t)has32 << 22);
-}
-
 // --------------------------------------------------------------------------
 // Bitboard rules
 // --------------------------------------------------------------------------
@@ -117,16 +101,6 @@ __device__ __forceinline__ uint64_t clear_full(uint64_t B, int& rows, int& cols)
 __device__ __forceinline__ uint64_t clear_full(uint64_t B) {
   int r, c;
   return clear_full(B, r, c);
-}
-
-// Board.count_holes (board.py:195-216): empty cells whose four neighbours are
-// all filled or off-board.
-__device__ __forceinline__ int count_holes(uint64_t B) {
-  uint64_t n = (B << 8) | kRow0;
-  uint64_t s = (B >> 8) | kRow7;
-  uint64_t w = ((B << 1) & ~kCol0) | kCol0;
-  uint64_t e = ((B >> 1) & ~kCol7) | kCol7;
-  return __popcll(~B & n & s & w & e);
 }
 
 // --------------------------------------------------------------------------

@@ -168,24 +168,18 @@ __device__ __forceinline__ bool apply_move(const Tables& t, StepCtx& s, int act)
   int rows, cols;
   s.B = clear_full(s.B | (pr.shape << cell), rows, cols);
   s.lines = rows + cols;
-  if (s.lines > 0) {
-    s.combo += 1;
-    s.max_combo = s.combo > s.max_combo ? s.combo : s.max_combo;
-    s.lines_tot += s.lines;
-    s.cm = s.lines < 4 ? s.lines : 4;
-    const int streak = s.combo + 1 < 8 ? s.combo + 1 : 8;  // post-increment combo (engine.py:261)
-    s.gained = s.nblk + (int64_t)(s.lines * 8 * 10) * s.cm * streak;  // blocks_in_lines = lines*8 (engine.py:427)
-  } else {
-    s.combo = 0;
-    s.gained = s.nblk;
-  }
+  s.cm = combo_multiplier(s.lines);
+  s.gained = score_gained(s.nblk, s.lines, combo_next(s.combo));
+  s.combo = combo_after(s.lines, s.combo);
+  if (s.lines > 0 && s.combo > s.max_combo) s.max_combo = s.combo;
+  s.lines_tot += s.lines;
   s.score += s.gained;
   if (used == 7u) {
     s.drew = true;
-    s.hand &= ~(7u << 18);
+    s.hand = hand_clear_used(s.hand);
     return true;
   }
-  s.hand = (s.hand & 0x3FFFFu) | (used << 18) | (s.hand & (1u << 22));
+  s.hand = hand_with_used(s.hand, used);
   return false;
 }
 
@@ -206,28 +200,24 @@ __device__ __forceinline__ bool apply_move_bf(const Tables& t, StepCtx& s, int a
   int rows, cols;
   const uint64_t B2 = clear_full(s.B | placed, rows, cols);
   const int lines = rows + cols;
-  const int combo1 = s.combo + 1;
-  const int cm = lines < 4 ? lines : 4;
-  const int streak = combo1 + 1 < 8 ? combo1 + 1 : 8;  // post-increment combo (engine.py:261)
-  const int64_t gained = lines > 0 ? nblk + (int64_t)(lines * 8 * 10) * cm * streak : (int64_t)nblk;
-  const bool clr = valid && lines > 0;
+  const int combo1 = combo_after(lines, s.combo);
+  const int64_t gained = score_gained(nblk, lines, combo_next(s.combo));
   s.valid = valid;
   s.nblk = valid ? nblk : 0;
   s.lines = valid ? lines : 0;
-  s.cm = clr ? cm : 1;
+  s.cm = valid ? combo_multiplier(lines) : 1;
   s.gained = valid ? gained : 0;
   s.B = valid ? B2 : s.B;
   s.moves += valid ? 1 : 0;
   s.blocks += valid ? nblk : 0;
-  s.max_combo = clr && combo1 > s.max_combo ? combo1 : s.max_combo;
-  s.combo = valid ? (lines > 0 ? combo1 : 0) : s.combo;
+  s.max_combo = valid && lines > 0 && combo1 > s.max_combo ? combo1 : s.max_combo;
+  s.combo = valid ? combo1 : s.combo;
   s.lines_tot += valid ? lines : 0;
   s.score += valid ? gained : 0;
   const uint32_t used = used0 | (1u << p);
   const bool drew = valid && used == 7u;
   s.drew = drew;
-  s.hand = !valid ? s.hand
-                  : (drew ? (s.hand & ~(7u << 18)) : ((s.hand & 0x3FFFFu) | (used << 18) | (s.hand & (1u << 22))));
+  s.hand = !valid ? s.hand : (drew ? hand_clear_used(s.hand) : hand_with_used(s.hand, used));
   return drew;
 }
 
@@ -272,27 +262,19 @@ __device__ __forceinline__ void store_reset(const EnvDev& e, int i, const Pcg& r
   e.mask[3 * i + 2] = m[2];
 }
 
-// _calculate_reward of a legal move (block_blast_env.py:158-193): fp64 in the
-// reference's exact operation order.  holes / center: the post-move values
-// that become _prev_holes / the filled-centre count.
+// _calculate_reward of a legal move (bb_rules.h move_reward).  holes / center:
+// the post-move values that become _prev_holes / the filled-centre count.
 __device__ __forceinline__ double move_reward(const StepCtx& s, const StepArgs& a, bool over, int& holes,
                                               int& center) {
-  double R = 0.0;
-  R = __dadd_rn(R, __dmul_rn((double)s.nblk, a.cfg.block_placed));
-  R = __dadd_rn(R, a.cfg.survival_bonus);
-  if (s.lines > 0) {
-    double lr = __dmul_rn((double)s.lines, a.cfg.line_clear_base);
-    lr = __dmul_rn(lr, (double)s.cm);
-    R = __dadd_rn(R, lr);
-    if (s.cm > 1) R = __dadd_rn(R, __dmul_rn((double)(s.cm - 1), a.cfg.combo_multiplier_bonus));
-  }
-  if (over) R = __dadd_rn(R, a.cfg.game_over_penalty);
   holes = count_holes(s.B);
-  const int dh = holes - (int)(s.prev & 0xFFu);
-  if (dh > 0) R = __dadd_rn(R, __dmul_rn((double)dh, a.cfg.hole_penalty));
   center = __popcll(s.B & kCenter);
-  if (center <= (int)(s.prev >> 8)) R = __dadd_rn(R, a.center_tenth);  // openness >= previous
-  return R;
+  return move_reward(a.cfg, a.center_tenth, s.nblk, s.lines, s.cm, over, holes, center, s.prev);
+}
+
+// the step's info record (block_blast_env.py:266-288): values after the move, before any auto-reset
+__device__ __forceinline__ bb_info step_info(const StepCtx& s, int holes, bool term) {
+  return make_info(s.score, s.gained, s.B, s.moves, s.lines_tot, s.max_combo, s.blocks, s.hand, holes, s.valid, term,
+                   s.nblk, s.lines, s.cm);
 }
 
 // ---------------------------------------------------------------------------
@@ -310,7 +292,7 @@ __device__ __forceinline__ void finalize(const Tables& t, const EnvDev& e, StepC
   int holes = 0, center = 0;
   if (s.valid) {
     const bool over = (m[0] | m[1] | m[2]) == 0ull;  // engine.py:440-441
-    if (over) s.hand |= 1u << 21;
+    if (over) s.hand = hand_set_over(s.hand);
     rew = move_reward(s, a, over, holes, center);
     term = over;
   } else if (a.info) {
@@ -319,23 +301,7 @@ __device__ __forceinline__ void finalize(const Tables& t, const EnvDev& e, StepC
 
   const uint64_t F2 = fprof ? __builtin_amdgcn_s_memtime() : 0;
   if (a.info) {
-    bb_info inf;
-    inf.score = s.score;
-    inf.score_gained = s.gained;
-    inf.term_board = s.B;
-    inf.moves = s.moves;
-    inf.lines = s.lines_tot;
-    inf.max_combo = s.max_combo;
-    inf.blocks = s.blocks;
-    inf.term_hand = s.hand;
-    inf.holes = (uint8_t)holes;
-    inf.filled = (uint8_t)__popcll(s.B);
-    inf.flags = (uint8_t)((s.valid ? 4u : 1u) | (term ? 2u : 0u));
-    inf.last_blocks = (uint8_t)s.nblk;
-    inf.last_lines = (uint8_t)s.lines;
-    inf.last_cm = (uint8_t)s.cm;
-    inf.pad[0] = inf.pad[1] = 0;
-    a.info[i] = inf;
+    a.info[i] = step_info(s, holes, term);
   }
   a.reward[i] = (float)rew;
   a.terminated[i] = term ? 1 : 0;
@@ -457,7 +423,7 @@ __global__ void __launch_bounds__(kStepBlock) step_kernel(EnvDev e, const PieceR
   uint64_t T3 = T2;
 
   if (valid) {
-    uint32_t ids = s.hand & 0x3FFFFu;
+    uint32_t ids = hand_ids(s.hand);
     if (prof) T3 = __builtin_amdgcn_s_memtime();
     if (draw) {
       // ---- all three used -> new hand (engine.py:432-437) ---------------
@@ -482,7 +448,7 @@ __global__ void __launch_bounds__(kStepBlock) step_kernel(EnvDev e, const PieceR
           a.dbg_out[4 * i + 3] = s.B;
         }
       }
-      s.hand = ids | ((uint32_t)s.rng.has << 22);
+      s.hand = hand_new(ids, s.rng.has);
       if (!done) {
         // park: post-move state + the unfinished attempt for escalate_kernel
         e.board[i] = s.B;
@@ -572,7 +538,7 @@ __global__ void __launch_bounds__(kEscBlock) escalate_kernel(EnvDev e, const Pie
     gen_hands_multi<kEscGroup, true>(parked, s.B, s.rng, my_ids, t.row, t.d, J, lane, a.pack_first, a.pack_next,
                                scratch + (threadIdx.x & ~63), nullptr, (int)(pr & 0xFFu));
     if (flagged) {
-      s.hand = my_ids | ((uint32_t)s.rng.has << 22);
+      s.hand = hand_new(my_ids, s.rng.has);
       finalize(t, e, s, a);
       e.pend[mine] = 0;
     }
@@ -611,7 +577,7 @@ __global__ void __launch_bounds__(kEscBlock) escalate_kernel(EnvDev e, const Pie
   }
   // finalise every parked env in parallel (its owner lane)
   if (flagged) {
-    s.hand = my_ids | ((uint32_t)s.rng.has << 22);
+    s.hand = hand_new(my_ids, s.rng.has);
     finalize(t, e, s, a);
     e.pend[mine] = 0;
   }
@@ -740,7 +706,7 @@ __global__ void __launch_bounds__(kStepRollBlock, 1) step_fused_kernel(EnvDev e,
     rng_moved = true;
     if (accepted) s.rng = after;
     park = !accepted;
-    s.hand = (s.hand & 0x3FFFFu) | ((uint32_t)s.rng.has << 22);
+    s.hand = hand_new(hand_ids(s.hand), s.rng.has);
   }
   // ---- hand searches the in-lane test left open (engine.py:155-172): the whole wave
   const uint64_t parked = __ballot(park) & kEnvMask;
@@ -751,7 +717,7 @@ __global__ void __launch_bounds__(kStepRollBlock, 1) step_fused_kernel(EnvDev e,
 #else
     gen_hands_multi<kE, true>(parked, s.B, s.rng, ids, t.row, t.d, jt, lane, a.pack_first, a.pack_next, lds);
 #endif
-    if ((parked >> (lane % kE)) & 1ull) s.hand = ids | ((uint32_t)s.rng.has << 22);
+    if ((parked >> (lane % kE)) & 1ull) s.hand = hand_new(ids, s.rng.has);
   }
   // ---- finalize (copy 0): game over, reward, outputs, auto-reset, mask, policy
   const uint32_t u_next = policy_uniform(a.policy_seed, a.env_offset + (uint64_t)i, r.policy_step0 + 1);
@@ -762,7 +728,7 @@ __global__ void __launch_bounds__(kStepRollBlock, 1) step_fused_kernel(EnvDev e,
     int holes = 0;
     if (s.valid) {
       const bool over = (m[0] | m[1] | m[2]) == 0ull;  // engine.py:440-441
-      if (over) s.hand |= 1u << 21;
+      if (over) s.hand = hand_set_over(s.hand);
       int center;
       rew = move_reward(s, a, over, holes, center);
       s.prev = (uint32_t)(holes | (center << 8));
@@ -776,23 +742,7 @@ __global__ void __launch_bounds__(kStepRollBlock, 1) step_fused_kernel(EnvDev e,
     if (r.actions) r.actions[i] = act;
     if (kStepOut && r.reward_f64) r.reward_f64[i] = rew;
     if (kStepOut && r.info) {  // block_blast_env.py:266-288, values after the move, before the auto-reset
-      bb_info inf;
-      inf.score = s.score;
-      inf.score_gained = s.gained;
-      inf.term_board = s.B;
-      inf.moves = s.moves;
-      inf.lines = s.lines_tot;
-      inf.max_combo = s.max_combo;
-      inf.blocks = s.blocks;
-      inf.term_hand = s.hand;
-      inf.holes = (uint8_t)holes;
-      inf.filled = (uint8_t)__popcll(s.B);
-      inf.flags = (uint8_t)((s.valid ? 4u : 1u) | (term ? 2u : 0u));
-      inf.last_blocks = (uint8_t)s.nblk;
-      inf.last_lines = (uint8_t)s.lines;
-      inf.last_cm = (uint8_t)s.cm;
-      inf.pad[0] = inf.pad[1] = 0;
-      r.info[i] = inf;
+      r.info[i] = step_info(s, holes, term);
     }
     if (term) {  // info['final_score'] / info['moves'] of the ending episode (wrappers.py:97-101)
       if (r.final_score) r.final_score[i] = s.score;
@@ -1199,7 +1149,7 @@ __global__ void __launch_bounds__(kABlock, 1) rollout_async_kernel(EnvDev e, con
         for (int k = 0; k < BB_ASYNC_SLOTS; ++k) ok = quick_slot_bf(s.B, q0, q1, q2, t.row, t.d, k) || ok;
 #endif
         if (ok) s.rng = after;
-        s.hand = (s.hand & 0x3FFFFu) | ((uint32_t)s.rng.has << 22);
+        s.hand = hand_new(hand_ids(s.hand), s.rng.has);
         if (ok) {
           ph = 2;
         } else {  // post the env: post-move board, stream rolled back to attempt 1
@@ -1224,7 +1174,7 @@ __global__ void __launch_bounds__(kABlock, 1) rollout_async_kernel(EnvDev e, con
       s.rng.buf = arec.buf[rid];
       const uint32_t hi = arec.has_ids[rid];
       s.rng.has = hi & 1u;
-      s.hand = (hi >> 1) | ((hi & 1u) << 22);
+      s.hand = hand_new(hi >> 1, hi & 1u);
       __hip_atomic_store(&astat[rid], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       ph = 2;
     }
@@ -1243,7 +1193,7 @@ __global__ void __launch_bounds__(kABlock, 1) rollout_async_kernel(EnvDev e, con
       int holes = 0;
       if (s.valid) {
         const bool over = (m[0] | m[1] | m[2]) == 0ull;  // engine.py:440-441
-        if (over) s.hand |= 1u << 21;
+        if (over) s.hand = hand_set_over(s.hand);
         int center;
         rew = move_reward(s, a, over, holes, center);
         s.prev = (uint32_t)(holes | (center << 8));

@@ -98,8 +98,8 @@ hipError_t launch_random_actions(const uint64_t* mbits, int n, uint64_t seed, ui
 // one-ply lookahead (bb_lookahead.hip): position columns [n] (combo / prev may be NULL = 0), outputs [n][192]
 hipError_t launch_afterstates(const uint64_t* board, const uint32_t* hand, const int32_t* combo, const uint16_t* prev,
                               int n, const bb_reward_cfg& cfg, const bb_afterstate_out& out, hipStream_t s);
-hipError_t launch_greedy(const uint64_t* board, const uint32_t* hand, const int32_t* combo, const uint16_t* prev,
-                         int n, const bb_greedy_weights& w, int32_t* action, int64_t* value, hipStream_t s);
+hipError_t launch_greedy(const uint64_t* board, const uint32_t* hand, const int32_t* combo, int n,
+                         const bb_greedy_weights& w, int32_t* action, int64_t* value, hipStream_t s);
 // full-hand lookahead (bb_lookahead.hip): depth 1..3, out.action required
 hipError_t launch_plan(const uint64_t* board, const uint32_t* hand, const int32_t* combo, int n,
                        const bb_greedy_weights& w, int depth, const bb_plan_out& out, hipStream_t s);

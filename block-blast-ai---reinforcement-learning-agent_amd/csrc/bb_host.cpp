@@ -14,6 +14,11 @@
 // env per thread (OpenMP over envs).  Parity: tests/test_host_backend.py runs it
 // against the C oracle (oracle/bb_oracle.c) step for step.
 //
+// The hand word, the score of a move, the reward, the lookahead's value terms
+// and the info record are the kernels' own definitions (bb_rules.h).  clear_full,
+// anchors_of and the piece table are this file's plain loops on purpose: they
+// are the independent check of the kernels' tuned versions.
+//
 // Reference: src/environment/wrappers.py:75-116 (vec step, auto-reset) ->
 // block_blast_env.py:224-264 (step, reward 148-193) -> engine.py:390-454.
 #include <stdint.h>
@@ -24,15 +29,19 @@
 #include <vector>
 
 #include "../../include/bbvec.h"
+#include "bb_rules.h"
 #include "bb_seed.h"
 
 namespace {
 
+// the rules shared with the kernels (bb_rules.h), by name: nothing else of the header can meet this file's own
+// clear_full, anchors_of, Pcg or Piece
+using bb::kPieces, bb::kCol0, bb::kCenter;
+using bb::hand_id, bb::hand_used, bb::hand_over, bb::hand_has32, bb::hand_pack, bb::hand_use, bb::hand_with_used,
+    bb::hand_set_over;
+using bb::count_holes, bb::combo_multiplier, bb::combo_next, bb::combo_after, bb::score_gained, bb::move_reward;
+using bb::After, bb::after_reward, bb::pack_aux, bb::move_terms, bb::state_terms, bb::make_info;
 using bb::seed::u128;
-constexpr int kPieces = 37;
-constexpr uint64_t kRow0 = 0xFFull, kRow7 = 0xFF00000000000000ull;
-constexpr uint64_t kCol0 = 0x0101010101010101ull, kCol7 = 0x8080808080808080ull;
-constexpr uint64_t kCenter = 0x00003C3C3C3C0000ull;  // rows 2-5 x cols 2-5 (board.py:242)
 
 struct Piece {
   uint64_t shape, anchors;
@@ -86,13 +95,6 @@ inline uint64_t clear_full(uint64_t B, int& rows, int& cols) {
 inline uint64_t clear_full(uint64_t B) {
   int r, c;
   return clear_full(B, r, c);
-}
-
-// board.py:195-216: empty cells whose four neighbours are filled or off-board
-inline int count_holes(uint64_t B) {
-  const uint64_t n = (B << 8) | kRow0, s = (B >> 8) | kRow7;
-  const uint64_t w = ((B << 1) & ~kCol0) | kCol0, e = ((B >> 1) & ~kCol7) | kCol7;
-  return __builtin_popcountll(~B & n & s & w & e);
 }
 
 // numpy PCG64 (XSL-RR) + Generator.integers(0, 37) buffered Lemire draw
@@ -192,7 +194,7 @@ struct bb_env {
   int autoreset = 1;
   bb_reward_cfg cfg{};
   std::vector<uint64_t> board, mask, seed_hi, seed_lo;
-  std::vector<uint32_t> hand;  // 3 x 6-bit ids | used << 18 | over << 21 | has_uint32 << 22
+  std::vector<uint32_t> hand;  // packed hand word (bb_rules.h)
   std::vector<int64_t> score;
   std::vector<int32_t> combo, max_combo, moves, lines, blocks;
   std::vector<uint16_t> prev;  // _prev_holes | filled centre cells << 8
@@ -211,10 +213,8 @@ int fail(bb_env* e, int code, const std::string& msg) {
   return code;
 }
 
-inline uint32_t hand_id(uint32_t h, int s) { return (h >> (6 * s)) & 63u; }
-
 void masks_of(uint64_t B, uint32_t hand, uint64_t m[3]) {  // engine.py:364-380 (status not consulted)
-  for (int s = 0; s < 3; ++s) m[s] = ((hand >> (18 + s)) & 1u) ? 0ull : anchors_of(hand_id(hand, s), B);
+  for (int s = 0; s < 3; ++s) m[s] = ((hand_used(hand) >> s) & 1u) ? 0ull : anchors_of(hand_id(hand, s), B);
 }
 
 // block_blast_env.py:195-222 -> engine.py:127-153: re-seed with seed_value when
@@ -228,7 +228,7 @@ void reset_env(bb_env* e, int i) {
   }
   const uint32_t a = draw_piece(g), b = draw_piece(g), c = draw_piece(g);
   e->board[i] = 0;
-  e->hand[i] = a | (b << 6) | (c << 12) | ((uint32_t)g.has << 22);
+  e->hand[i] = hand_pack(a, b, c, 0u, false, g.has);
   e->score[i] = 0;
   e->combo[i] = e->max_combo[i] = e->moves[i] = e->lines[i] = e->blocks[i] = 0;
   e->prev[i] = 0;  // _prev_holes = 0, _prev_center_openness = 1.0
@@ -248,8 +248,8 @@ Out step_env(bb_env* e, int i, int act, bb_info* info, int64_t* final_score, int
   uint64_t B = e->board[i];
   uint32_t hand = e->hand[i];
   const int p = act >> 6, cell = act & 63;
-  const uint32_t used = (hand >> 18) & 7u;
-  bool valid = act >= 0 && act < 192 && !((hand >> 21) & 1u) && !((used >> p) & 1u);
+  const uint32_t used = hand_used(hand);
+  bool valid = act >= 0 && act < 192 && !hand_over(hand) && !((used >> p) & 1u);
   const Piece* pc = nullptr;
   if (valid) {
     pc = &T().p[hand_id(hand, p)];
@@ -264,17 +264,11 @@ Out step_env(bb_env* e, int i, int act, bb_info* info, int64_t* final_score, int
     int rows, cols;
     B = clear_full(B | (pc->shape << cell), rows, cols);
     lines = rows + cols;
-    if (lines > 0) {
-      e->combo[i] += 1;
-      if (e->combo[i] > e->max_combo[i]) e->max_combo[i] = e->combo[i];
-      e->lines[i] += lines;
-      cm = lines < 4 ? lines : 4;
-      const int streak = e->combo[i] + 1 < 8 ? e->combo[i] + 1 : 8;  // post-increment combo (engine.py:261)
-      gained = nblk + (int64_t)(lines * 8 * 10) * cm * streak;         // blocks_in_lines = lines*8 (engine.py:427)
-    } else {
-      e->combo[i] = 0;
-      gained = nblk;
-    }
+    cm = combo_multiplier(lines);
+    gained = score_gained(nblk, lines, combo_next(e->combo[i]));
+    e->combo[i] = combo_after(lines, e->combo[i]);
+    if (lines > 0 && e->combo[i] > e->max_combo[i]) e->max_combo[i] = e->combo[i];
+    e->lines[i] += lines;
     e->score[i] += gained;
     const uint32_t nu = used | (1u << p);
     if (nu == 7u) {  // engine.py:432-437 -> _generate_new_pieces (155-172)
@@ -286,31 +280,17 @@ Out step_env(bb_env* e, int i, int act, bb_info* info, int64_t* final_score, int
         id[2] = draw_piece(g);
         if (solvable(B, id)) break;  // after 100 failures the last draw stays (engine.py:171-172)
       }
-      hand = id[0] | (id[1] << 6) | (id[2] << 12) | ((uint32_t)g.has << 22);
+      hand = hand_pack(id[0], id[1], id[2], 0u, false, g.has);
     } else {
-      hand = (hand & 0x3FFFFu) | (nu << 18) | (hand & (1u << 22));
+      hand = hand_with_used(hand, nu);
     }
     uint64_t m[3];
     masks_of(B, hand, m);
     const bool over = (m[0] | m[1] | m[2]) == 0ull;  // engine.py:440-441
-    if (over) hand |= 1u << 21;
-    // _calculate_reward (block_blast_env.py:158-193), fp64 in the reference's order
-    const bb_reward_cfg& c = e->cfg;
-    double R = 0.0;
-    R += (double)nblk * c.block_placed;
-    R += c.survival_bonus;
-    if (lines > 0) {
-      double lr = (double)lines * c.line_clear_base;
-      lr *= (double)cm;
-      R += lr;
-      if (cm > 1) R += (double)(cm - 1) * c.combo_multiplier_bonus;
-    }
-    if (over) R += c.game_over_penalty;
+    if (over) hand = hand_set_over(hand);
     holes = count_holes(B);
-    const int dh = holes - (int)(e->prev[i] & 0xFFu);
-    if (dh > 0) R += (double)dh * c.hole_penalty;
     const int center = __builtin_popcountll(B & kCenter);
-    if (center <= (int)(e->prev[i] >> 8)) R += c.center_bonus * 0.1;  // openness >= previous
+    const double R = move_reward(e->cfg, e->cfg.center_bonus * 0.1, nblk, lines, cm, over, holes, center, e->prev[i]);
     e->prev[i] = (uint16_t)(holes | (center << 8));
     e->board[i] = B;
     e->hand[i] = hand;
@@ -319,24 +299,9 @@ Out step_env(bb_env* e, int i, int act, bb_info* info, int64_t* final_score, int
   } else if (info) {
     holes = count_holes(B);
   }
-  if (info) {  // block_blast_env.py:266-288: after the move, before any auto-reset
-    bb_info& f = info[i];
-    f.score = e->score[i];
-    f.score_gained = gained;
-    f.term_board = e->board[i];
-    f.moves = e->moves[i];
-    f.lines = e->lines[i];
-    f.max_combo = e->max_combo[i];
-    f.blocks = e->blocks[i];
-    f.term_hand = e->hand[i];
-    f.holes = (uint8_t)holes;
-    f.filled = (uint8_t)__builtin_popcountll(e->board[i]);
-    f.flags = (uint8_t)((valid ? 4u : 1u) | (o.term ? 2u : 0u));
-    f.last_blocks = (uint8_t)nblk;
-    f.last_lines = (uint8_t)lines;
-    f.last_cm = (uint8_t)cm;
-    f.pad[0] = f.pad[1] = 0;
-  }
+  if (info)  // block_blast_env.py:266-288: after the move, before any auto-reset
+    info[i] = make_info(e->score[i], gained, e->board[i], e->moves[i], e->lines[i], e->max_combo[i], e->blocks[i],
+                        e->hand[i], holes, valid, o.term, nblk, lines, cm);
   if (o.term) {
     if (final_score) final_score[i] = e->score[i];
     if (final_moves) final_moves[i] = e->moves[i];
@@ -348,20 +313,13 @@ Out step_env(bb_env* e, int i, int act, bb_info* info, int64_t* final_score, int
 // ---------------------------------------------------------------------------
 // one-ply lookahead (bbvec.h bb_afterstates / bb_greedy_actions): the host twin of csrc/bb_lookahead.hip
 // ---------------------------------------------------------------------------
-struct After {
-  bool legal, dead, refill;
-  uint64_t board;
-  int ncells, lines, holes, centre, filled, mobility;
-  int64_t gained;
-};
-
 // engine.py:326-346 (legal), 390-431 (place, clear, combo, score) and the mobility of the slots that stay
 // unused on the new board (engine.py:348-362)
 After eval_action(uint64_t B, uint32_t hand, int combo, int act) {
   After a{};
   const int p = act >> 6, cell = act & 63;
-  const uint32_t used0 = (hand >> 18) & 7u, id = hand_id(hand, p);
-  if (id >= (uint32_t)kPieces || ((hand >> 21) & 1u) || ((used0 >> p) & 1u)) return a;
+  const uint32_t used0 = hand_used(hand), id = hand_id(hand, p);
+  if (id >= (uint32_t)kPieces || hand_over(hand) || ((used0 >> p) & 1u)) return a;
   const Piece& pc = T().p[id];
   if (!((pc.anchors >> cell) & 1ull) || ((pc.shape << cell) & B)) return a;
   a.legal = true;
@@ -369,10 +327,8 @@ After eval_action(uint64_t B, uint32_t hand, int combo, int act) {
   int rows, cols;
   a.board = clear_full(B | (pc.shape << cell), rows, cols);
   a.lines = rows + cols;
-  const int combo1 = a.lines > 0 ? combo + 1 : 0;
-  const int cm = a.lines < 4 ? a.lines : 4;
-  const int streak = combo1 + 1 < 8 ? combo1 + 1 : 8;
-  a.gained = a.lines > 0 ? a.ncells + (int64_t)(a.lines * 8 * 10) * cm * streak : (int64_t)a.ncells;
+  a.combo1 = combo_after(a.lines, combo);
+  a.gained = score_gained(a.ncells, a.lines, a.combo1);
   const uint32_t used = used0 | (1u << p);
   a.refill = used == 7u;
   for (int q = 0; q < 3; ++q)
@@ -385,41 +341,19 @@ After eval_action(uint64_t B, uint32_t hand, int combo, int act) {
   return a;
 }
 
-// _calculate_reward (block_blast_env.py:158-193) with game_over = dead, fp64 in the reference's order (the
-// library is built with -ffp-contract=off), as step_env above
-double after_reward(const After& a, const bb_reward_cfg& c, uint32_t prev) {
-  const int cm = a.lines > 0 ? (a.lines < 4 ? a.lines : 4) : 1;
-  double R = 0.0;
-  R += (double)a.ncells * c.block_placed;
-  R += c.survival_bonus;
-  if (a.lines > 0) {
-    double lr = (double)a.lines * c.line_clear_base;
-    lr *= (double)cm;
-    R += lr;
-    if (cm > 1) R += (double)(cm - 1) * c.combo_multiplier_bonus;
-  }
-  if (a.dead) R += c.game_over_penalty;
-  const int dh = a.holes - (int)(prev & 0xFFu);
-  if (dh > 0) R += (double)dh * c.hole_penalty;
-  if (a.centre <= (int)(prev >> 8)) R += c.center_bonus * 0.1;
-  return R;
-}
-
 void afterstates_host(const uint64_t* board, const uint32_t* hand, const int32_t* combo, const uint16_t* prev,
                       int32_t n, const bb_reward_cfg& cfg, const bb_afterstate_out& out) {
 #pragma omp parallel for schedule(static)
   for (int32_t i = 0; i < n; ++i) {
+    const double center_tenth = cfg.center_bonus * 0.1;
+    const uint32_t pv = prev ? prev[i] : 0u;
     for (int act = 0; act < 192; ++act) {
       const After a = eval_action(board[i], hand[i], combo ? combo[i] : 0, act);
       const size_t o = (size_t)i * 192 + (size_t)act;
       if (out.board) out.board[o] = a.legal ? a.board : board[i];
-      if (out.reward_f64) out.reward_f64[o] = a.legal ? after_reward(a, cfg, prev ? prev[i] : 0u) : -10.0;
+      if (out.reward_f64) out.reward_f64[o] = a.legal ? after_reward(a, cfg, center_tenth, pv) : -10.0;
       if (out.score_gained) out.score_gained[o] = a.legal ? (int32_t)a.gained : 0;
-      if (out.aux)
-        out.aux[o] = a.legal ? 1u | ((uint32_t)a.dead << 1) | ((uint32_t)a.refill << 2) | ((uint32_t)a.lines << 8) |
-                                   ((uint32_t)a.holes << 12) | ((uint32_t)a.centre << 19) |
-                                   ((uint32_t)a.mobility << 24)
-                             : 0u;
+      if (out.aux) out.aux[o] = a.legal ? pack_aux(a) : 0u;
     }
   }
 }
@@ -433,10 +367,7 @@ void greedy_host(const uint64_t* board, const uint32_t* hand, const int32_t* com
     for (int act = 0; act < 192; ++act) {  // ascending: a later action must be strictly better
       const After a = eval_action(board[i], hand[i], combo ? combo[i] : 0, act);
       if (!a.legal) continue;
-      const int64_t v = (int64_t)w.lines * a.lines + (int64_t)w.score * a.gained + (int64_t)w.holes * a.holes +
-                        (int64_t)w.filled * a.filled + (int64_t)w.centre * a.centre +
-                        (int64_t)w.mobility * a.mobility + (int64_t)w.dead * (int)a.dead +
-                        (int64_t)w.refill * (int)a.refill;
+      const int64_t v = move_terms(w, a) + state_terms(w, a);
       if (v > best) best = v, best_a = act;
     }
     action[i] = best_a;
@@ -457,25 +388,23 @@ struct PlanBest {
 
 void plan_dfs(uint64_t B, uint32_t hand, int combo, int depth, int ply, int64_t sum, int32_t* seq,
               const bb_greedy_weights& w, PlanBest& best) {
-  if ((hand >> 21) & 1u) return;  // game over: nothing is legal
+  if (hand_over(hand)) return;  // game over: nothing is legal
   for (int p = 0; p < 3; ++p) {
     const uint32_t id = hand_id(hand, p);
-    if (((hand >> (18 + p)) & 1u) || id >= (uint32_t)kPieces) continue;
+    if (((hand_used(hand) >> p) & 1u) || id >= (uint32_t)kPieces) continue;
     for (uint64_t m = anchors_of((int)id, B); m; m &= m - 1) {
       const int act = p * 64 + __builtin_ctzll(m);
       const After a = eval_action(B, hand, combo, act);
-      const int64_t s = sum + (int64_t)w.lines * a.lines + (int64_t)w.score * a.gained;
+      const int64_t s = sum + move_terms(w, a);
       seq[ply] = act;
       if (depth == 1 || a.refill || a.dead) {
-        const int64_t v = s + (int64_t)w.holes * a.holes + (int64_t)w.filled * a.filled +
-                          (int64_t)w.centre * a.centre + (int64_t)w.mobility * a.mobility +
-                          (int64_t)w.dead * (int)a.dead + (int64_t)w.refill * (int)a.refill;
+        const int64_t v = s + state_terms(w, a);
         if (best.leaves++ == 0 || v > best.value) {
           best.value = v;
           for (int k = 0; k < 3; ++k) best.plan[k] = k <= ply ? seq[k] : -1;
         }
       } else {
-        plan_dfs(a.board, hand | (1u << (18 + p)), a.lines > 0 ? combo + 1 : 0, depth - 1, ply + 1, s, seq, w, best);
+        plan_dfs(a.board, hand_use(hand, p), a.combo1, depth - 1, ply + 1, s, seq, w, best);
       }
     }
   }
@@ -578,7 +507,7 @@ int bb_reset(bb_env* env, const uint8_t* d_env_mask, void* stream) {
 #pragma omp parallel for schedule(static)
   for (int i = 0; i < env->n; ++i) {
     if (d_env_mask && !d_env_mask[i]) continue;
-    env->rng[i].has = (env->hand[i] >> 22) & 1u;
+    env->rng[i].has = hand_has32(env->hand[i]);
     reset_env(env, i);
   }
   return BB_OK;
@@ -650,7 +579,7 @@ int bb_obs(bb_env* env, float* d_x, int8_t* d_mask_i8, float* d_mask_f32, uint64
       const uint32_t h = env->hand[i];
       for (int pl = 0; pl < 4; ++pl) {
         const uint64_t v = pl == 0 ? env->board[i]
-                                   : (((h >> (17 + pl)) & 1u) ? 0ull : T().p[hand_id(h, pl - 1)].shape);
+                                   : (((hand_used(h) >> (pl - 1)) & 1u) ? 0ull : T().p[hand_id(h, pl - 1)].shape);
         for (int b = 0; b < 64; ++b) x[64 * pl + b] = (float)((v >> b) & 1ull);
       }
     }
@@ -724,7 +653,7 @@ int bb_set_state(bb_env* env, const bb_state_view* v) {
       env->rng[i].state = ((u128)v->rng[3 * i] << 64) | v->rng[3 * i + 1];
       env->rng[i].buf = (uint32_t)v->rng[3 * i + 2];
     }
-    env->rng[i].has = (env->hand[i] >> 22) & 1u;
+    env->rng[i].has = hand_has32(env->hand[i]);
     masks_of(env->board[i], env->hand[i], &env->mask[3 * i]);  // derived state
   }
   return BB_OK;

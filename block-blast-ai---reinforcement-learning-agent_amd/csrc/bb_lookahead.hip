@@ -28,16 +28,9 @@ struct LookTable {
   PieceRow row[kPieces];
 };
 
-// What one legal placement leads to (illegal: legal == false and the rest unspecified).
-struct After {
-  bool legal, dead, refill;
-  uint64_t board;  // B' (after the clears)
-  int ncells, lines, combo1, holes, centre, filled, mobility;
-  int64_t gained;
-};
-
 // Lane `cell` of slot p: engine.py:326-346 (legal), 390-431 (place, clear, combo, score), then the
-// mobility of the slots that stay unused (engine.py:348-362 valid_moves on the new board).
+// mobility of the slots that stay unused (engine.py:348-362 valid_moves on the new board).  After, its
+// reward, aux word and value terms are the shared ones of bb_rules.h.
 __device__ __forceinline__ After eval_action(const LookTable& t, uint64_t B, uint32_t hand, int combo, int p,
                                              int cell) {
   After a;
@@ -50,10 +43,8 @@ __device__ __forceinline__ After eval_action(const LookTable& t, uint64_t B, uin
   int rows, cols;
   a.board = clear_full(B | (pr.shape << cell), rows, cols);
   a.lines = rows + cols;
-  a.combo1 = a.lines > 0 ? combo + 1 : 0;
-  const int cm = a.lines < 4 ? a.lines : 4;
-  const int streak = a.combo1 + 1 < 8 ? a.combo1 + 1 : 8;  // post-increment combo (engine.py:261)
-  a.gained = a.lines > 0 ? a.ncells + (int64_t)(a.lines * 8 * 10) * cm * streak : (int64_t)a.ncells;
+  a.combo1 = combo_after(a.lines, combo);
+  a.gained = score_gained(a.ncells, a.lines, a.combo1);
   const uint32_t used = used0 | (1u << p);
   a.refill = used == 7u;
   int mob = 0;
@@ -68,32 +59,6 @@ __device__ __forceinline__ After eval_action(const LookTable& t, uint64_t B, uin
   a.centre = __popcll(a.board & kCenter);
   a.filled = __popcll(a.board);
   return a;
-}
-
-// _calculate_reward of a legal move (block_blast_env.py:158-193) with game_over = dead: the same fp64
-// operations in the same order as move_reward in bb_env.hip (restated here so that file stays untouched).
-__device__ __forceinline__ double after_reward(const After& a, const bb_reward_cfg& cfg, double center_tenth,
-                                               uint32_t prev) {
-  const int cm = a.lines > 0 ? (a.lines < 4 ? a.lines : 4) : 1;
-  double R = 0.0;
-  R = __dadd_rn(R, __dmul_rn((double)a.ncells, cfg.block_placed));
-  R = __dadd_rn(R, cfg.survival_bonus);
-  if (a.lines > 0) {
-    double lr = __dmul_rn((double)a.lines, cfg.line_clear_base);
-    lr = __dmul_rn(lr, (double)cm);
-    R = __dadd_rn(R, lr);
-    if (cm > 1) R = __dadd_rn(R, __dmul_rn((double)(cm - 1), cfg.combo_multiplier_bonus));
-  }
-  if (a.dead) R = __dadd_rn(R, cfg.game_over_penalty);
-  const int dh = a.holes - (int)(prev & 0xFFu);
-  if (dh > 0) R = __dadd_rn(R, __dmul_rn((double)dh, cfg.hole_penalty));
-  if (a.centre <= (int)(prev >> 8)) R = __dadd_rn(R, center_tenth);  // openness >= previous
-  return R;
-}
-
-__device__ __forceinline__ uint32_t pack_aux(const After& a) {
-  return 1u | ((uint32_t)a.dead << 1) | ((uint32_t)a.refill << 2) | ((uint32_t)a.lines << 8) |
-         ((uint32_t)a.holes << 12) | ((uint32_t)a.centre << 19) | ((uint32_t)a.mobility << 24);
 }
 
 // The position columns are read at a wave-uniform index; readfirstlane tells the compiler so, which keeps the
@@ -147,10 +112,7 @@ greedy_kernel(LookTable t, LookPos pos, int n, bb_greedy_weights w, int32_t* __r
                                 (int)uniform32(pos.combo ? (uint32_t)pos.combo[i] : 0u), p, cell);
     // an illegal lane carries (INT64_MIN, 0): every legal value is above INT64_MIN (|weight| < 2^31, every
     // feature < 2^15), so it never wins over a legal lane, and with no legal lane the result is action 0
-    int64_t v = (int64_t)w.lines * a.lines + (int64_t)w.score * a.gained + (int64_t)w.holes * a.holes +
-                (int64_t)w.filled * a.filled + (int64_t)w.centre * a.centre + (int64_t)w.mobility * a.mobility +
-                (int64_t)w.dead * (int)a.dead + (int64_t)w.refill * (int)a.refill;
-    v = a.legal ? v : INT64_MIN;
+    int64_t v = a.legal ? move_terms(w, a) + state_terms(w, a) : INT64_MIN;
     int act = a.legal ? p * 64 + cell : 0;
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) {
@@ -206,15 +168,6 @@ struct PlanRecord {
   int32_t combo;   // combo'
   int32_t action;  // a1
 };
-
-__device__ __forceinline__ int64_t move_terms(const bb_greedy_weights& w, const After& a) {
-  return (int64_t)w.lines * a.lines + (int64_t)w.score * a.gained;
-}
-
-__device__ __forceinline__ int64_t state_terms(const bb_greedy_weights& w, const After& a) {
-  return (int64_t)w.holes * a.holes + (int64_t)w.filled * a.filled + (int64_t)w.centre * a.centre +
-         (int64_t)w.mobility * a.mobility + (int64_t)w.dead * (int)a.dead + (int64_t)w.refill * (int)a.refill;
-}
 
 // (value, key) order of the plan choice: the larger value, then the lower key
 __device__ __forceinline__ void take_plan(int64_t& v, uint32_t& key, int64_t v2, uint32_t key2) {
@@ -272,7 +225,7 @@ plan_kernel(LookTable t, LookPos pos, int n, bb_greedy_weights w, int depth, bb_
       const int64_t sum1 = (int64_t)uniform64((uint64_t)s_rec[r].sum);
       const int combo1 = (int)uniform32((uint32_t)s_rec[r].combo);
       const int act1 = (int)uniform32((uint32_t)s_rec[r].action);
-      const uint32_t hand1 = hand | (1u << (18 + (act1 >> 6)));
+      const uint32_t hand1 = hand_use(hand, act1 >> 6);
 #pragma unroll 1
       for (int q = 0; q < kHand; ++q) {
         if ((hand_used(hand1) >> q) & 1u) continue;  // wave-uniform
@@ -288,7 +241,7 @@ plan_kernel(LookTable t, LookPos pos, int n, bb_greedy_weights w, int depth, bb_
         // somewhere and placing it ends the sequence (refill).  Each such lane walks the set bits of its own
         // ply-3 anchor mask; the lanes' trip counts differ, the bound is the 64 bits.
         if (a2.legal && !end2) {
-          const uint32_t hand2 = hand1 | (1u << (18 + q));
+          const uint32_t hand2 = hand_use(hand1, q);
           const int q3 = __ffs((int)(~hand_used(hand2) & 7u)) - 1;  // wave-uniform; >= 0 here
           const uint32_t id3 = hand_id(hand2, q3);
           uint64_t m3 = anchors_of(t.row[id3 < (uint32_t)kPieces ? id3 : 0u], a2.board);  // != 0: not dead
@@ -361,9 +314,9 @@ hipError_t launch_afterstates(const uint64_t* board, const uint32_t* hand, const
   return hipGetLastError();
 }
 
-hipError_t launch_greedy(const uint64_t* board, const uint32_t* hand, const int32_t* combo, const uint16_t* prev,
-                         int n, const bb_greedy_weights& w, int32_t* action, int64_t* value, hipStream_t s) {
-  const LookPos pos{board, hand, combo, prev};
+hipError_t launch_greedy(const uint64_t* board, const uint32_t* hand, const int32_t* combo, int n,
+                         const bb_greedy_weights& w, int32_t* action, int64_t* value, hipStream_t s) {
+  const LookPos pos{board, hand, combo, nullptr};
   hipLaunchKernelGGL(greedy_kernel, look_grid(n), dim3(kLookBlock), 0, s, look_table(), pos, n, w, action, value);
   return hipGetLastError();
 }

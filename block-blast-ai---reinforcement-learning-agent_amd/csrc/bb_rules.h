@@ -1,0 +1,170 @@
+// bb_rules.h -- the rules of a Block Blast move that the HIP kernels and the host backend share.
+//
+// One definition each of: the board constants, the packed hand word, count_holes, the score of a move, the
+// fp64 shaped reward, what a placement leads to (After) with its greedy value terms and aux word, and the
+// bb_info record.  Plain C++ with no HIP include: g++ compiles it for libbbvec_host.so, hipcc for host and
+// device of libbbvec.so.  Every function names the reference code whose semantics it reproduces.
+//
+// Deliberately not here: clear_full, anchors_of / dilate and the piece tables.  The device versions are tuned
+// (byte-permute, Minkowski program) and the host's plain loops are their independent check in the
+// cross-backend tests; likewise the PCG64 / Philox streams, the hand solver and the search structure.
+#pragma once
+#include <stdint.h>
+
+#include "../../include/bbvec.h"
+
+#if defined(__HIPCC__)
+#define BB_RULE __host__ __device__ inline
+#else
+#define BB_RULE inline
+#endif
+
+namespace bb {
+
+constexpr int kPieces = 37;
+constexpr int kHand = 3;
+
+constexpr uint64_t kRow0 = 0x00000000000000FFull;
+constexpr uint64_t kRow7 = 0xFF00000000000000ull;
+constexpr uint64_t kCol0 = 0x0101010101010101ull;
+constexpr uint64_t kCol7 = 0x8080808080808080ull;
+constexpr uint64_t kCenter = 0x00003C3C3C3C0000ull;  // rows 2-5 x cols 2-5 (board.py:242)
+
+// --------------------------------------------------------------------------
+// Packed hand word (also the host-visible layout, see bbvec.h bb_state_view):
+// 3 x 6-bit piece ids | used << 18 | over << 21 | has_uint32 << 22.
+// --------------------------------------------------------------------------
+constexpr uint32_t kHandIds = 0x3FFFFu;
+constexpr int kHandUsedShift = 18, kHandOverShift = 21, kHandHas32Shift = 22;
+
+BB_RULE uint32_t hand_id(uint32_t h, int slot) { return (h >> (6 * slot)) & 63u; }
+BB_RULE uint32_t hand_ids(uint32_t h) { return h & kHandIds; }
+BB_RULE uint32_t hand_used(uint32_t h) { return (h >> kHandUsedShift) & 7u; }
+BB_RULE bool hand_over(uint32_t h) { return (h >> kHandOverShift) & 1u; }
+BB_RULE bool hand_has32(uint32_t h) { return (h >> kHandHas32Shift) & 1u; }
+BB_RULE uint32_t hand_pack(uint32_t a, uint32_t b, uint32_t c, uint32_t used, bool over, bool has32) {
+  return a | (b << 6) | (c << 12) | (used << kHandUsedShift) | ((uint32_t)over << kHandOverShift) |
+         ((uint32_t)has32 << kHandHas32Shift);
+}
+// a freshly drawn hand from its id word (has32: 0 or 1): nothing used, not over
+BB_RULE uint32_t hand_new(uint32_t ids, uint32_t has32) { return ids | (has32 << kHandHas32Shift); }
+// slot p marked used
+BB_RULE uint32_t hand_use(uint32_t h, int p) { return h | (1u << (kHandUsedShift + p)); }
+// the hand a move leaves behind: ids and has_uint32 kept, the used bits replaced, not over
+BB_RULE uint32_t hand_with_used(uint32_t h, uint32_t used) {
+  return (h & kHandIds) | (used << kHandUsedShift) | (h & (1u << kHandHas32Shift));
+}
+BB_RULE uint32_t hand_clear_used(uint32_t h) { return h & ~(7u << kHandUsedShift); }
+BB_RULE uint32_t hand_set_over(uint32_t h) { return h | (1u << kHandOverShift); }
+
+// Board.count_holes (board.py:195-216): empty cells whose four neighbours are
+// all filled or off-board.
+BB_RULE int count_holes(uint64_t B) {
+  const uint64_t n = (B << 8) | kRow0;
+  const uint64_t s = (B >> 8) | kRow7;
+  const uint64_t w = ((B << 1) & ~kCol0) | kCol0;
+  const uint64_t e = ((B >> 1) & ~kCol7) | kCol7;
+  return __builtin_popcountll(~B & n & s & w & e);
+}
+
+// --------------------------------------------------------------------------
+// Score of a move (engine.py:240-262, 406-429), select-only so that the branch-free move of the rollout kernel
+// uses it as it is.  `lines` lines cleared at combo `combo`:
+// --------------------------------------------------------------------------
+BB_RULE int line_cap(int lines) { return lines < 4 ? lines : 4; }
+// the combo multiplier: 1 without a clear
+BB_RULE int combo_multiplier(int lines) { return lines > 0 ? line_cap(lines) : 1; }
+// the combo after a move that clears, and after any move
+BB_RULE int combo_next(int combo) { return combo + 1; }
+BB_RULE int combo_after(int lines, int combo) { return lines > 0 ? combo_next(combo) : 0; }
+// score_gained of a move that placed `ncells` cells; combo1 is the combo after the move (read only with a clear,
+// so combo_next(combo) serves as well as combo_after(lines, combo))
+BB_RULE int64_t score_gained(int ncells, int lines, int combo1) {
+  const int cm = line_cap(lines);
+  const int streak = combo1 + 1 < 8 ? combo1 + 1 : 8;  // post-increment combo (engine.py:261)
+  // blocks_in_lines = lines * 8 (engine.py:427)
+  return lines > 0 ? ncells + (int64_t)(lines * 8 * 10) * cm * streak : (int64_t)ncells;
+}
+
+// _calculate_reward of a legal move (block_blast_env.py:158-193) in fp64.  The operation order is the
+// contract (it is the reference's, and the results are compared bit for bit); both libraries are built with
+// -ffp-contract=off, so none of these pairs is fused.  center_tenth = cfg.center_bonus * 0.1; holes / centre
+// are the post-move hole and filled-centre counts, prev the pre-move ones (_prev_holes | centre << 8).
+BB_RULE double move_reward(const bb_reward_cfg& cfg, double center_tenth, int ncells, int lines, int cm, bool over,
+                           int holes, int centre, uint32_t prev) {
+  double R = 0.0;
+  R += (double)ncells * cfg.block_placed;
+  R += cfg.survival_bonus;
+  if (lines > 0) {
+    double lr = (double)lines * cfg.line_clear_base;
+    lr *= (double)cm;
+    R += lr;
+    if (cm > 1) R += (double)(cm - 1) * cfg.combo_multiplier_bonus;
+  }
+  if (over) R += cfg.game_over_penalty;
+  const int dh = holes - (int)(prev & 0xFFu);
+  if (dh > 0) R += (double)dh * cfg.hole_penalty;
+  if (centre <= (int)(prev >> 8)) R += center_tenth;  // openness >= previous
+  return R;
+}
+
+// --------------------------------------------------------------------------
+// One-ply lookahead (bbvec.h bb_afterstates / bb_greedy_actions / bb_plan_actions)
+// --------------------------------------------------------------------------
+// What one legal placement leads to (illegal: legal == false and the rest unspecified).
+struct After {
+  bool legal, dead, refill;
+  uint64_t board;  // B' (after the clears)
+  int ncells, lines, combo1, holes, centre, filled, mobility;
+  int64_t gained;
+};
+
+// the reward of the placement, with game_over = dead
+BB_RULE double after_reward(const After& a, const bb_reward_cfg& cfg, double center_tenth, uint32_t prev) {
+  return move_reward(cfg, center_tenth, a.ncells, a.lines, combo_multiplier(a.lines), a.dead, a.holes, a.centre, prev);
+}
+
+// the aux word of bb_afterstate_out
+BB_RULE uint32_t pack_aux(const After& a) {
+  return 1u | ((uint32_t)a.dead << 1) | ((uint32_t)a.refill << 2) | ((uint32_t)a.lines << 8) |
+         ((uint32_t)a.holes << 12) | ((uint32_t)a.centre << 19) | ((uint32_t)a.mobility << 24);
+}
+
+// The greedy value of a placement is move_terms + state_terms; a plan sums the move terms of its plies and
+// adds the state terms of its last afterstate.
+BB_RULE int64_t move_terms(const bb_greedy_weights& w, const After& a) {
+  return (int64_t)w.lines * a.lines + (int64_t)w.score * a.gained;
+}
+
+BB_RULE int64_t state_terms(const bb_greedy_weights& w, const After& a) {
+  return (int64_t)w.holes * a.holes + (int64_t)w.filled * a.filled + (int64_t)w.centre * a.centre +
+         (int64_t)w.mobility * a.mobility + (int64_t)w.dead * (int)a.dead + (int64_t)w.refill * (int)a.refill;
+}
+
+// --------------------------------------------------------------------------
+// The info record of one step (block_blast_env.py:266-288): totals after the move and before any auto-reset,
+// then the move's own summary.
+// --------------------------------------------------------------------------
+BB_RULE bb_info make_info(int64_t score, int64_t gained, uint64_t board, int32_t moves, int32_t lines_tot,
+                          int32_t max_combo, int32_t blocks, uint32_t hand, int holes, bool valid, bool term,
+                          int nblk, int lines, int cm) {
+  bb_info f;
+  f.score = score;
+  f.score_gained = gained;
+  f.term_board = board;
+  f.moves = moves;
+  f.lines = lines_tot;
+  f.max_combo = max_combo;
+  f.blocks = blocks;
+  f.term_hand = hand;
+  f.holes = (uint8_t)holes;
+  f.filled = (uint8_t)__builtin_popcountll(board);
+  f.flags = (uint8_t)((valid ? 4u : 1u) | (term ? 2u : 0u));
+  f.last_blocks = (uint8_t)nblk;
+  f.last_lines = (uint8_t)lines;
+  f.last_cm = (uint8_t)cm;
+  f.pad[0] = f.pad[1] = 0;
+  return f;
+}
+
+}  // namespace bb

@@ -39,6 +39,30 @@ def test_build_id_is_these_sources(lib):
     assert B.built_id(host) == B.host_source_id() == L.build_id(host=True)
 
 
+def _quoted_includes(sources):
+    """Every file reached from `sources` through #include "..." lines, followed recursively."""
+    seen, todo = set(), [os.path.realpath(s) for s in sources]
+    while todo:
+        f = todo.pop()
+        if f in seen:
+            continue
+        seen.add(f)
+        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(f).read(), flags=re.M):
+            todo.append(os.path.realpath(os.path.join(os.path.dirname(f), inc)))
+    return seen
+
+
+def test_build_id_hashes_every_included_file():
+    """A header that a source includes but the id does not hash would leave a stale library looking current."""
+    from runtime import build as B
+
+    for sources, headers in ((B.SOURCES, B.HEADERS), (B.HOST_SOURCES, B.HOST_HEADERS)):
+        hashed = {os.path.realpath(os.path.join(B.CSRC, f)) for f in sources + headers} | {os.path.realpath(B.HEADER)}
+        found = _quoted_includes([os.path.join(B.CSRC, s) for s in sources])
+        assert len(found) > len(sources)
+        assert found <= hashed, sorted(os.path.relpath(f, B.CSRC) for f in found - hashed)
+
+
 def test_stale_library_is_refused(lib, tmp_path, monkeypatch):
     """A library whose id differs from the sources beside it is refused by name, not loaded silently."""
     from runtime import build as B
