@@ -716,142 +716,59 @@ extern "C" int64_t bb_bn_workspace_bytes(int32_t dtype, int32_t nhwc, int32_t N,
 }
 
 namespace {
-int bn_forward_impl(const void* d_x, const void* d_res, int32_t dtype, int32_t nhwc, int32_t N, int32_t C, int32_t HW,
-                    const float* d_pre_bias, const float* d_weight, const float* d_bias, float eps, int32_t relu,
-                    double* d_ws, float* d_save_mean, float* d_save_invstd, float* d_running_mean,
-                    float* d_running_var, float momentum, int64_t* d_num_batches_tracked, void* d_y, void* stream,
-                    const char* what, const double* d_part = nullptr, int32_t nb_part = 0) {
-  int rc = bn_check(dtype, nhwc, N, C, HW);
+bool al16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
+
+// Every rule of an argument struct (include/bbvec.h), checked before any HIP call.
+int bn_fwd_check(const bb_bn_fwd* a) {
+  if (!a) return fail(nullptr, BB_ERR_ARG, "bb_bn_forward: NULL argument struct");
+  int rc = bn_check(a->dtype, a->nhwc, a->N, a->C, a->HW);
   if (rc != BB_OK) return rc;
-  if (!d_x || !d_weight || !d_bias || !d_ws || !d_save_mean || !d_save_invstd || !d_y)
-    return fail(nullptr, BB_ERR_ARG, std::string(what) + ": NULL argument");
-  if (reinterpret_cast<uintptr_t>(d_ws) % 16 != 0) return fail(nullptr, BB_ERR_ARG, "bb_bn: d_ws must be 16-byte aligned");
-  if (d_res && reinterpret_cast<uintptr_t>(d_res) % 16 != 0)
-    return fail(nullptr, BB_ERR_ARG, "bb_bn: d_res must be 16-byte aligned");
-  hipError_t st = launch_bn_forward(d_x, d_res, dtype, nhwc, N, C, HW, d_pre_bias, d_weight, d_bias, eps, relu, d_ws,
-                                    d_save_mean, d_save_invstd, d_running_mean, d_running_var, momentum,
-                                    d_num_batches_tracked, d_y, (hipStream_t)stream, d_part, nb_part);
-  if (st != hipSuccess) return hip_fail(nullptr, st, what);
+  if (!a->x || !a->weight || !a->bias || !a->ws || !a->save_mean || !a->save_invstd || !a->y)
+    return fail(nullptr, BB_ERR_ARG, "bb_bn_forward: NULL argument");
+  if (!al16(a->ws)) return fail(nullptr, BB_ERR_ARG, "bb_bn: ws must be 16-byte aligned");
+  if (!al16(a->res)) return fail(nullptr, BB_ERR_ARG, "bb_bn: res must be 16-byte aligned");
+  if (a->part && a->nb_part <= 0) return fail(nullptr, BB_ERR_ARG, "bb_bn_forward: part needs nb_part > 0");
+  return BB_OK;
+}
+
+int bn_bwd_check(const bb_bn_bwd* a) {
+  if (!a) return fail(nullptr, BB_ERR_ARG, "bb_bn_backward: NULL argument struct");
+  int rc = bn_check(a->dtype, a->nhwc, a->N, a->C, a->HW);
+  if (rc != BB_OK) return rc;
+  if (!a->x || !a->dy || !a->weight || !a->bias || !a->save_mean || !a->save_invstd || !a->ws || !a->dx)
+    return fail(nullptr, BB_ERR_ARG, "bb_bn_backward: NULL argument");
+  if (!al16(a->ws)) return fail(nullptr, BB_ERR_ARG, "bb_bn: ws must be 16-byte aligned");
+  if (a->part && a->nb_part <= 0) return fail(nullptr, BB_ERR_ARG, "bb_bn_backward: part needs nb_part > 0");
+  if (!a->y != !a->gres) return fail(nullptr, BB_ERR_ARG, "bb_bn_backward: y and gres come together");
+  if (a->y && (a->relu != 0 || a->part))
+    return fail(nullptr, BB_ERR_ARG, "bb_bn_backward: y (the ReLU mask) takes relu = 0 and no part");
+  const bb_wgrad_reduce& r = a->reduce;
+  if (r.ws && (!r.dw || r.chunks <= 0 || (r.w_layout != 0 && r.w_layout != 1) || !conv3x3_supported(r.cin, r.cout)))
+    return fail(nullptr, BB_ERR_ARG, "bb_bn_backward: bad convolution reduction arguments");
+  return BB_OK;
+}
+
+// stats: the forward's outputs are required; grad: the backward's
+int loss_check(const bb_ppo_loss_args* a, bool stats, bool grad, const char* what) {
+  if (!a || a->B <= 0 || !a->logits || !a->values || !a->mask || !a->actions || !a->old_logp || !a->adv || !a->ret ||
+      (stats && (!a->ws || !a->cnt || !a->stats)) || (grad && (!a->grad_loss || !a->dlogits || !a->dvalues)))
+    return fail(nullptr, BB_ERR_ARG, std::string(what) + ": bad arguments");
   return BB_OK;
 }
 }  // namespace
 
-extern "C" int bb_bn_forward_part(const void* d_x, const void* d_res, int32_t dtype, int32_t nhwc, int32_t N,
-                                  int32_t C, int32_t HW, const float* d_pre_bias, const float* d_weight,
-                                  const float* d_bias, float eps, int32_t relu, double* d_ws, float* d_save_mean,
-                                  float* d_save_invstd, float* d_running_mean, float* d_running_var, float momentum,
-                                  int64_t* d_num_batches_tracked, void* d_y, const double* d_part, int32_t nb_part,
-                                  void* stream) {
-  if (!d_part || nb_part <= 0) return fail(nullptr, BB_ERR_ARG, "bb_bn_forward_part: no statistics partials");
-  return bn_forward_impl(d_x, d_res, dtype, nhwc, N, C, HW, d_pre_bias, d_weight, d_bias, eps, relu, d_ws,
-                         d_save_mean, d_save_invstd, d_running_mean, d_running_var, momentum, d_num_batches_tracked,
-                         d_y, stream, "bb_bn_forward_part", d_part, nb_part);
-}
-
-extern "C" int bb_bn_forward(const void* d_x, int32_t dtype, int32_t nhwc, int32_t N, int32_t C, int32_t HW,
-                             const float* d_pre_bias, const float* d_weight, const float* d_bias, float eps,
-                             int32_t relu, double* d_ws, float* d_save_mean, float* d_save_invstd,
-                             float* d_running_mean, float* d_running_var, float momentum,
-                             int64_t* d_num_batches_tracked, void* d_y, void* stream) {
-  return bn_forward_impl(d_x, nullptr, dtype, nhwc, N, C, HW, d_pre_bias, d_weight, d_bias, eps, relu, d_ws,
-                         d_save_mean, d_save_invstd, d_running_mean, d_running_var, momentum, d_num_batches_tracked,
-                         d_y, stream, "bb_bn_forward");
-}
-
-extern "C" int bb_bn_forward_res(const void* d_x, const void* d_res, int32_t dtype, int32_t nhwc, int32_t N,
-                                 int32_t C, int32_t HW, const float* d_pre_bias, const float* d_weight,
-                                 const float* d_bias, float eps, int32_t relu, double* d_ws, float* d_save_mean,
-                                 float* d_save_invstd, float* d_running_mean, float* d_running_var, float momentum,
-                                 int64_t* d_num_batches_tracked, void* d_y, void* stream) {
-  if (!d_res) return fail(nullptr, BB_ERR_ARG, "bb_bn_forward_res: NULL residual");
-  return bn_forward_impl(d_x, d_res, dtype, nhwc, N, C, HW, d_pre_bias, d_weight, d_bias, eps, relu, d_ws,
-                         d_save_mean, d_save_invstd, d_running_mean, d_running_var, momentum, d_num_batches_tracked,
-                         d_y, stream, "bb_bn_forward_res");
-}
-
-extern "C" int bb_bn_backward(const void* d_x, const void* d_dy, int32_t dtype, int32_t nhwc, int32_t N, int32_t C,
-                              int32_t HW, const float* d_pre_bias, const float* d_weight, const float* d_bias,
-                              const float* d_save_mean, const float* d_save_invstd, int32_t relu, double* d_ws,
-                              void* d_dx, float* d_dweight, float* d_dbias, float* d_dpre_bias, void* stream) {
-  int rc = bn_check(dtype, nhwc, N, C, HW);
+extern "C" int bb_bn_forward(const bb_bn_fwd* a, void* stream) {
+  int rc = bn_fwd_check(a);
   if (rc != BB_OK) return rc;
-  if (!d_x || !d_dy || !d_weight || !d_bias || !d_save_mean || !d_save_invstd || !d_ws || !d_dx)
-    return fail(nullptr, BB_ERR_ARG, "bb_bn_backward: NULL argument");
-  if (reinterpret_cast<uintptr_t>(d_ws) % 16 != 0) return fail(nullptr, BB_ERR_ARG, "bb_bn: d_ws must be 16-byte aligned");
-  hipError_t st = launch_bn_backward(d_x, d_dy, dtype, nhwc, N, C, HW, d_pre_bias, d_weight, d_bias, d_save_mean,
-                                     d_save_invstd, relu, d_ws, d_dx, d_dweight, d_dbias, d_dpre_bias,
-                                     (hipStream_t)stream);
-  if (st != hipSuccess) return hip_fail(nullptr, st, "bb_bn_backward");
-  return BB_OK;
+  hipError_t st = launch_bn_forward(*a, (hipStream_t)stream);
+  return st == hipSuccess ? BB_OK : hip_fail(nullptr, st, "bb_bn_forward");
 }
 
-extern "C" int bb_bn_backward_red(const void* d_x, const void* d_dy, int32_t dtype, int32_t nhwc, int32_t N, int32_t C,
-                                  int32_t HW, const float* d_pre_bias, const float* d_weight, const float* d_bias,
-                                  const float* d_save_mean, const float* d_save_invstd, int32_t relu, double* d_ws,
-                                  void* d_dx, float* d_dweight, float* d_dbias, float* d_dpre_bias,
-                                  const float* d_conv_ws, int32_t conv_chunks, int32_t conv_cin, int32_t conv_cout,
-                                  int32_t conv_w_layout, float* d_conv_dw, void* stream) {
-  int rc = bn_check(dtype, nhwc, N, C, HW);
+extern "C" int bb_bn_backward(const bb_bn_bwd* a, void* stream) {
+  int rc = bn_bwd_check(a);
   if (rc != BB_OK) return rc;
-  if (!d_x || !d_dy || !d_weight || !d_bias || !d_save_mean || !d_save_invstd || !d_ws || !d_dx || !d_conv_ws ||
-      !d_conv_dw || conv_chunks <= 0 || (conv_w_layout != 0 && conv_w_layout != 1) ||
-      !conv3x3_supported(conv_cin, conv_cout))
-    return fail(nullptr, BB_ERR_ARG, "bb_bn_backward_red: bad arguments");
-  if (reinterpret_cast<uintptr_t>(d_ws) % 16 != 0) return fail(nullptr, BB_ERR_ARG, "bb_bn: d_ws must be 16-byte aligned");
-  const WgradReduceJob job{d_conv_ws, conv_chunks, conv_cout, conv_cin, conv_w_layout, d_conv_dw};
-  hipError_t st = launch_bn_backward(d_x, d_dy, dtype, nhwc, N, C, HW, d_pre_bias, d_weight, d_bias, d_save_mean,
-                                     d_save_invstd, relu, d_ws, d_dx, d_dweight, d_dbias, d_dpre_bias,
-                                     (hipStream_t)stream, nullptr, nullptr, &job);
-  if (st != hipSuccess) return hip_fail(nullptr, st, "bb_bn_backward_red");
-  return BB_OK;
-}
-
-extern "C" int bb_bn_backward_part(const void* d_x, const void* d_dy, int32_t dtype, int32_t nhwc, int32_t N,
-                                   int32_t C, int32_t HW, const float* d_pre_bias, const float* d_weight,
-                                   const float* d_bias, const float* d_save_mean, const float* d_save_invstd,
-                                   int32_t relu, double* d_ws, void* d_dx, float* d_dweight, float* d_dbias,
-                                   float* d_dpre_bias, const float* d_conv_ws, int32_t conv_chunks, int32_t conv_cin,
-                                   int32_t conv_cout, int32_t conv_w_layout, float* d_conv_dw, const double* d_part,
-                                   int32_t nb_part, void* stream) {
-  int rc = bn_check(dtype, nhwc, N, C, HW);
-  if (rc != BB_OK) return rc;
-  if (!d_x || !d_dy || !d_weight || !d_bias || !d_save_mean || !d_save_invstd || !d_ws || !d_dx || !d_part ||
-      nb_part <= 0)
-    return fail(nullptr, BB_ERR_ARG, "bb_bn_backward_part: NULL argument");
-  if (reinterpret_cast<uintptr_t>(d_ws) % 16 != 0) return fail(nullptr, BB_ERR_ARG, "bb_bn: d_ws must be 16-byte aligned");
-  const bool red = d_conv_ws != nullptr;
-  if (red && (!d_conv_dw || conv_chunks <= 0 || (conv_w_layout != 0 && conv_w_layout != 1) ||
-              !conv3x3_supported(conv_cin, conv_cout)))
-    return fail(nullptr, BB_ERR_ARG, "bb_bn_backward_part: bad convolution reduction arguments");
-  const WgradReduceJob job{d_conv_ws, conv_chunks, conv_cout, conv_cin, conv_w_layout, d_conv_dw};
-  hipError_t st = launch_bn_backward(d_x, d_dy, dtype, nhwc, N, C, HW, d_pre_bias, d_weight, d_bias, d_save_mean,
-                                     d_save_invstd, relu, d_ws, d_dx, d_dweight, d_dbias, d_dpre_bias,
-                                     (hipStream_t)stream, nullptr, nullptr, red ? &job : nullptr, d_part, nb_part);
-  if (st != hipSuccess) return hip_fail(nullptr, st, "bb_bn_backward_part");
-  return BB_OK;
-}
-
-extern "C" int bb_bn_backward_res(const void* d_x, const void* d_dy, const void* d_y, int32_t dtype, int32_t nhwc,
-                                  int32_t N, int32_t C, int32_t HW, const float* d_pre_bias, const float* d_weight,
-                                  const float* d_bias, const float* d_save_mean, const float* d_save_invstd,
-                                  double* d_ws, void* d_dx, float* d_dweight, float* d_dbias, float* d_dpre_bias,
-                                  void* d_gres, const float* d_conv_ws, int32_t conv_chunks, int32_t conv_cin,
-                                  int32_t conv_cout, int32_t conv_w_layout, float* d_conv_dw, void* stream) {
-  int rc = bn_check(dtype, nhwc, N, C, HW);
-  if (rc != BB_OK) return rc;
-  if (!d_x || !d_dy || !d_y || !d_weight || !d_bias || !d_save_mean || !d_save_invstd || !d_ws || !d_dx || !d_gres)
-    return fail(nullptr, BB_ERR_ARG, "bb_bn_backward_res: NULL argument");
-  if (reinterpret_cast<uintptr_t>(d_ws) % 16 != 0) return fail(nullptr, BB_ERR_ARG, "bb_bn: d_ws must be 16-byte aligned");
-  const bool red = d_conv_ws != nullptr;
-  if (red && (!d_conv_dw || conv_chunks <= 0 || (conv_w_layout != 0 && conv_w_layout != 1) ||
-              !conv3x3_supported(conv_cin, conv_cout)))
-    return fail(nullptr, BB_ERR_ARG, "bb_bn_backward_res: bad convolution reduction arguments");
-  const WgradReduceJob job{d_conv_ws, conv_chunks, conv_cout, conv_cin, conv_w_layout, d_conv_dw};
-  hipError_t st = launch_bn_backward(d_x, d_dy, dtype, nhwc, N, C, HW, d_pre_bias, d_weight, d_bias, d_save_mean,
-                                     d_save_invstd, 0, d_ws, d_dx, d_dweight, d_dbias, d_dpre_bias, (hipStream_t)stream,
-                                     d_y, d_gres, red ? &job : nullptr);
-  if (st != hipSuccess) return hip_fail(nullptr, st, "bb_bn_backward_res");
-  return BB_OK;
+  hipError_t st = launch_bn_backward(*a, (hipStream_t)stream);
+  return st == hipSuccess ? BB_OK : hip_fail(nullptr, st, "bb_bn_backward");
 }
 
 extern "C" int64_t bb_ppo_loss_workspace_bytes(int32_t B) {
@@ -859,83 +776,25 @@ extern "C" int64_t bb_ppo_loss_workspace_bytes(int32_t B) {
   return ppo_loss_workspace_bytes(B);
 }
 
-namespace {
-int loss_forward_impl(const void* d_logits, const void* d_values, int bf16, const float* d_mask,
-                      const int64_t* d_actions, const float* d_old_logp, const float* d_adv, const float* d_ret,
-                      int32_t B, float clip, float value_coef, float entropy_coef, double* d_ws, uint32_t* d_cnt,
-                      float* d_stats, float* d_loss, void* stream, const char* what) {
-  if (B <= 0 || !d_logits || !d_values || !d_mask || !d_actions || !d_old_logp || !d_adv || !d_ret || !d_ws ||
-      !d_cnt || !d_stats)
-    return fail(nullptr, BB_ERR_ARG, std::string(what) + ": bad arguments");
-  hipError_t st = launch_ppo_loss_forward(d_logits, d_values, bf16, d_mask, d_actions, d_old_logp, d_adv, d_ret, B,
-                                          clip, value_coef, entropy_coef, d_ws, d_cnt, d_stats, d_loss,
-                                          (hipStream_t)stream);
-  if (st != hipSuccess) return hip_fail(nullptr, st, what);
-  return BB_OK;
+extern "C" int bb_ppo_loss_forward(const bb_ppo_loss_args* a, void* stream) {
+  int rc = loss_check(a, true, false, "bb_ppo_loss_forward");
+  if (rc != BB_OK) return rc;
+  hipError_t st = launch_ppo_loss_forward(*a, (hipStream_t)stream);
+  return st == hipSuccess ? BB_OK : hip_fail(nullptr, st, "bb_ppo_loss_forward");
 }
 
-int loss_backward_impl(const void* d_logits, const void* d_values, int bf16, const float* d_mask,
-                       const int64_t* d_actions, const float* d_old_logp, const float* d_adv, const float* d_ret,
-                       int32_t B, float clip, float value_coef, float entropy_coef, const float* d_grad_loss,
-                       void* d_dlogits, void* d_dvalues, void* stream, const char* what) {
-  if (B <= 0 || !d_logits || !d_values || !d_mask || !d_actions || !d_old_logp || !d_adv || !d_ret ||
-      !d_grad_loss || !d_dlogits || !d_dvalues)
-    return fail(nullptr, BB_ERR_ARG, std::string(what) + ": bad arguments");
-  hipError_t st = launch_ppo_loss_backward(d_logits, d_values, bf16, d_mask, d_actions, d_old_logp, d_adv, d_ret, B,
-                                           clip, value_coef, entropy_coef, d_grad_loss, d_dlogits, d_dvalues,
-                                           (hipStream_t)stream);
-  if (st != hipSuccess) return hip_fail(nullptr, st, what);
-  return BB_OK;
-}
-}  // namespace
-
-extern "C" int bb_ppo_loss_forward(const float* d_logits, const float* d_values, const float* d_mask,
-                                   const int64_t* d_actions, const float* d_old_logp, const float* d_adv,
-                                   const float* d_ret, int32_t B, float clip, float value_coef, float entropy_coef,
-                                   double* d_ws, uint32_t* d_cnt, float* d_stats, float* d_loss, void* stream) {
-  return loss_forward_impl(d_logits, d_values, 0, d_mask, d_actions, d_old_logp, d_adv, d_ret, B, clip, value_coef,
-                           entropy_coef, d_ws, d_cnt, d_stats, d_loss, stream, "bb_ppo_loss_forward");
+extern "C" int bb_ppo_loss_backward(const bb_ppo_loss_args* a, void* stream) {
+  int rc = loss_check(a, false, true, "bb_ppo_loss_backward");
+  if (rc != BB_OK) return rc;
+  hipError_t st = launch_ppo_loss_backward(*a, (hipStream_t)stream);
+  return st == hipSuccess ? BB_OK : hip_fail(nullptr, st, "bb_ppo_loss_backward");
 }
 
-extern "C" int bb_ppo_loss_backward(const float* d_logits, const float* d_values, const float* d_mask,
-                                    const int64_t* d_actions, const float* d_old_logp, const float* d_adv,
-                                    const float* d_ret, int32_t B, float clip, float value_coef, float entropy_coef,
-                                    const float* d_grad_loss, float* d_dlogits, float* d_dvalues, void* stream) {
-  return loss_backward_impl(d_logits, d_values, 0, d_mask, d_actions, d_old_logp, d_adv, d_ret, B, clip, value_coef,
-                            entropy_coef, d_grad_loss, d_dlogits, d_dvalues, stream, "bb_ppo_loss_backward");
-}
-
-extern "C" int bb_ppo_loss_forward_bf16(const void* d_logits, const void* d_values, const float* d_mask,
-                                        const int64_t* d_actions, const float* d_old_logp, const float* d_adv,
-                                        const float* d_ret, int32_t B, float clip, float value_coef,
-                                        float entropy_coef, double* d_ws, uint32_t* d_cnt, float* d_stats,
-                                        float* d_loss, void* stream) {
-  return loss_forward_impl(d_logits, d_values, 1, d_mask, d_actions, d_old_logp, d_adv, d_ret, B, clip, value_coef,
-                           entropy_coef, d_ws, d_cnt, d_stats, d_loss, stream, "bb_ppo_loss_forward_bf16");
-}
-
-extern "C" int bb_ppo_loss_fused(const void* d_logits, const void* d_values, int32_t bf16, const float* d_mask,
-                                 const int64_t* d_actions, const float* d_old_logp, const float* d_adv,
-                                 const float* d_ret, int32_t B, float clip, float value_coef, float entropy_coef,
-                                 const float* d_grad_loss, void* d_dlogits, void* d_dvalues, double* d_ws,
-                                 uint32_t* d_cnt, float* d_stats, float* d_loss, void* stream) {
-  if (B <= 0 || !d_logits || !d_values || !d_mask || !d_actions || !d_old_logp || !d_adv || !d_ret || !d_grad_loss ||
-      !d_dlogits || !d_dvalues || !d_ws || !d_cnt || !d_stats)
-    return fail(nullptr, BB_ERR_ARG, "bb_ppo_loss_fused: bad arguments");
-  hipError_t st = launch_ppo_loss_fused(d_logits, d_values, bf16 ? 1 : 0, d_mask, d_actions, d_old_logp, d_adv, d_ret,
-                                        B, clip, value_coef, entropy_coef, d_grad_loss, d_dlogits, d_dvalues, d_ws,
-                                        d_cnt, d_stats, d_loss, (hipStream_t)stream);
-  if (st != hipSuccess) return hip_fail(nullptr, st, "bb_ppo_loss_fused");
-  return BB_OK;
-}
-
-extern "C" int bb_ppo_loss_backward_bf16(const void* d_logits, const void* d_values, const float* d_mask,
-                                         const int64_t* d_actions, const float* d_old_logp, const float* d_adv,
-                                         const float* d_ret, int32_t B, float clip, float value_coef,
-                                         float entropy_coef, const float* d_grad_loss, void* d_dlogits,
-                                         void* d_dvalues, void* stream) {
-  return loss_backward_impl(d_logits, d_values, 1, d_mask, d_actions, d_old_logp, d_adv, d_ret, B, clip, value_coef,
-                            entropy_coef, d_grad_loss, d_dlogits, d_dvalues, stream, "bb_ppo_loss_backward_bf16");
+extern "C" int bb_ppo_loss_fused(const bb_ppo_loss_args* a, void* stream) {
+  int rc = loss_check(a, true, true, "bb_ppo_loss_fused");
+  if (rc != BB_OK) return rc;
+  hipError_t st = launch_ppo_loss_fused(*a, (hipStream_t)stream);
+  return st == hipSuccess ? BB_OK : hip_fail(nullptr, st, "bb_ppo_loss_fused");
 }
 
 namespace {
@@ -945,7 +804,6 @@ int conv_check(int32_t N, int32_t cin, int32_t cout, const char* what) {
     return fail(nullptr, BB_ERR_ARG, std::string(what) + ": channels must be 64 or 128 in and out");
   return BB_OK;
 }
-bool al16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
 }  // namespace
 
 extern "C" int64_t bb_conv3x3_workspace_bytes(int32_t N, int32_t cin, int32_t cout) {

@@ -214,10 +214,10 @@ __device__ __forceinline__ uint32_t add2_bf16(uint32_t a, uint32_t b) {  // two 
 // the workgroup's pixels (f32 per thread over its rows, the lanes of a channel by a fixed xor tree, the waves
 // added in order in f64) -> st.part[(blockIdx.x * COUT + c) * 3 + q], bn_reduce_nhwc's partial layout:
 //   st.bx NULL: the following BatchNorm's forward statistics, q = {sum y, sum y^2, 0} of the stored bf16
-//               outputs (bb_bn_forward_part finalises from them without its own pass over y);
+//               outputs (bb_bn_forward with bb_bn_fwd.part finalises from them without its own pass over y);
 //   st.bx set : this is a data gradient dy of a BatchNorm [+ ReLU] output whose input was st.bx (bf16, y's
 //               shape): q = {sum g, sum g xhat, sum xhat}, g = dy masked where the forward's ReLU was off,
-//               xhat = (x - mean) invstd -- bn_reduce_nhwc's backward arithmetic (bb_bn_backward_part).
+//               xhat = (x - mean) invstd -- bn_reduce_nhwc's backward arithmetic (bb_bn_bwd.part).
 // BSTATS: the backward-statistics instantiation (st.bx set); the others carry none of its code.
 template <int CIN, int COUT, bool BSTATS = false>
 __global__ void __launch_bounds__(kFwdThreads) conv_fwd_kernel(const uint16_t* __restrict__ x,

@@ -111,22 +111,15 @@ hipError_t launch_gae(const float* r, const float* v, const float* d, const floa
                       float gl, float* adv, float* ret, hipStream_t s);
 
 int64_t bn_workspace_bytes(int dtype, int nhwc, int N, int C, int HW);
-hipError_t launch_bn_forward(const void* x, const void* res, int dtype, int nhwc, int N, int C, int HW,
-                             const float* pb, const float* w, const float* b, float eps, int relu, double* ws,
-                             float* save_mean, float* save_invstd, float* rmean, float* rvar, float momentum,
-                             int64_t* nbt, void* y, hipStream_t s, const double* ext_part = nullptr, int ext_nb = 0);
-// a board convolution's weight-gradient partial-sum reduction (csrc/bb_conv.hip conv_wgrad_reduce's arguments),
-// run inside a BatchNorm backward finalisation's launch by bb_bn_backward_red
-struct WgradReduceJob {  // conv_wgrad_reduce's arguments
+// bb_bn_forward / bb_bn_backward behind their validation (bb_capi.cpp bn_fwd_check / bn_bwd_check)
+hipError_t launch_bn_forward(const bb_bn_fwd& a, hipStream_t s);
+// conv_wgrad_reduce's arguments (csrc/bb_conv.hip) as bn_finalize_bwd's kernel argument, filled from bb_wgrad_reduce
+struct WgradReduceJob {
   const float* part;
   int nchunk, cout, cin, wl;
   float* dw;
 };
-hipError_t launch_bn_backward(const void* x, const void* dy, int dtype, int nhwc, int N, int C, int HW,
-                              const float* pb, const float* w, const float* b, const float* mean, const float* invstd,
-                              int relu, double* ws, void* dx, float* dw, float* db, float* dpb, hipStream_t s,
-                              const void* mask = nullptr, void* gout = nullptr, const WgradReduceJob* job = nullptr,
-                              const double* ext_part = nullptr, int ext_nb = 0);
+hipError_t launch_bn_backward(const bb_bn_bwd& a, hipStream_t s);
 
 bool conv3x3_supported(int cin, int cout);
 int64_t conv3x3_wgrad_workspace_bytes(int nb, int cin, int cout);
@@ -151,7 +144,7 @@ int conv3x3_stats_blocks(int nb, int cout);
 hipError_t launch_conv3x3_wgrad(const void* x, const void* dy, int nb, int cin, int cout, float* ws, int wl,
                                 float* dw, hipStream_t s);
 // the weight gradient in two parts: the partial-sum kernel, and the fixed-order sum of its `used` chunks (which
-// bb_bn_backward_red can run inside the next BatchNorm finalisation's launch)
+// bb_bn_backward can run inside its finalisation's launch: bb_bn_bwd.reduce)
 int conv3x3_wgrad_chunks_used(int nb, int cin, int cout);
 hipError_t launch_conv3x3_wgrad_partial(const void* x, const void* dy, int nb, int cin, int cout, float* ws,
                                         hipStream_t s);
@@ -174,19 +167,9 @@ hipError_t launch_linear_f32(const float* x, const float* w, const float* bias, 
                              hipStream_t s);
 
 int64_t ppo_loss_workspace_bytes(int B);
-// logits / values (and backward's dlogits / dvalues): f32, or bf16 when bf16 != 0
-hipError_t launch_ppo_loss_forward(const void* logits, const void* values, int bf16, const float* mask,
-                                   const int64_t* actions, const float* old_logp, const float* adv, const float* ret,
-                                   int B, float clip, float vcoef, float ecoef, double* ws, uint32_t* cnt, float* stats,
-                                   float* loss, hipStream_t s);
-hipError_t launch_ppo_loss_backward(const void* logits, const void* values, int bf16, const float* mask,
-                                    const int64_t* actions, const float* old_logp, const float* adv, const float* ret,
-                                    int B, float clip, float vcoef, float ecoef, const float* gloss, void* dlogits,
-                                    void* dvalues, hipStream_t s);
-hipError_t launch_ppo_loss_fused(const void* logits, const void* values, int bf16, const float* mask,
-                                 const int64_t* actions, const float* old_logp, const float* adv, const float* ret,
-                                 int B, float clip, float vcoef, float ecoef, const float* gloss, void* dlogits,
-                                 void* dvalues, double* ws, uint32_t* cnt, float* stats, float* loss, hipStream_t s);
+hipError_t launch_ppo_loss_forward(const bb_ppo_loss_args& a, hipStream_t s);
+hipError_t launch_ppo_loss_backward(const bb_ppo_loss_args& a, hipStream_t s);
+hipError_t launch_ppo_loss_fused(const bb_ppo_loss_args& a, hipStream_t s);
 
 constexpr int kOptMaxTensors = 48;  // == BB_OPT_MAX_TENSORS
 int64_t adam_clip_workspace_bytes(int count, const int64_t* n);

@@ -285,54 +285,19 @@ int loss_blocks(int B) {
 int64_t ppo_loss_workspace_bytes(int B) { return (int64_t)sizeof(double) * kStats * loss_blocks(B); }
 
 // stats / loss from one launch: block partials summed by the last block to arrive (cnt: a zeroed counter)
-hipError_t launch_ppo_loss_forward(const void* logits, const void* values, int bf16, const float* mask,
-                                   const int64_t* actions, const float* old_logp, const float* adv, const float* ret,
-                                   int B, float clip, float vcoef, float ecoef, double* ws, uint32_t* cnt, float* stats,
-                                   float* loss, hipStream_t s) {
-  if (B <= 0 || !cnt) return hipErrorInvalidValue;
-  const int nb = loss_blocks(B);
-  if (bf16)
-    hipLaunchKernelGGL((ppo_loss_kernel<true, true, false>), dim3(nb), dim3(kLossThreads), 0, s, logits, values, mask,
-                       actions, old_logp, adv, ret, B, clip, vcoef, ecoef, nullptr, nullptr, nullptr, ws, cnt, stats,
-                       loss);
-  else
-    hipLaunchKernelGGL((ppo_loss_kernel<false, true, false>), dim3(nb), dim3(kLossThreads), 0, s, logits, values, mask,
-                       actions, old_logp, adv, ret, B, clip, vcoef, ecoef, nullptr, nullptr, nullptr, ws, cnt, stats,
-                       loss);
+// STATS: the forward's half (a.ws, a.cnt, a.stats, a.loss); GRAD: the backward's (a.grad_loss, a.dlogits, a.dvalues)
+template <bool STATS, bool GRAD>
+hipError_t launch_ppo_loss(const bb_ppo_loss_args& a, hipStream_t s) {
+  if (a.B <= 0 || (STATS && !a.cnt)) return hipErrorInvalidValue;
+  const auto kernel = a.bf16 ? ppo_loss_kernel<true, STATS, GRAD> : ppo_loss_kernel<false, STATS, GRAD>;
+  hipLaunchKernelGGL(kernel, dim3(loss_blocks(a.B)), dim3(kLossThreads), 0, s, a.logits, a.values, a.mask, a.actions,
+                     a.old_logp, a.adv, a.ret, a.B, a.clip, a.value_coef, a.entropy_coef, GRAD ? a.grad_loss : nullptr,
+                     GRAD ? a.dlogits : nullptr, GRAD ? a.dvalues : nullptr, STATS ? a.ws : nullptr,
+                     STATS ? a.cnt : nullptr, STATS ? a.stats : nullptr, STATS ? a.loss : nullptr);
   return hipGetLastError();
 }
-
-hipError_t launch_ppo_loss_backward(const void* logits, const void* values, int bf16, const float* mask,
-                                    const int64_t* actions, const float* old_logp, const float* adv, const float* ret,
-                                    int B, float clip, float vcoef, float ecoef, const float* gloss, void* dlogits,
-                                    void* dvalues, hipStream_t s) {
-  if (B <= 0) return hipErrorInvalidValue;
-  if (bf16)
-    hipLaunchKernelGGL((ppo_loss_kernel<true, false, true>), dim3(loss_blocks(B)), dim3(kLossThreads), 0, s, logits,
-                       values, mask, actions, old_logp, adv, ret, B, clip, vcoef, ecoef, gloss, dlogits, dvalues,
-                       nullptr, nullptr, nullptr, nullptr);
-  else
-    hipLaunchKernelGGL((ppo_loss_kernel<false, false, true>), dim3(loss_blocks(B)), dim3(kLossThreads), 0, s, logits,
-                       values, mask, actions, old_logp, adv, ret, B, clip, vcoef, ecoef, gloss, dlogits, dvalues,
-                       nullptr, nullptr, nullptr, nullptr);
-  return hipGetLastError();
-}
-
-hipError_t launch_ppo_loss_fused(const void* logits, const void* values, int bf16, const float* mask,
-                                 const int64_t* actions, const float* old_logp, const float* adv, const float* ret,
-                                 int B, float clip, float vcoef, float ecoef, const float* gloss, void* dlogits,
-                                 void* dvalues, double* ws, uint32_t* cnt, float* stats, float* loss, hipStream_t s) {
-  if (B <= 0 || !cnt) return hipErrorInvalidValue;
-  const int nb = loss_blocks(B);
-  if (bf16)
-    hipLaunchKernelGGL((ppo_loss_kernel<true, true, true>), dim3(nb), dim3(kLossThreads), 0, s, logits, values, mask,
-                       actions, old_logp, adv, ret, B, clip, vcoef, ecoef, gloss, dlogits, dvalues, ws, cnt, stats,
-                       loss);
-  else
-    hipLaunchKernelGGL((ppo_loss_kernel<false, true, true>), dim3(nb), dim3(kLossThreads), 0, s, logits, values, mask,
-                       actions, old_logp, adv, ret, B, clip, vcoef, ecoef, gloss, dlogits, dvalues, ws, cnt, stats,
-                       loss);
-  return hipGetLastError();
-}
+hipError_t launch_ppo_loss_forward(const bb_ppo_loss_args& a, hipStream_t s) { return launch_ppo_loss<true, false>(a, s); }
+hipError_t launch_ppo_loss_backward(const bb_ppo_loss_args& a, hipStream_t s) { return launch_ppo_loss<false, true>(a, s); }
+hipError_t launch_ppo_loss_fused(const bb_ppo_loss_args& a, hipStream_t s) { return launch_ppo_loss<true, true>(a, s); }
 
 }  // namespace bb

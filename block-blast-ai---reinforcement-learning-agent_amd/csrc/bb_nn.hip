@@ -391,7 +391,7 @@ __global__ void __launch_bounds__(kBnThreads) bn_finalize_fwd(const double* __re
 // Backward finalisation: dweight = sum(g * xhat), dbias = sum(g), the
 // convolution bias gradient sum(dx) (dx = sc * (g - mg - xhat * mgx) summed in
 // fp64), coefficients.
-// With a WgradReduceJob (bb_bn_backward_red): blocks from the finalisation's on add a preceding board convolution's
+// With a WgradReduceJob (bb_bn_bwd.reduce): blocks from the finalisation's on add a preceding board convolution's
 // weight-gradient partials instead -- two independent small passes in one launch.
 __global__ void __launch_bounds__(kBnThreads) bn_finalize_bwd(const double* __restrict__ part, int nb, int C, double M,
                                                               const float* __restrict__ pre_bias,
@@ -612,57 +612,55 @@ Ws split_ws(double* ws, int C) {
 }
 
 template <typename T>
-hipError_t bn_forward_t(const void* x, const void* res, int nhwc, int N, int C, int HW, const float* pb, const float* w,
-                        const float* b, float eps, int relu, double* ws, float* save_mean, float* save_invstd,
-                        float* rmean, float* rvar, float momentum, int64_t* nbt, void* y, hipStream_t s,
-                        const double* ext_part, int ext_nb) {
-  const Plan p = plan_for(sizeof(T), nhwc, N, C, HW);
-  const Ws k = split_ws(ws, C);
-  // ext_part: the block partials a preceding board convolution's store pass produced (conv_fwd_kernel stats)
-  const double* part = ext_part ? ext_part : k.part;
-  const int nbp = ext_part ? ext_nb : p.nb;
-  if (!ext_part) launch_reduce<T, false>(p, nhwc, x, nullptr, N, C, HW, pb, w, b, nullptr, nullptr, 0, k.part, s);
-  hipLaunchKernelGGL(bn_finalize_fwd, dim3((C + kFinCpb - 1) / kFinCpb), dim3(kBnThreads), 0, s, part, nbp, C, (double)N * HW, eps,
-                     pb, w, b, save_mean, save_invstd, rmean, rvar, momentum, nbt, k.coef);
-  const dim3 ge(grid_for_elems(p.chunks, nhwc));
-  if (nhwc)
-    hipLaunchKernelGGL((bn_apply_fwd<T, true>), ge, dim3(kBnThreads), 0, s, x, res, y, p.chunks, C, p.cpr, relu,
-                       k.coef);
+hipError_t bn_forward_t(const bb_bn_fwd& a, hipStream_t s) {
+  const int C = a.C;
+  const Plan p = plan_for(sizeof(T), a.nhwc, a.N, C, a.HW);
+  const Ws k = split_ws(a.ws, C);
+  // a.part: the block partials a preceding board convolution's store pass produced (conv_fwd_kernel stats)
+  const double* part = a.part ? a.part : k.part;
+  const int nbp = a.part ? a.nb_part : p.nb;
+  if (!a.part)
+    launch_reduce<T, false>(p, a.nhwc, a.x, nullptr, a.N, C, a.HW, a.pre_bias, a.weight, a.bias, nullptr, nullptr, 0,
+                            k.part, s);
+  hipLaunchKernelGGL(bn_finalize_fwd, dim3((C + kFinCpb - 1) / kFinCpb), dim3(kBnThreads), 0, s, part, nbp, C,
+                     (double)a.N * a.HW, a.eps, a.pre_bias, a.weight, a.bias, a.save_mean, a.save_invstd,
+                     a.running_mean, a.running_var, a.momentum, a.num_batches_tracked, k.coef);
+  const dim3 ge(grid_for_elems(p.chunks, a.nhwc));
+  if (a.nhwc)
+    hipLaunchKernelGGL((bn_apply_fwd<T, true>), ge, dim3(kBnThreads), 0, s, a.x, a.res, a.y, p.chunks, C, p.cpr,
+                       a.relu, k.coef);
   else
-    hipLaunchKernelGGL((bn_apply_fwd<T, false>), ge, dim3(kBnThreads), 0, s, x, res, y, p.chunks, C, p.cpr, relu,
-                       k.coef);
+    hipLaunchKernelGGL((bn_apply_fwd<T, false>), ge, dim3(kBnThreads), 0, s, a.x, a.res, a.y, p.chunks, C, p.cpr,
+                       a.relu, k.coef);
   return hipGetLastError();
 }
 
 template <typename T>
-hipError_t bn_backward_t(const void* x, const void* dy, int nhwc, int N, int C, int HW, const float* pb,
-                         const float* w, const float* b, const float* mean, const float* invstd, int relu, double* ws,
-                         void* dx, float* dw, float* db, float* dpb, hipStream_t s, const void* mask, void* gout,
-                         const WgradReduceJob* job, const double* ext_part, int ext_nb) {
-  const Plan p = plan_for(sizeof(T), nhwc, N, C, HW);
-  const Ws k = split_ws(ws, C);
-  // with a mask (the ResidualBlock tail): the reduction writes the masked gradient g to gout, and the
-  // elementwise pass reads g as its dy (no mask there).  ext_part (no mask): the reduction's partials came
+hipError_t bn_backward_t(const bb_bn_bwd& a, hipStream_t s) {
+  const int C = a.C;
+  const Plan p = plan_for(sizeof(T), a.nhwc, a.N, C, a.HW);
+  const Ws k = split_ws(a.ws, C);
+  // with a.y (the ResidualBlock tail): the reduction writes the masked gradient g to a.gres, and the
+  // elementwise pass reads g as its dy (no mask there).  a.part (never with a.y): the reduction's partials came
   // from the board convolution that produced dy (conv_fwd_kernel's backward statistics)
-  if (ext_part && mask) return hipErrorInvalidValue;
-  const double* part = ext_part ? ext_part : k.part;
-  const int nbp = ext_part ? ext_nb : p.nb;
-  if (!ext_part) launch_reduce<T, true>(p, nhwc, x, dy, N, C, HW, pb, w, b, mean, invstd, relu, k.part, s, mask, gout);
-  if (mask) dy = gout;
-  WgradReduceJob jb{};
-  int red_blocks = 0;
-  if (job) {
-    jb = *job;
-    red_blocks = (9 * jb.cout * jb.cin + kBnThreads - 1) / kBnThreads;
-  }
-  hipLaunchKernelGGL(bn_finalize_bwd, dim3((C + kFinCpb - 1) / kFinCpb + red_blocks), dim3(kBnThreads), 0, s, part, nbp, C,
-                     (double)N * HW, pb, w, b, mean, invstd, dw, db, dpb, k.coef, jb);
-  const dim3 ge(grid_for_elems(p.chunks, nhwc));
-  if (nhwc)
-    hipLaunchKernelGGL((bn_apply_bwd<T, true>), ge, dim3(kBnThreads), 0, s, x, dy, dx, p.chunks, C, p.cpr, relu,
+  const double* part = a.part ? a.part : k.part;
+  const int nbp = a.part ? a.nb_part : p.nb;
+  if (!a.part)
+    launch_reduce<T, true>(p, a.nhwc, a.x, a.dy, a.N, C, a.HW, a.pre_bias, a.weight, a.bias, a.save_mean,
+                           a.save_invstd, a.relu, k.part, s, a.y, a.gres);
+  const void* dy = a.y ? a.gres : a.dy;
+  const bb_wgrad_reduce& r = a.reduce;
+  const WgradReduceJob jb = r.ws ? WgradReduceJob{r.ws, r.chunks, r.cout, r.cin, r.w_layout, r.dw} : WgradReduceJob{};
+  const int red_blocks = r.ws ? (9 * jb.cout * jb.cin + kBnThreads - 1) / kBnThreads : 0;
+  hipLaunchKernelGGL(bn_finalize_bwd, dim3((C + kFinCpb - 1) / kFinCpb + red_blocks), dim3(kBnThreads), 0, s, part,
+                     nbp, C, (double)a.N * a.HW, a.pre_bias, a.weight, a.bias, a.save_mean, a.save_invstd, a.dweight,
+                     a.dbias, a.dpre_bias, k.coef, jb);
+  const dim3 ge(grid_for_elems(p.chunks, a.nhwc));
+  if (a.nhwc)
+    hipLaunchKernelGGL((bn_apply_bwd<T, true>), ge, dim3(kBnThreads), 0, s, a.x, dy, a.dx, p.chunks, C, p.cpr, a.relu,
                        k.coef);
   else
-    hipLaunchKernelGGL((bn_apply_bwd<T, false>), ge, dim3(kBnThreads), 0, s, x, dy, dx, p.chunks, C, p.cpr, relu,
+    hipLaunchKernelGGL((bn_apply_bwd<T, false>), ge, dim3(kBnThreads), 0, s, a.x, dy, a.dx, p.chunks, C, p.cpr, a.relu,
                        k.coef);
   return hipGetLastError();
 }
@@ -674,27 +672,12 @@ int64_t bn_workspace_bytes(int dtype, int nhwc, int N, int C, int HW) {
   return (int64_t)sizeof(double) * C * (kCoef / 2 + kQ * (int64_t)p.nb);
 }
 
-hipError_t launch_bn_forward(const void* x, const void* res, int dtype, int nhwc, int N, int C, int HW,
-                             const float* pb, const float* w, const float* b, float eps, int relu, double* ws,
-                             float* save_mean, float* save_invstd, float* rmean, float* rvar, float momentum,
-                             int64_t* nbt, void* y, hipStream_t s, const double* ext_part, int ext_nb) {
-  if (dtype == 1)
-    return bn_forward_t<__hip_bfloat16>(x, res, nhwc, N, C, HW, pb, w, b, eps, relu, ws, save_mean, save_invstd, rmean,
-                                        rvar, momentum, nbt, y, s, ext_part, ext_nb);
-  return bn_forward_t<float>(x, res, nhwc, N, C, HW, pb, w, b, eps, relu, ws, save_mean, save_invstd, rmean, rvar, momentum,
-                             nbt, y, s, ext_part, ext_nb);
+hipError_t launch_bn_forward(const bb_bn_fwd& a, hipStream_t s) {
+  return a.dtype == 1 ? bn_forward_t<__hip_bfloat16>(a, s) : bn_forward_t<float>(a, s);
 }
 
-hipError_t launch_bn_backward(const void* x, const void* dy, int dtype, int nhwc, int N, int C, int HW,
-                              const float* pb, const float* w, const float* b, const float* mean, const float* invstd,
-                              int relu, double* ws, void* dx, float* dw, float* db, float* dpb, hipStream_t s,
-                              const void* mask, void* gout, const WgradReduceJob* job, const double* ext_part,
-                              int ext_nb) {
-  if (dtype == 1)
-    return bn_backward_t<__hip_bfloat16>(x, dy, nhwc, N, C, HW, pb, w, b, mean, invstd, relu, ws, dx, dw, db, dpb, s,
-                                         mask, gout, job, ext_part, ext_nb);
-  return bn_backward_t<float>(x, dy, nhwc, N, C, HW, pb, w, b, mean, invstd, relu, ws, dx, dw, db, dpb, s, mask, gout,
-                              job, ext_part, ext_nb);
+hipError_t launch_bn_backward(const bb_bn_bwd& a, hipStream_t s) {
+  return a.dtype == 1 ? bn_backward_t<__hip_bfloat16>(a, s) : bn_backward_t<float>(a, s);
 }
 
 }  // namespace bb

@@ -297,7 +297,7 @@ def bn_fusable(x: torch.Tensor) -> bool:
 
 
 # BatchNorm batch statistics from the producing convolution's store pass (bb_conv3x3_forward_stats ->
-# bb_bn_forward_part): no reduction pass over the convolution's output (0: bb_bn_forward's own pass, for A/B)
+# bb_bn_fwd.part): no reduction pass over the convolution's output (0: bb_bn_forward's own pass, for A/B)
 CONV_STATS = os.environ.get("BB_CONV_STATS", "1") != "0"
 # ... and a ResidualBlock's bn1 backward sums from conv2's data-gradient store pass (bb_conv3x3_forward_bstats).
 # Off: 1.510 against 1.503 ms per update step (the store pass's +11.5 us per launch outweighs the 13.6 us
@@ -333,26 +333,55 @@ def _bn_workspace(x: torch.Tensor, nhwc: int) -> torch.Tensor:
     return torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=x.device)
 
 
-def _bn_backward_call(x, dy, nhwc, pre_bias, weight, bias, mean, invstd, relu: int, ws, dx, dw, db, dpb, dev,
-                      part=None):
-    """bb_bn_backward, or bb_bn_backward_red carrying a board convolution's pending weight-gradient reduction
-    (wgrad_piggyback) in its finalisation launch; part = (partials, blocks): bb_bn_backward_part (the reduction
-    sums from the convolution that produced dy)."""
+def _a(t: Optional[torch.Tensor]):
+    """A tensor's address for a pointer field of an argument struct (None: NULL, the field is absent)."""
+    return None if t is None else t.data_ptr()
+
+
+def _bn_forward_call(x, nhwc, pre_bias, weight, bias, running_mean, running_var, momentum, eps, relu, nbt, stats,
+                     res=None):
+    """bb_bn_forward into fresh tensors -> (y, saved mean, saved inverse std).  res: the residual added before the
+    ReLU; stats: a StatsSlot whose partials, when they are x's, replace the reduction pass (bb_bn_fwd.part)."""
     n, c, h, w = x.shape
-    lib = L.load()
+    dev = x.device
+    y = torch.empty_like(x)
+    ws = _bn_workspace(x, nhwc)
+    mean = torch.empty(c, dtype=torch.float32, device=dev)
+    invstd = torch.empty(c, dtype=torch.float32, device=dev)
+    part, nb_part = _stats_for(stats, x) or (None, 0)
+    a = L.BnFwd(x=_a(x), res=_a(res), dtype=_BN_DTYPES[x.dtype], nhwc=nhwc, N=n, C=c, HW=h * w, pre_bias=_a(pre_bias),
+                weight=_a(weight), bias=_a(bias), eps=float(eps), relu=int(relu), ws=_a(ws), save_mean=_a(mean),
+                save_invstd=_a(invstd), running_mean=_a(running_mean), running_var=_a(running_var),
+                momentum=float(momentum), num_batches_tracked=_a(nbt), y=_a(y), part=_a(part), nb_part=nb_part)
+    L.check(L.load().bb_bn_forward(C.byref(a), _s(dev)), "bb_bn_forward")
+    return y, mean, invstd
+
+
+def _bn_backward_call(x, dy, nhwc, pre_bias, weight, bias, mean, invstd, relu: int, part=None, y=None):
+    """bb_bn_backward into fresh tensors -> (dx, dweight, dbias, dpre_bias, g).  It carries a board convolution's
+    pending weight-gradient reduction (wgrad_piggyback), if there is one, in its finalisation launch.  part =
+    (partials, blocks): the reduction sums from the convolution that produced dy (bb_bn_bwd.part).  y: the
+    forward's output after a residual add and ReLU; the backward then runs over g = threshold_backward(dy, y),
+    which it writes (g is None without y)."""
+    n, c, h, w = x.shape
+    dev = x.device
+    dx = torch.empty_like(x)
+    dw = torch.empty_like(weight)
+    db = torch.empty_like(bias)
+    dpb = torch.empty_like(pre_bias) if pre_bias is not None else None
+    ws = _bn_workspace(x, nhwc)
+    g = torch.empty_like(x) if y is not None else None
+    a = L.BnBwd(x=_a(x), dy=_a(dy), y=_a(y), dtype=_BN_DTYPES[x.dtype], nhwc=nhwc, N=n, C=c, HW=h * w,
+                pre_bias=_a(pre_bias), weight=_a(weight), bias=_a(bias), save_mean=_a(mean), save_invstd=_a(invstd),
+                relu=int(relu), ws=_a(ws), dx=_a(dx), dweight=_a(dw), dbias=_a(db), dpre_bias=_a(dpb), gres=_a(g))
     job = _take_pending_reduce(dev)
-    args = (_p(x), _p(dy), _BN_DTYPES[x.dtype], nhwc, n, c, h * w, _p(pre_bias), _p(weight), _p(bias), _p(mean),
-            _p(invstd), int(relu), _p(ws), _p(dx), _p(dw), _p(db), _p(dpb))
-    if part is not None:
-        cws, chunks, cin, cout, wl, cdw = job if job is not None else (None, 0, 0, 0, 0, None)
-        L.check(lib.bb_bn_backward_part(*args, _p(cws), chunks, cin, cout, wl, C.c_void_p(cdw), _p(part[0]), part[1],
-                                        _s(dev)), "bb_bn_backward_part")
-    elif job is None:
-        L.check(lib.bb_bn_backward(*args, _s(dev)), "bb_bn_backward")
-    else:
+    if job is not None:
         cws, chunks, cin, cout, wl, cdw = job
-        L.check(lib.bb_bn_backward_red(*args, _p(cws), chunks, cin, cout, wl, C.c_void_p(cdw), _s(dev)),
-                "bb_bn_backward_red")
+        a.reduce = L.WgradReduce(ws=_a(cws), chunks=chunks, cin=cin, cout=cout, w_layout=wl, dw=cdw)
+    if part is not None:
+        a.part, a.nb_part = _a(part[0]), part[1]
+    L.check(L.load().bb_bn_backward(C.byref(a), _s(dev)), "bb_bn_backward")
+    return dx, dw, db, dpb, g
 
 
 class BatchNormReLUFunction(torch.autograd.Function):
@@ -367,21 +396,8 @@ class BatchNormReLUFunction(torch.autograd.Function):
                 num_batches_tracked=None, stats=None, bwd_slot=None):
         nhwc = _bn_layout(x)
         x = x.contiguous(memory_format=torch.channels_last if nhwc else torch.contiguous_format)
-        n, c, h, w = x.shape
-        dev = x.device
-        y = torch.empty_like(x)
-        ws = _bn_workspace(x, nhwc)
-        mean = torch.empty(c, dtype=torch.float32, device=dev)
-        invstd = torch.empty(c, dtype=torch.float32, device=dev)
-        args = (_p(x), _BN_DTYPES[x.dtype], nhwc, n, c, h * w, _p(pre_bias), _p(weight), _p(bias), float(eps),
-                int(relu), _p(ws), _p(mean), _p(invstd), _p(running_mean), _p(running_var), float(momentum),
-                _p(num_batches_tracked), _p(y))
-        st = _stats_for(stats, x)
-        if st is None:
-            L.check(L.load().bb_bn_forward(*args, _s(dev)), "bb_bn_forward")
-        else:  # the statistics came out of the convolution's store pass
-            L.check(L.load().bb_bn_forward_part(args[0], None, *args[1:], _p(st[0]), st[1], _s(dev)),
-                    "bb_bn_forward_part")
+        y, mean, invstd = _bn_forward_call(x, nhwc, pre_bias, weight, bias, running_mean, running_var, momentum, eps,
+                                           relu, num_batches_tracked, stats)
         ctx.save_for_backward(x, pre_bias, weight, bias, mean, invstd)
         ctx.relu = bool(relu)
         ctx.nhwc = nhwc
@@ -396,24 +412,16 @@ class BatchNormReLUFunction(torch.autograd.Function):
         x, pre_bias, weight, bias, mean, invstd = ctx.saved_tensors
         fmt = torch.channels_last if ctx.nhwc else torch.contiguous_format
         dy = dy.to(x.dtype).contiguous(memory_format=fmt)
-        n, c, h, w = x.shape
-        dev = x.device
-        dx = torch.empty_like(x)
-        dw = torch.empty_like(weight)
-        db = torch.empty_like(bias)
-        dpb = torch.empty_like(pre_bias) if pre_bias is not None else None
-        ws = _bn_workspace(x, ctx.nhwc)
         slot = ctx.bwd_slot
         part = _stats_for(slot, dy)
         if slot is not None:
             slot.part, slot.bn = None, None  # used once
-        _bn_backward_call(x, dy, ctx.nhwc, pre_bias, weight, bias, mean, invstd, int(ctx.relu), ws, dx, dw, db, dpb,
-                          dev, part)
+        dx, dw, db, dpb, _ = _bn_backward_call(x, dy, ctx.nhwc, pre_bias, weight, bias, mean, invstd, ctx.relu, part)
         return dx, dpb, dw, db, None, None, None, None, None, None, None, None
 
 
-# ResidualBlock tail backward on bb_bn_backward_res: the ReLU mask applied in the BatchNorm reduction, which
-# writes the masked gradient for the elementwise pass (0: threshold_backward + bb_bn_backward, for A/B).
+# ResidualBlock tail backward on bb_bn_backward with bb_bn_bwd.y: the ReLU mask applied in the BatchNorm reduction,
+# which writes the masked gradient for the elementwise pass (0: threshold_backward + a plain bb_bn_backward, for A/B).
 # 1.575-1.579 against 1.579-1.583 ms per step, three interleaved repeats, 2 launches fewer
 # (profiles/r05/rm/r05rm2_ab.log; the first form, mask applied in both passes, was 1.619 against 1.613)
 RES_MASK = os.environ.get("BB_RES_MASK", "1") != "0"
@@ -422,8 +430,8 @@ RES_MASK = os.environ.get("BB_RES_MASK", "1") != "0"
 class BatchNormAddReLUFunction(torch.autograd.Function):
     """relu(batch_norm(x + pre_bias) + res) with running-stat update: the tail
     of ResidualBlock (network.py:14-30, bn2 -> + identity -> relu) in the
-    BatchNorm apply pass (bb_bn_forward_res) instead of two more elementwise
-    passes.  Backward: bb_bn_backward_res -- the ReLU mask from the saved
+    BatchNorm apply pass (bb_bn_fwd.res) instead of two more elementwise
+    passes.  Backward: bb_bn_bwd.y / gres -- the ReLU mask from the saved
     output (torch's threshold_backward, as F.relu's backward) applied inside
     the BatchNorm passes, the masked gradient (the residual's) written by the
     elementwise pass."""
@@ -436,20 +444,8 @@ class BatchNormAddReLUFunction(torch.autograd.Function):
         fmt = torch.channels_last if nhwc else torch.contiguous_format
         x = x.contiguous(memory_format=fmt)
         res = res.contiguous(memory_format=fmt)
-        n, c, h, w = x.shape
-        dev = x.device
-        y = torch.empty_like(x)
-        ws = _bn_workspace(x, nhwc)
-        mean = torch.empty(c, dtype=torch.float32, device=dev)
-        invstd = torch.empty(c, dtype=torch.float32, device=dev)
-        args = (_p(x), _p(res), _BN_DTYPES[x.dtype], nhwc, n, c, h * w, _p(pre_bias), _p(weight), _p(bias),
-                float(eps), 1, _p(ws), _p(mean), _p(invstd), _p(running_mean), _p(running_var), float(momentum),
-                _p(num_batches_tracked), _p(y))
-        st = _stats_for(stats, x)
-        if st is None:
-            L.check(L.load().bb_bn_forward_res(*args, _s(dev)), "bb_bn_forward_res")
-        else:  # the statistics came out of the convolution's store pass
-            L.check(L.load().bb_bn_forward_part(*args, _p(st[0]), st[1], _s(dev)), "bb_bn_forward_part")
+        y, mean, invstd = _bn_forward_call(x, nhwc, pre_bias, weight, bias, running_mean, running_var, momentum, eps,
+                                           1, num_batches_tracked, stats, res=res)
         ctx.save_for_backward(x, pre_bias, weight, bias, mean, invstd, y)
         ctx.nhwc = nhwc
         return y
@@ -459,26 +455,12 @@ class BatchNormAddReLUFunction(torch.autograd.Function):
         x, pre_bias, weight, bias, mean, invstd, y = ctx.saved_tensors
         fmt = torch.channels_last if ctx.nhwc else torch.contiguous_format
         dy = dy.to(x.dtype).contiguous(memory_format=fmt)
-        n, c, h, w = x.shape
-        dev = x.device
-        dx = torch.empty_like(x)
-        dw = torch.empty_like(weight)
-        db = torch.empty_like(bias)
-        dpb = torch.empty_like(pre_bias) if pre_bias is not None else None
-        ws = _bn_workspace(x, ctx.nhwc)
-        if RES_MASK:  # the ReLU's mask from the saved output inside the BatchNorm passes (threshold_backward)
-            g = torch.empty_like(x)  # the masked gradient: the residual's, and the elementwise pass's input
-            job = _take_pending_reduce(dev)  # a convolution's weight-gradient reduction, carried along
-            red = (None, 0, 0, 0, 0, None) if job is None else job
-            L.check(L.load().bb_bn_backward_res(_p(x), _p(dy), _p(y), _BN_DTYPES[x.dtype], ctx.nhwc, n, c, h * w,
-                                                _p(pre_bias), _p(weight), _p(bias), _p(mean), _p(invstd), _p(ws),
-                                                _p(dx), _p(dw), _p(db), _p(dpb), _p(g), _p(red[0]), red[1], red[2],
-                                                red[3], red[4], None if red[5] is None else C.c_void_p(red[5]),
-                                                _s(dev)),
-                    "bb_bn_backward_res")
+        if RES_MASK:  # the ReLU's mask from the saved output inside the BatchNorm passes (threshold_backward);
+            # g: the masked gradient, the residual's and the elementwise pass's input
+            dx, dw, db, dpb, g = _bn_backward_call(x, dy, ctx.nhwc, pre_bias, weight, bias, mean, invstd, 0, y=y)
         else:
             g = torch.ops.aten.threshold_backward(dy, y, 0).contiguous(memory_format=fmt)
-            _bn_backward_call(x, g, ctx.nhwc, pre_bias, weight, bias, mean, invstd, 0, ws, dx, dw, db, dpb, dev)
+            dx, dw, db, dpb, _ = _bn_backward_call(x, g, ctx.nhwc, pre_bias, weight, bias, mean, invstd, 0)
         gres = g
         if ctx.mailbox is not None and ctx.needs_input_grad[2]:
             ctx.mailbox.put(g)  # the block's first convolution adds it to its data gradient
@@ -561,7 +543,7 @@ def _wgrad_deferred(weight: torch.Tensor, dev: torch.device, saved, compute) -> 
 # Weight-gradient reductions carried by the next BatchNorm backward: inside ``wgrad_piggyback(device)`` a board
 # convolution's backward launches only the weight-gradient partial-sum kernel and leaves its fixed-order reduction
 # pending; the next BatchNorm backward on the device (the one that always follows a convolution in the CNN's
-# backward) runs it as extra workgroups of its finalisation launch (bb_bn_backward_red): two small launches become
+# backward) runs it as extra workgroups of its finalisation launch (bb_bn_bwd.reduce): two small launches become
 # one.  Whatever is still pending when the block closes (or when a second convolution comes first) is reduced in
 # a launch of its own, so every weight gradient is complete at the block's exit -- before clip + Adam or a
 # data-parallel all-reduce reads it.  Only for backward passes with no gradient hooks in between (a hook would see
@@ -913,6 +895,15 @@ def conv3x3_prep_multi(weights, defer: bool = False):
 # ---------------------------------------------------------------------------
 # PPO minibatch loss, forward and backward (csrc/bb_loss.hip)
 # ---------------------------------------------------------------------------
+def _ppo_loss_args(ins, bf16: bool, coef, **outs) -> L.PpoLossArgs:
+    """bb_ppo_loss_args of the seven input tensors, (clip, value_coef, entropy_coef) and the call's own tensors
+    (grad_loss / dlogits / dvalues, ws / cnt / stats / loss) by field name."""
+    logits, values, mask, actions, old_logp, adv, ret = ins
+    return L.PpoLossArgs(logits=_a(logits), values=_a(values), bf16=int(bf16), mask=_a(mask), actions=_a(actions),
+                         old_logp=_a(old_logp), adv=_a(adv), ret=_a(ret), B=logits.shape[0], clip=coef[0],
+                         value_coef=coef[1], entropy_coef=coef[2], **{k: _a(t) for k, t in outs.items()})
+
+
 class PPOLossFunction(torch.autograd.Function):
     """PPOAgent's minibatch loss (ppo.py:362-401) with the masked Categorical
     tail (network.py:173-180, 210-262) on bb_ppo_loss_forward/backward.
@@ -928,7 +919,7 @@ class PPOLossFunction(torch.autograd.Function):
                 value_coef: float, entropy_coef: float, seed: Optional[torch.Tensor] = None):
         _need_cuda(logits, values, masks, actions, old_log_probs, advantages, returns)
         # bf16 logits and values (the autocast network's) are read as they are and get bf16 gradients
-        # (bb_ppo_loss_*_bf16: the values of autograd's casts, without the cast launches)
+        # (bb_ppo_loss_args.bf16: the values of autograd's casts, without the cast launches)
         bf16 = logits.dtype == torch.bfloat16 and values.dtype == torch.bfloat16
         act = torch.bfloat16 if bf16 else torch.float32
         ins = (logits.contiguous().to(act), values.contiguous().to(act), masks.contiguous().float(),
@@ -943,15 +934,14 @@ class PPOLossFunction(torch.autograd.Function):
         loss = torch.empty((), dtype=torch.float32, device=dev)
         coef = (float(clip), float(value_coef), float(entropy_coef))
         ctx.seed, ctx.grads = None, None
+        fwd = dict(ws=ws, cnt=cnt, stats=stats, loss=loss)
         if seed is not None and seed.is_cuda and seed.dtype == torch.float32 and seed.numel() == 1:
             dlogits, dvalues = torch.empty_like(ins[0]), torch.empty_like(ins[1])
-            L.check(lib.bb_ppo_loss_fused(_p(ins[0]), _p(ins[1]), int(bf16), *[_p(t) for t in ins[2:]], b, *coef,
-                                          _p(seed), _p(dlogits), _p(dvalues), _p(ws), _p(cnt), _p(stats), _p(loss),
-                                          _s(dev)), "bb_ppo_loss_fused")
+            a = _ppo_loss_args(ins, bf16, coef, grad_loss=seed, dlogits=dlogits, dvalues=dvalues, **fwd)
+            L.check(lib.bb_ppo_loss_fused(C.byref(a), _s(dev)), "bb_ppo_loss_fused")
             ctx.seed, ctx.grads = seed, (dlogits, dvalues)
         else:
-            fn = lib.bb_ppo_loss_forward_bf16 if bf16 else lib.bb_ppo_loss_forward
-            L.check(fn(*[_p(t) for t in ins], b, *coef, _p(ws), _p(cnt), _p(stats), _p(loss), _s(dev)),
+            L.check(lib.bb_ppo_loss_forward(C.byref(_ppo_loss_args(ins, bf16, coef, **fwd)), _s(dev)),
                     "bb_ppo_loss_forward")
         ctx.save_for_backward(*ins)
         ctx.coef = coef
@@ -969,14 +959,11 @@ class PPOLossFunction(torch.autograd.Function):
             ctx.grads = None
             return dlogits, dvalues, None, None, None, None, None, None, None, None, None
         ins = ctx.saved_tensors
-        b = ins[0].shape[0]
-        dev = ins[0].device
         g = grad_loss.float().reshape(1).contiguous()
         dlogits = torch.empty_like(ins[0])
         dvalues = torch.empty_like(ins[1])
-        fn = L.load().bb_ppo_loss_backward_bf16 if ctx.bf16 else L.load().bb_ppo_loss_backward
-        L.check(fn(*[_p(t) for t in ins], b, *ctx.coef, _p(g), _p(dlogits), _p(dvalues), _s(dev)),
-                "bb_ppo_loss_backward")
+        a = _ppo_loss_args(ins, ctx.bf16, ctx.coef, grad_loss=g, dlogits=dlogits, dvalues=dvalues)
+        L.check(L.load().bb_ppo_loss_backward(C.byref(a), _s(ins[0].device)), "bb_ppo_loss_backward")
         return dlogits, dvalues, None, None, None, None, None, None, None, None, None
 
 

@@ -60,7 +60,7 @@ class Info(C.Structure):
     ]
 
 
-ABI_VERSION = 8  # include/bbvec.h BB_ABI_VERSION
+ABI_VERSION = 9  # include/bbvec.h BB_ABI_VERSION
 INFO_BYTES = C.sizeof(Info)  # 56, matches sizeof(bb_info)
 
 
@@ -146,6 +146,39 @@ _I32 = C.c_int32
 _U64 = C.c_uint64
 _F = C.c_float
 
+
+_BN_SHAPE = [("dtype", _I32), ("nhwc", _I32), ("N", _I32), ("C", _I32), ("HW", _I32)]
+
+
+class BnFwd(C.Structure):
+    """bb_bn_fwd: res, pre_bias, running_mean / _var, num_batches_tracked, part / nb_part are optional (NULL / 0)."""
+    _fields_ = [("x", _P), ("res", _P), *_BN_SHAPE, ("pre_bias", _P), ("weight", _P), ("bias", _P), ("eps", _F),
+                ("relu", _I32), ("ws", _P), ("save_mean", _P), ("save_invstd", _P), ("running_mean", _P),
+                ("running_var", _P), ("momentum", _F), ("num_batches_tracked", _P), ("y", _P), ("part", _P),
+                ("nb_part", _I32)]
+
+
+class WgradReduce(C.Structure):
+    """bb_wgrad_reduce: bb_conv3x3_wgrad_reduce's arguments; ws NULL = no job."""
+    _fields_ = [("ws", _P), ("chunks", _I32), ("cin", _I32), ("cout", _I32), ("w_layout", _I32), ("dw", _P)]
+
+
+class BnBwd(C.Structure):
+    """bb_bn_bwd: y + gres (the ReLU mask of a residual tail), pre_bias, dweight / dbias / dpre_bias, reduce and
+    part / nb_part are optional (NULL / 0)."""
+    _fields_ = [("x", _P), ("dy", _P), ("y", _P), *_BN_SHAPE, ("pre_bias", _P), ("weight", _P), ("bias", _P),
+                ("save_mean", _P), ("save_invstd", _P), ("relu", _I32), ("ws", _P), ("dx", _P), ("dweight", _P),
+                ("dbias", _P), ("dpre_bias", _P), ("gres", _P), ("reduce", WgradReduce), ("part", _P),
+                ("nb_part", _I32)]
+
+
+class PpoLossArgs(C.Structure):
+    """bb_ppo_loss_args: grad_loss / dlogits / dvalues are the backward's, ws / cnt / stats / loss the forward's."""
+    _fields_ = [("logits", _P), ("values", _P), ("bf16", _I32), ("mask", _P), ("actions", _P), ("old_logp", _P),
+                ("adv", _P), ("ret", _P), ("B", _I32), ("clip", _F), ("value_coef", _F), ("entropy_coef", _F),
+                ("grad_loss", _P), ("dlogits", _P), ("dvalues", _P), ("ws", _P), ("cnt", _P), ("stats", _P),
+                ("loss", _P)]
+
 # name -> (restype, argtypes); exactly the entry points of include/bbvec.h
 SIGNATURES = {
     "bb_abi_version": (C.c_int, []),
@@ -178,20 +211,8 @@ SIGNATURES = {
     "bb_gae": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _F, _F, _P, _P, _P]),
     "bb_gather_obs": (C.c_int, [_P, _P, _P, _P, _I32, _P, _P, _P]),
     "bb_bn_workspace_bytes": (C.c_int64, [_I32, _I32, _I32, _I32, _I32]),
-    "bb_bn_forward": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _F, _I32, _P, _P, _P, _P, _P, _F, _P, _P,
-                                _P]),
-    "bb_bn_forward_res": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _F, _I32, _P, _P, _P, _P, _P,
-                                    _F, _P, _P, _P]),
-    "bb_bn_backward_part": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _P,
-                                      _P, _P, _I32, _I32, _I32, _I32, _P, _P, _I32, _P]),
-    "bb_bn_forward_part": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _F, _I32, _P, _P, _P, _P, _P,
-                                     _F, _P, _P, _P, _I32, _P]),
-    "bb_bn_backward": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _P,
-                                 _P]),
-    "bb_bn_backward_red": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _P,
-                                     _P, _I32, _I32, _I32, _I32, _P, _P]),
-    "bb_bn_backward_res": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
-                                     _P, _P, _I32, _I32, _I32, _I32, _P, _P]),
+    "bb_bn_forward": (C.c_int, [C.POINTER(BnFwd), _P]),
+    "bb_bn_backward": (C.c_int, [C.POINTER(BnBwd), _P]),
     "bb_conv3x3_workspace_bytes": (C.c_int64, [_I32, _I32, _I32]),
     "bb_conv3x3_prep": (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _P]),
     "bb_conv3x3_prep_multi": (C.c_int, [_I32, _P, _P, _P, _P, _P, _P, _P]),
@@ -208,11 +229,9 @@ SIGNATURES = {
     "bb_conv3x3_f32_forward": (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P]),
     "bb_linear_f32": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _P, _P]),
     "bb_ppo_loss_workspace_bytes": (C.c_int64, [_I32]),
-    "bb_ppo_loss_forward": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I32, _F, _F, _F, _P, _P, _P, _P, _P]),
-    "bb_ppo_loss_backward": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I32, _F, _F, _F, _P, _P, _P, _P]),
-    "bb_ppo_loss_forward_bf16": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I32, _F, _F, _F, _P, _P, _P, _P, _P]),
-    "bb_ppo_loss_fused": (C.c_int, [_P, _P, _I32, _P, _P, _P, _P, _P, _I32, _F, _F, _F, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "bb_ppo_loss_backward_bf16": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I32, _F, _F, _F, _P, _P, _P, _P]),
+    "bb_ppo_loss_forward": (C.c_int, [C.POINTER(PpoLossArgs), _P]),
+    "bb_ppo_loss_backward": (C.c_int, [C.POINTER(PpoLossArgs), _P]),
+    "bb_ppo_loss_fused": (C.c_int, [C.POINTER(PpoLossArgs), _P]),
     "bb_adam_clip_workspace_bytes": (C.c_int64, [_I32, _P]),
     "bb_adam_clip_step": (C.c_int, [_I32, _P, _P, _P, _P, _P, _P, C.c_double, C.c_double, C.c_double, C.c_double, _F,
                                     _P, _P, _P]),

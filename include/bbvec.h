@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define BB_ABI_VERSION 8  /* 2: bb_step_out.final_score / final_moves; 3: bb_sync, BB_ERR_DEVICE;
+#define BB_ABI_VERSION 9  /* 2: bb_step_out.final_score / final_moves; 3: bb_sync, BB_ERR_DEVICE;
                               4: bb_conv_in_* and bb_relu_bias_grad* removed;
                               5: bb_conv3x3_forward_stats / _stats_parts and bb_bn_forward_parts removed;
                               6: bb_build_id; bb_obs / bb_snapshot report BB_ERR_DEVICE;
@@ -48,7 +48,11 @@ extern "C" {
                                  (additive, still 8) bb_positions / bb_afterstate_out / bb_greedy_weights with
                                  bb_afterstates(_pos) and bb_greedy_actions(_pos): one-ply lookahead
                                  (engine.py:326-346, 390-454; block_blast_env.py:148-193);
-                                 (additive, still 8) bb_plan_out with bb_plan_actions(_pos): full-hand lookahead */
+                                 (additive, still 8) bb_plan_out with bb_plan_actions(_pos): full-hand lookahead;
+                              9: bb_bn_fwd / bb_bn_bwd / bb_wgrad_reduce / bb_ppo_loss_args: bb_bn_forward, bb_bn_backward
+                                 and bb_ppo_loss_forward / _backward / _fused take one argument struct;
+                                 bb_bn_forward_res / _part, bb_bn_backward_red / _part / _res and
+                                 bb_ppo_loss_forward_bf16 / _backward_bf16 removed (fields of the structs) */
 
 #define BB_OK 0
 #define BB_ERR_ARG (-1)
@@ -415,7 +419,7 @@ int bb_gather_obs(const uint64_t* d_board, const uint32_t* d_hand,
  * bias of the preceding convolution, for the policy/value CNN's conv stack
  * (network.py:75-117 conv -> BatchNorm2d -> ReLU, ResidualBlock
  * network.py:14-30).  Input x is the convolution output WITHOUT its bias;
- * d_pre_bias (NULL = none) is that bias, added per channel before the
+ * pre_bias (NULL = none) is that bias, added per channel before the
  * statistics, so the result equals nn.BatchNorm2d(conv(x) + bias).
  * dtype 0 = f32, 1 = bf16 activations; nhwc 0 = NCHW contiguous (HW * element
  * size a multiple of 16 bytes), 1 = NHWC / channels_last contiguous (C *
@@ -423,114 +427,122 @@ int bb_gather_obs(const uint64_t* d_board, const uint32_t* d_hand,
  * statistics are f32.  Forward = nn.BatchNorm2d training forward (batch mean,
  * biased variance for the normalisation; running_mean / running_var updated
  * with `momentum` and the unbiased variance when non-NULL, num_batches_tracked
- * incremented when non-NULL), then max(y, 0) if
- * relu.  d_ws is caller scratch of bb_bn_workspace_bytes(...) bytes (16-byte
- * aligned).  Backward takes the forward's input x and saved mean / inverse
- * std; with relu it recomputes the mask from x.  It writes dx and, where
- * non-NULL, dweight, dbias and d_dpre_bias = sum of dx per channel.  No
- * atomics: results are deterministic. */
+ * incremented when non-NULL), then max(y, 0) if relu.  ws is caller scratch of
+ * bb_bn_workspace_bytes(...) bytes (16-byte aligned).  Backward takes the
+ * forward's input x and saved mean / inverse std; with relu it recomputes the
+ * mask from x.  It writes dx and, where non-NULL, dweight, dbias and
+ * dpre_bias = sum of dx per channel.  Three launches each (two with `part`).
+ * No atomics: results are deterministic.  All pointers are device pointers;
+ * every optional field is "NULL / 0: absent". */
 int64_t bb_bn_workspace_bytes(int32_t dtype, int32_t nhwc, int32_t N, int32_t C, int32_t HW);
-int bb_bn_forward(const void* d_x, int32_t dtype, int32_t nhwc, int32_t N, int32_t C, int32_t HW,
-                  const float* d_pre_bias, const float* d_weight, const float* d_bias, float eps,
-                  int32_t relu, double* d_ws, float* d_save_mean, float* d_save_invstd,
-                  float* d_running_mean, float* d_running_var, float momentum,
-                  int64_t* d_num_batches_tracked, void* d_y, void* stream);
-/* bb_bn_forward with a residual input (ResidualBlock, network.py:14-30:
- * relu(bn2(conv2(.)) + x)): y = [relu](round(BatchNorm(x + pre_bias)) + res),
- * where round is the activation dtype's rounding (the BatchNorm output tensor
- * of the unfused module) and the sum is rounded once, as torch's add.  d_res
- * has x's shape, dtype and layout (16-byte aligned).  The backward is
- * bb_bn_backward_res (dy masked by y > 0, as threshold_backward; the masked dy
- * is also the residual's gradient). */
-int bb_bn_forward_res(const void* d_x, const void* d_res, int32_t dtype, int32_t nhwc, int32_t N,
-                      int32_t C, int32_t HW, const float* d_pre_bias, const float* d_weight,
-                      const float* d_bias, float eps, int32_t relu, double* d_ws, float* d_save_mean,
-                      float* d_save_invstd, float* d_running_mean, float* d_running_var, float momentum,
-                      int64_t* d_num_batches_tracked, void* d_y, void* stream);
-/* bb_bn_forward (d_res NULL) or bb_bn_forward_res from statistics partials a board convolution's forward
- * already produced (bb_conv3x3_forward_stats: d_part [nb_part][C][3] doubles, nb_part =
- * bb_conv3x3_stats_blocks(N, C)) instead of its own reduction pass over x: two launches (ABI 8). */
-int bb_bn_forward_part(const void* d_x, const void* d_res, int32_t dtype, int32_t nhwc, int32_t N, int32_t C,
-                       int32_t HW, const float* d_pre_bias, const float* d_weight, const float* d_bias, float eps,
-                       int32_t relu, double* d_ws, float* d_save_mean, float* d_save_invstd, float* d_running_mean,
-                       float* d_running_var, float momentum, int64_t* d_num_batches_tracked, void* d_y,
-                       const double* d_part, int32_t nb_part, void* stream);
-int bb_bn_backward(const void* d_x, const void* d_dy, int32_t dtype, int32_t nhwc, int32_t N,
-                   int32_t C, int32_t HW, const float* d_pre_bias, const float* d_weight,
-                   const float* d_bias, const float* d_save_mean, const float* d_save_invstd,
-                   int32_t relu, double* d_ws, void* d_dx, float* d_dweight, float* d_dbias,
-                   float* d_dpre_bias, void* stream);
-/* bb_bn_backward with a board convolution's weight-gradient reduction (bb_conv3x3_wgrad_reduce's arguments)
- * run as extra workgroups of the BatchNorm finalisation's launch: two small launches in one (ABI 8). */
-int bb_bn_backward_red(const void* d_x, const void* d_dy, int32_t dtype, int32_t nhwc, int32_t N, int32_t C, int32_t HW,
-                       const float* d_pre_bias, const float* d_weight, const float* d_bias, const float* d_save_mean,
-                       const float* d_save_invstd, int32_t relu, double* d_ws, void* d_dx, float* d_dweight,
-                       float* d_dbias, float* d_dpre_bias, const float* d_conv_ws, int32_t conv_chunks,
-                       int32_t conv_cin, int32_t conv_cout, int32_t conv_w_layout, float* d_conv_dw, void* stream);
-/* bb_bn_backward / _red from reduction partials the board convolution that produced d_dy already made
- * (bb_conv3x3_forward_bstats: d_part [nb_part][C][3] doubles) instead of its own pass over x and dy; d_conv_ws
- * NULL: no carried weight-gradient reduction (ABI 8). */
-int bb_bn_backward_part(const void* d_x, const void* d_dy, int32_t dtype, int32_t nhwc, int32_t N, int32_t C,
-                        int32_t HW, const float* d_pre_bias, const float* d_weight, const float* d_bias,
-                        const float* d_save_mean, const float* d_save_invstd, int32_t relu, double* d_ws, void* d_dx,
-                        float* d_dweight, float* d_dbias, float* d_dpre_bias, const float* d_conv_ws,
-                        int32_t conv_chunks, int32_t conv_cin, int32_t conv_cout, int32_t conv_w_layout,
-                        float* d_conv_dw, const double* d_part, int32_t nb_part, void* stream);
-/* The backward of bb_bn_forward_res with its ReLU: bb_bn_backward (relu = 0) over g = (y > 0 ? dy : 0), y the
- * forward's output (torch's threshold_backward): the reduction pass applies the mask and writes g to d_gres (x's
- * shape, dtype and layout; required), the elementwise pass reads it -- three launches, as bb_bn_backward, and no
- * pass of the mask's own.  g is also the residual's gradient.  d_conv_ws non-NULL: a preceding convolution's
- * weight-gradient reduction rides in the finalisation launch, as in bb_bn_backward_red. */
-int bb_bn_backward_res(const void* d_x, const void* d_dy, const void* d_y, int32_t dtype, int32_t nhwc, int32_t N,
-                       int32_t C, int32_t HW, const float* d_pre_bias, const float* d_weight, const float* d_bias,
-                       const float* d_save_mean, const float* d_save_invstd, double* d_ws, void* d_dx,
-                       float* d_dweight, float* d_dbias, float* d_dpre_bias, void* d_gres, const float* d_conv_ws,
-                       int32_t conv_chunks, int32_t conv_cin, int32_t conv_cout, int32_t conv_w_layout,
-                       float* d_conv_dw, void* stream);
+
+typedef struct bb_bn_fwd {
+  const void* x;            /* [N][C][HW] or [N][HW][C], required                               */
+  const void* res;          /* optional residual (ResidualBlock, network.py:14-30: relu(bn2(conv2(.)) + x)),
+                               x's shape, dtype and layout, 16-byte aligned: y = [relu](round(BatchNorm(x +
+                               pre_bias)) + res), round = the activation dtype's rounding (the BatchNorm output
+                               tensor of the unfused module), the sum rounded once, as torch's add */
+  int32_t dtype, nhwc, N, C, HW;
+  const float* pre_bias;    /* [C] optional                                                     */
+  const float* weight;      /* [C] required                                                     */
+  const float* bias;        /* [C] required                                                     */
+  float eps;
+  int32_t relu;
+  double* ws;               /* required                                                         */
+  float* save_mean;         /* [C] required                                                     */
+  float* save_invstd;       /* [C] required                                                     */
+  float* running_mean;      /* [C] optional                                                     */
+  float* running_var;       /* [C] optional                                                     */
+  float momentum;
+  int64_t* num_batches_tracked; /* optional                                                     */
+  void* y;                  /* x's shape, required                                              */
+  const double* part;       /* optional: statistics partials [nb_part][C][3] a board convolution's forward already
+                               produced (bb_conv3x3_forward_stats, nb_part = bb_conv3x3_stats_blocks(N, C))
+                               instead of a reduction pass over x                               */
+  int32_t nb_part;          /* > 0 with part                                                    */
+} bb_bn_fwd;
+
+/* A board convolution's pending weight-gradient reduction (bb_conv3x3_wgrad_reduce's arguments), run as extra
+ * workgroups of a BatchNorm backward's finalisation launch: two small launches in one.  ws NULL: no job. */
+typedef struct bb_wgrad_reduce {
+  const float* ws;
+  int32_t chunks, cin, cout, w_layout;
+  float* dw;
+} bb_wgrad_reduce;
+
+typedef struct bb_bn_bwd {
+  const void* x;            /* the forward's input, required                                    */
+  const void* dy;           /* x's shape, required                                              */
+  const void* y;            /* optional, with gres: the forward's output, whose ReLU (after a residual add) is
+                               undone here: the backward runs over g = (y > 0 ? dy : 0) (torch's
+                               threshold_backward), which the reduction pass writes to gres and the elementwise
+                               pass reads; g is also the residual's gradient.  relu must be 0; not with part */
+  int32_t dtype, nhwc, N, C, HW;
+  const float* pre_bias;    /* [C] optional                                                     */
+  const float* weight;      /* [C] required                                                     */
+  const float* bias;        /* [C] required                                                     */
+  const float* save_mean;   /* [C] required                                                     */
+  const float* save_invstd; /* [C] required                                                     */
+  int32_t relu;
+  double* ws;               /* required                                                         */
+  void* dx;                 /* x's shape, required                                              */
+  float* dweight;           /* [C] optional                                                     */
+  float* dbias;             /* [C] optional                                                     */
+  float* dpre_bias;         /* [C] optional                                                     */
+  void* gres;               /* x's shape; required with y, absent without                       */
+  bb_wgrad_reduce reduce;   /* optional (reduce.ws NULL: none)                                  */
+  const double* part;       /* optional: reduction partials [nb_part][C][3] the board convolution that produced dy
+                               already made (bb_conv3x3_forward_bstats) instead of a pass over x and dy */
+  int32_t nb_part;          /* > 0 with part                                                    */
+} bb_bn_bwd;
+
+int bb_bn_forward(const bb_bn_fwd* a, void* stream);
+int bb_bn_backward(const bb_bn_bwd* a, void* stream);
 
 /* The PPO minibatch loss (PPOAgent.update, ppo.py:362-401) with the masked
  * Categorical tail (network.py:173-180, 210-262), fused, forward and backward.
- * Per row i < B: logits f32 [B][192] (raw policy head), mask f32 [B][192]
+ * Per row i < B: logits [B][192] (raw policy head), mask f32 [B][192]
  * (non-zero = legal), action, old log-prob, advantage, return and value.
- * Forward writes d_stats[6] = {policy_loss, value_loss, entropy, total_loss,
+ * logits / values and their gradients are f32 (bf16 = 0) or bf16 (1: the
+ * autocast network's outputs, widened exactly on load; the gradients rounded
+ * to nearest even: exactly the values of autograd's casts around the f32 loss,
+ * bit-identical, without the four cast launches).
+ * Forward writes stats[6] = {policy_loss, value_loss, entropy, total_loss,
  * approx_kl, clip_fraction} (the reference's update metrics) and, if non-NULL,
- * d_loss[0] = total_loss, in one launch: d_ws is scratch of
+ * loss[0] = total_loss, in one launch: ws is scratch of
  * bb_ppo_loss_workspace_bytes(B) bytes for the blocks' partial sums, which the
- * last block to finish adds in a fixed order (deterministic); d_cnt is one
- * uint32 counter, zero before the first launch and re-armed by each (ABI 8;
- * one counter per stream).  Backward takes d(total_loss) from d_grad_loss[0]
- * (device memory, so a HIP graph can replay it) and writes d/dlogits [B][192]
- * and d/dvalues [B], following torch autograd's rules for min / clamp / log.
+ * last block to finish adds in a fixed order (deterministic); cnt is one
+ * uint32 counter, zero before the first launch and re-armed by each (one
+ * counter per stream).  Backward takes d(total_loss) from grad_loss[0]
+ * (device memory, so a HIP graph can replay it) and writes dlogits [B][192]
+ * and dvalues [B], following torch autograd's rules for min / clamp / log.
  * bb_ppo_loss_fused is both in one launch (the caller knows the loss gradient
- * before the forward: the root of its backward), f32 (bf16 = 0) or bf16 (1)
- * logits / values and gradients. */
+ * before the forward: the root of its backward). */
 int64_t bb_ppo_loss_workspace_bytes(int32_t B);
-int bb_ppo_loss_forward(const float* d_logits, const float* d_values, const float* d_mask,
-                        const int64_t* d_actions, const float* d_old_logp, const float* d_adv,
-                        const float* d_ret, int32_t B, float clip, float value_coef,
-                        float entropy_coef, double* d_ws, uint32_t* d_cnt, float* d_stats, float* d_loss,
-                        void* stream);
-int bb_ppo_loss_backward(const float* d_logits, const float* d_values, const float* d_mask,
-                         const int64_t* d_actions, const float* d_old_logp, const float* d_adv,
-                         const float* d_ret, int32_t B, float clip, float value_coef,
-                         float entropy_coef, const float* d_grad_loss, float* d_dlogits,
-                         float* d_dvalues, void* stream);
-/* The same loss on bf16 logits [B][192] and values [B] (the autocast network's outputs), widened exactly on
- * load; the backward writes d/dlogits and d/dvalues in bf16, rounded to nearest even: exactly the values of
- * autograd's casts around the f32 loss (bit-identical), without the four cast launches. */
-int bb_ppo_loss_forward_bf16(const void* d_logits, const void* d_values, const float* d_mask,
-                             const int64_t* d_actions, const float* d_old_logp, const float* d_adv,
-                             const float* d_ret, int32_t B, float clip, float value_coef, float entropy_coef,
-                             double* d_ws, uint32_t* d_cnt, float* d_stats, float* d_loss, void* stream);
-int bb_ppo_loss_backward_bf16(const void* d_logits, const void* d_values, const float* d_mask,
-                              const int64_t* d_actions, const float* d_old_logp, const float* d_adv,
-                              const float* d_ret, int32_t B, float clip, float value_coef, float entropy_coef,
-                              const float* d_grad_loss, void* d_dlogits, void* d_dvalues, void* stream);
-int bb_ppo_loss_fused(const void* d_logits, const void* d_values, int32_t bf16, const float* d_mask,
-                      const int64_t* d_actions, const float* d_old_logp, const float* d_adv, const float* d_ret,
-                      int32_t B, float clip, float value_coef, float entropy_coef, const float* d_grad_loss,
-                      void* d_dlogits, void* d_dvalues, double* d_ws, uint32_t* d_cnt, float* d_stats, float* d_loss,
-                      void* stream);
+
+typedef struct bb_ppo_loss_args {
+  const void* logits;       /* [B][192]                                  all: required */
+  const void* values;       /* [B]                                                     */
+  int32_t bf16;
+  const float* mask;        /* [B][192]                                                */
+  const int64_t* actions;   /* [B]                                                     */
+  const float* old_logp;    /* [B]                                                     */
+  const float* adv;         /* [B]                                                     */
+  const float* ret;         /* [B]                                                     */
+  int32_t B;
+  float clip, value_coef, entropy_coef;
+  const float* grad_loss;   /* [1]       backward, fused: required; forward: unused    */
+  void* dlogits;            /* [B][192]  backward, fused: required; forward: unused    */
+  void* dvalues;            /* [B]       backward, fused: required; forward: unused    */
+  double* ws;               /*           forward, fused: required; backward: unused    */
+  uint32_t* cnt;            /* [1]       forward, fused: required; backward: unused    */
+  float* stats;             /* [6]       forward, fused: required; backward: unused    */
+  float* loss;              /* [1]       forward, fused: optional; backward: unused    */
+} bb_ppo_loss_args;
+
+int bb_ppo_loss_forward(const bb_ppo_loss_args* a, void* stream);
+int bb_ppo_loss_backward(const bb_ppo_loss_args* a, void* stream);
+int bb_ppo_loss_fused(const bb_ppo_loss_args* a, void* stream);
 
 /* The CNN's 3x3 / padding-1 convolutions over 8x8 boards (network.py:75-117,
  * ResidualBlock network.py:14-30; nn.Conv2d.forward and its autograd
@@ -565,21 +577,21 @@ int bb_conv3x3_forward_add(const void* d_x, const void* d_w, int32_t N, int32_t 
                            const void* d_add, void* d_y, void* stream);
 /* bb_conv3x3_forward that also writes, from its store pass, the following BatchNorm's batch-statistics
  * partials: per workgroup and output channel the f64 sum and sum of squares of the stored bf16 outputs
- * (d_part [bb_conv3x3_stats_blocks(N, cout)][cout][3], the third 0), for bb_bn_forward_part (ABI 8). */
+ * (d_part [bb_conv3x3_stats_blocks(N, cout)][cout][3], the third 0), for bb_bn_fwd.part (ABI 8). */
 int32_t bb_conv3x3_stats_blocks(int32_t N, int32_t cout);
 int bb_conv3x3_forward_stats(const void* d_x, const void* d_w, int32_t N, int32_t cin, int32_t cout, void* d_y,
                              double* d_part, void* stream);
 /* bb_conv3x3_forward run as a data gradient (y = dL/d(BatchNorm [+ ReLU] output)) that also writes that
  * BatchNorm's backward reduction partials: per workgroup and channel {sum g, sum g xhat, sum xhat}, g = y where
  * the forward's ReLU (relu != 0) passed, xhat = (bn_x - mean) invstd, bn_x the BatchNorm's bf16 NHWC input
- * (y's shape) and mean / invstd / weight / bias its forward's (bb_bn_backward_part; ABI 8). */
+ * (y's shape) and mean / invstd / weight / bias its forward's (bb_bn_bwd.part; ABI 8). */
 int bb_conv3x3_forward_bstats(const void* d_x, const void* d_w, int32_t N, int32_t cin, int32_t cout, void* d_y,
                               const void* d_bn_x, const float* d_mean, const float* d_invstd, const float* d_weight,
                               const float* d_bias, int32_t relu, double* d_part, void* stream);
 int bb_conv3x3_wgrad(const void* d_x, const void* d_dy, int32_t N, int32_t cin, int32_t cout, float* d_ws,
                      int32_t w_layout, float* d_dw, void* stream);
 /* bb_conv3x3_wgrad in two parts (ABI 8): the partial-sum kernel into d_ws, then the fixed-order sum of its
- * bb_conv3x3_wgrad_chunks(N, cin, cout) chunks into d_dw (alone, or inside bb_bn_backward_red); together
+ * bb_conv3x3_wgrad_chunks(N, cin, cout) chunks into d_dw (alone, or as bb_bn_bwd.reduce); together
  * bit-identical to bb_conv3x3_wgrad. */
 int32_t bb_conv3x3_wgrad_chunks(int32_t N, int32_t cin, int32_t cout);
 int bb_conv3x3_wgrad_partial(const void* d_x, const void* d_dy, int32_t N, int32_t cin, int32_t cout, float* d_ws,

@@ -1,7 +1,9 @@
 """The C-ABI library loads (no GPU needed) and exports every symbol that
 include/bbvec.h declares; host-only entry points are exact."""
+import ctypes as C
 import os
 import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -24,7 +26,7 @@ def test_header_and_binding_agree():
 def test_library_exports_every_symbol(lib):
     for name in declared_symbols():
         assert hasattr(lib, name), name
-    assert lib.bb_abi_version() == L.ABI_VERSION == 8
+    assert lib.bb_abi_version() == L.ABI_VERSION == 9
 
 
 def test_build_id_is_these_sources(lib):
@@ -73,8 +75,90 @@ def test_stale_library_is_refused(lib, tmp_path, monkeypatch):
         L.load()
 
 
-def test_struct_sizes(lib):
+ARG_STRUCTS = {"bb_bn_fwd": L.BnFwd, "bb_wgrad_reduce": L.WgradReduce, "bb_bn_bwd": L.BnBwd,
+               "bb_ppo_loss_args": L.PpoLossArgs}
+
+
+def test_struct_sizes(lib, tmp_path):
+    """The argument structs as the C compiler lays them out against the ctypes mirrors: the size, and every
+    field's name and offset (a transposed pointer / int32 pair moves an offset)."""
     assert L.INFO_BYTES == 56
+    src = ["#include <stddef.h>\n#include <stdio.h>\n#include \"bbvec.h\"\nint main(void) {"]
+    want = []
+    for cname, cls in ARG_STRUCTS.items():
+        src.append(f'printf("%zu\\n", sizeof({cname}));')
+        want.append(C.sizeof(cls))
+        for field, _ in cls._fields_:
+            src.append(f'printf("%zu\\n", offsetof({cname}, {field}));')
+            want.append(getattr(cls, field).offset)
+    (tmp_path / "sizes.cpp").write_text("\n".join(src) + "\nreturn 0; }\n")
+    exe = str(tmp_path / "sizes")
+    subprocess.run([os.environ.get("CXX", "g++"), "-std=c++17", "-I", os.path.dirname(HEADER),  # the host library's compiler
+                    str(tmp_path / "sizes.cpp"), "-o", exe], check=True)
+    got = [int(v) for v in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split()]
+    assert got == want
+
+
+FAKE = 0x10000  # a host integer standing for a 16-byte aligned device pointer: validation never dereferences it
+
+
+def _bn_fwd(**kw):
+    a = dict(x=FAKE, dtype=1, nhwc=1, N=2, C=64, HW=64, weight=FAKE, bias=FAKE, eps=1e-5, relu=1, ws=FAKE,
+             save_mean=FAKE, save_invstd=FAKE, y=FAKE)
+    return L.BnFwd(**{**a, **kw})
+
+
+def _bn_bwd(**kw):
+    a = dict(x=FAKE, dy=FAKE, dtype=1, nhwc=1, N=2, C=64, HW=64, weight=FAKE, bias=FAKE, save_mean=FAKE,
+             save_invstd=FAKE, relu=0, ws=FAKE, dx=FAKE)
+    return L.BnBwd(**{**a, **kw})
+
+
+def _loss(**kw):
+    a = {k: FAKE for k, _ in L.PpoLossArgs._fields_ if k not in ("bf16", "B", "clip", "value_coef", "entropy_coef")}
+    return L.PpoLossArgs(**{**a, "B": 4, "clip": 0.2, "value_coef": 0.5, "entropy_coef": 0.01, **kw})
+
+
+_RED =dict(ws=FAKE, chunks=4, cin=64, cout=128, w_layout=0, dw=FAKE)
+_SHAPE = [(dict(dtype=2), "dtype"), (dict(nhwc=2), "layout"), (dict(N=0), "empty"),
+          (dict(nhwc=0, HW=4), "16-byte"),  # NCHW bf16 rows of 8 bytes
+          (dict(C=24), "power of two")]     # NHWC bf16 rows of 48 bytes
+BAD_ARGS = (
+    [("bb_bn_forward", None, "NULL")]
+    + [("bb_bn_forward", _bn_fwd(**kw), msg) for kw, msg in _SHAPE]
+    + [("bb_bn_forward", _bn_fwd(**{k: None}), "NULL argument")
+       for k in ("x", "weight", "bias", "ws", "save_mean", "save_invstd", "y")]
+    + [("bb_bn_forward", _bn_fwd(ws=FAKE + 8), "ws must be 16-byte aligned"),
+       ("bb_bn_forward", _bn_fwd(res=FAKE + 8), "res must be 16-byte aligned"),
+       ("bb_bn_forward", _bn_fwd(part=FAKE, nb_part=0), "nb_part"),
+       ("bb_bn_backward", None, "NULL")]
+    + [("bb_bn_backward", _bn_bwd(**kw), msg) for kw, msg in _SHAPE]
+    + [("bb_bn_backward", _bn_bwd(**{k: None}), "NULL argument")
+       for k in ("x", "dy", "weight", "bias", "save_mean", "save_invstd", "ws", "dx")]
+    + [("bb_bn_backward", _bn_bwd(ws=FAKE + 8), "ws must be 16-byte aligned"),
+       ("bb_bn_backward", _bn_bwd(part=FAKE, nb_part=0), "nb_part"),
+       ("bb_bn_backward", _bn_bwd(y=FAKE), "y and gres"),
+       ("bb_bn_backward", _bn_bwd(gres=FAKE), "y and gres"),
+       ("bb_bn_backward", _bn_bwd(y=FAKE, gres=FAKE, part=FAKE, nb_part=2), "no part"),
+       ("bb_bn_backward", _bn_bwd(y=FAKE, gres=FAKE, relu=1), "relu = 0")]
+    + [("bb_bn_backward", _bn_bwd(reduce=L.WgradReduce(**{**_RED, **kw})), "convolution reduction")
+       for kw in (dict(cin=3), dict(cout=96), dict(dw=None), dict(chunks=0), dict(w_layout=2))]
+    + [(fn, None, "bad arguments") for fn in ("bb_ppo_loss_forward", "bb_ppo_loss_backward", "bb_ppo_loss_fused")]
+    + [(fn, _loss(B=0), "bad arguments") for fn in ("bb_ppo_loss_forward", "bb_ppo_loss_backward", "bb_ppo_loss_fused")]
+    + [(fn, _loss(**{k: None}), "bad arguments")
+       for fn, ks in (("bb_ppo_loss_forward", "logits values mask actions old_logp adv ret ws cnt stats"),
+                      ("bb_ppo_loss_backward", "logits values mask actions old_logp adv ret grad_loss dlogits dvalues"),
+                      ("bb_ppo_loss_fused", "logits values mask actions old_logp adv ret grad_loss dlogits dvalues "
+                                            "ws cnt stats"))
+       for k in ks.split()])
+
+
+@pytest.mark.parametrize("fn,args,msg", BAD_ARGS, ids=[f"{i}-{c[0]}-{c[2]}" for i, c in enumerate(BAD_ARGS)])
+def test_argument_structs_are_validated_before_any_hip_call(lib, fn, args, msg):
+    """Every rule of bb_bn_fwd / bb_bn_bwd / bb_wgrad_reduce / bb_ppo_loss_args is checked before the first HIP
+    call, so it shows without a GPU: BB_ERR_ARG, and bb_last_error(NULL) names the rule."""
+    assert getattr(lib, fn)(C.byref(args) if args is not None else None, None) == -1  # BB_ERR_ARG
+    assert msg in L.last_error()
 
 
 @pytest.mark.parametrize("seed", [0, 1, 42, 43, 2 ** 32 - 1, 2 ** 32, 2 ** 40 + 7, 2 ** 63, 2 ** 64 - 1])

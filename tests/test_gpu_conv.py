@@ -305,7 +305,7 @@ def test_network_conv_in_equals_miopen(cuda, monkeypatch):
 
 def test_wgrad_piggyback_equals_plain(cuda, monkeypatch):
     """The board convolutions' weight-gradient reductions carried by the next BatchNorm backward's finalisation
-    launch (wgrad_piggyback, bb_bn_backward_red) == the plain two-launch weight gradient, bit for bit: the whole
+    launch (wgrad_piggyback, bb_bn_bwd.reduce) == the plain two-launch weight gradient, bit for bit: the whole
     bf16 CNN's parameter gradients and the BatchNorm outputs; a pending reduction with no BatchNorm after it is
     flushed when the block closes."""
     import models.network as N
@@ -372,8 +372,8 @@ def test_conv3x3_forward_stats(cuda, lib, cin, cout, n):
 
 @pytest.mark.parametrize("res", [False, True])
 def test_bn_forward_from_conv_stats(cuda, lib, res):
-    """BatchNorm forward from the convolution's partials (bb_bn_forward_part) == its own reduction
-    (bb_bn_forward / _res): saved mean and inverse std within f64-vs-f32 summation noise, outputs within one
+    """BatchNorm forward from the convolution's partials (bb_bn_fwd.part) == its own reduction
+    (bb_bn_forward, with and without bb_bn_fwd.res): saved mean and inverse std within f64-vs-f32 summation noise, outputs within one
     bf16 step (an element may round the other way), running statistics and num_batches_tracked alike."""
     from runtime import kernels as K
 

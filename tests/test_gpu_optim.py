@@ -1,4 +1,4 @@
-"""GPU parity of the minibatch-step fusions (csrc/bb_optim.hip, bb_bn_forward_res), through the C-ABI.
+"""GPU parity of the minibatch-step fusions (csrc/bb_optim.hip, bb_bn_fwd.res), through the C-ABI.
 
 bb_adam_clip_step vs torch's own nn.utils.clip_grad_norm_ + torch.optim.Adam
 (fp32, the reference's ppo.py:400-401): parameters, moments and clipped
@@ -214,7 +214,7 @@ def test_network_fused_casts_equal_autocast(cuda, monkeypatch):
 def test_bn_add_relu_equals_composite(cuda, dtype, nhwc, res_mask, monkeypatch):
     """BatchNormAddReLUFunction == BatchNormReLUFunction(relu=False) -> + res ->
     relu, forward, running statistics and every gradient, bit for bit; the backward both ways
-    (threshold_backward + bb_bn_backward, and bb_bn_backward_res with the mask inside the passes)."""
+    (threshold_backward + bb_bn_backward, and bb_bn_backward with bb_bn_bwd.y: the mask inside the passes)."""
     from runtime import kernels as K
 
     monkeypatch.setattr(K, "RES_MASK", res_mask)

@@ -285,7 +285,7 @@ def test_fused_ppo_loss_matches_torch(cuda, density):
 
 @pytest.mark.parametrize("density", [0.02, 0.3])
 def test_fused_ppo_loss_bf16_inputs_equal_cast_path(cuda, density):
-    """bb_ppo_loss_*_bf16 (bf16 logits / values, as the autocast network outputs them) == the fp32 loss on the same
+    """bb_ppo_loss_* with bb_ppo_loss_args.bf16 (bf16 logits / values, as the autocast network outputs them) == the fp32 loss on the same
     values widened, then its gradients cast to bf16 (autograd's casts around the fp32 loss): the loss and the
     metrics bit for bit, d/dlogits and d/dvalues bit for bit."""
     from agents.ppo import PPOConfig
