@@ -44,6 +44,15 @@ def _position_of(observation: Dict[str, Any]):
     return bits, hand
 
 
+def apply_safe_mask(env_batch, mask_bits: torch.Tensor, safe_bits: torch.Tensor) -> torch.Tensor:
+    """AND the hand-safe mask of a ``DeviceEnvBatch`` (``safe_mask``, written to safe_bits) into its legal mask
+    words mask_bits (int64 [N, 3] each), in place; an env without a safe action keeps its legal mask.  No sync."""
+    env_batch.safe_mask(safe_bits)
+    has_safe = (safe_bits != 0).any(dim=1, keepdim=True)
+    mask_bits.copy_(torch.where(has_safe, mask_bits & safe_bits, mask_bits))
+    return mask_bits
+
+
 class GreedyAgent(BaseAgent):
     """Plays the legal action with the largest one-ply greedy value (ties: the lowest action)."""
 
@@ -127,21 +136,28 @@ class HandPlanAgent(GreedyAgent):
 
 class RandomAgent(BaseAgent):
     """Uniform random legal play: the Philox policy of ``bb_random_actions`` (bb_step_out.next_action), keyed
-    by ``seed`` and counting one step per call."""
+    by ``seed`` and counting one step per call.  ``safe=True`` (``act_env`` only) draws from the hand-safe actions
+    of ``bb_plan_values`` instead -- the legal moves after which the rest of the hand still fits in some order -- and
+    from the legal ones where no move is safe: such a player never loses in the middle of a hand."""
 
-    def __init__(self, seed: int = 0xB10C, device=None):
+    def __init__(self, seed: int = 0xB10C, device=None, safe: bool = False):
         from runtime.device_env import resolve_device
 
         super().__init__(resolve_device(device))
         self.seed = int(seed)
         self.step = 0
+        self.safe = bool(safe)
         self._mask_bits = None
+        self._safe_bits = None
 
     def act_env(self, env_batch, out: torch.Tensor) -> torch.Tensor:
         n = env_batch.num_envs
         if self._mask_bits is None or self._mask_bits.shape[0] != n or self._mask_bits.device != env_batch.device:
             self._mask_bits = torch.zeros((n, 3), dtype=torch.int64, device=env_batch.device)
+            self._safe_bits = torch.zeros_like(self._mask_bits)
         env_batch.obs(mask_bits=self._mask_bits)
+        if self.safe:
+            apply_safe_mask(env_batch, self._mask_bits, self._safe_bits)
         env_batch.random_actions(self._mask_bits, out, seed=self.seed, step=self.step)
         self.step += 1
         return out

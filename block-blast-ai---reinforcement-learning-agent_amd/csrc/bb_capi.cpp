@@ -636,6 +636,41 @@ int bb_plan_actions(bb_env* env, const bb_greedy_weights* w, int32_t depth, cons
   return BB_OK;
 }
 
+// Per-action full-hand values (plan_values_kernel in csrc/bb_lookahead.hip).  The rule an argument set breaks,
+// or NULL: checked before any HIP call.
+static const char* plan_values_rule(const bb_greedy_weights* w, int32_t depth, const bb_plan_values_out* out) {
+  if (!w) return "weights are NULL";
+  if (!out) return "out is NULL";
+  if (!out->q && !out->rest && !out->leaves && !out->safe) return "all four outputs are NULL";
+  if (depth < 1 || depth > 3) return "depth must be 1..3";
+  return nullptr;
+}
+
+int bb_plan_values_pos(const bb_positions* pos, int32_t n, const bb_greedy_weights* w, int32_t depth,
+                       const bb_plan_values_out* out, void* stream) {
+  const char* rule = !pos || !pos->board || !pos->hand ? "positions (board, hand) are NULL"
+                     : n < 0                           ? "n is negative"
+                                                       : plan_values_rule(w, depth, out);
+  if (rule) return fail(nullptr, BB_ERR_ARG, std::string("bb_plan_values_pos: ") + rule);
+  if (n == 0) return BB_OK;
+  hipError_t st = launch_plan_values(pos->board, pos->hand, pos->combo, n, *w, depth, *out, (hipStream_t)stream);
+  if (st != hipSuccess) return fail(nullptr, BB_ERR_HIP, std::string("bb_plan_values_pos: ") + hipGetErrorString(st));
+  return BB_OK;
+}
+
+int bb_plan_values(bb_env* env, const bb_greedy_weights* w, int32_t depth, const bb_plan_values_out* out, void* stream) {
+  if (!env) return BB_ERR_ARG;
+  if (const char* rule = plan_values_rule(w, depth, out))
+    return fail(env, BB_ERR_ARG, std::string("bb_plan_values: ") + rule);
+  if (status_fail(env, "bb_plan_values") != BB_OK) return BB_ERR_DEVICE;
+  if (env->broken) return broken_fail(env, "bb_plan_values");
+  DeviceGuard g(env->device);
+  hipError_t st =
+      launch_plan_values(env->d.board, env->d.hand, env->d.combo, env->n, *w, depth, *out, (hipStream_t)stream);
+  if (st != hipSuccess) return hip_fail(env, st, "bb_plan_values");
+  return BB_OK;
+}
+
 int bb_masked_sample(const float* d_logits, const uint64_t* d_mask_bits, int32_t n, const float* d_uniform,
                      uint64_t seed, uint64_t step, uint64_t env_offset, int32_t deterministic,
                      const int64_t* d_action_in, int64_t* d_action, float* d_logp, float* d_entropy,

@@ -103,6 +103,9 @@ hipError_t launch_greedy(const uint64_t* board, const uint32_t* hand, const int3
 // full-hand lookahead (bb_lookahead.hip): depth 1..3, out.action required
 hipError_t launch_plan(const uint64_t* board, const uint32_t* hand, const int32_t* combo, int n,
                        const bb_greedy_weights& w, int depth, const bb_plan_out& out, hipStream_t s);
+// the same search per first move (bb_lookahead.hip): depth 1..3, n > 0, at least one output
+hipError_t launch_plan_values(const uint64_t* board, const uint32_t* hand, const int32_t* combo, int n,
+                              const bb_greedy_weights& w, int depth, const bb_plan_values_out& out, hipStream_t s);
 hipError_t launch_masked_sample(const float* logits, const uint64_t* mbits, int n, const float* uniform,
                                 uint64_t seed, uint64_t step, const uint64_t* d_step, uint64_t offset,
                                 int deterministic, const int64_t* action_in, int64_t* action, float* logp,

@@ -384,6 +384,7 @@ struct PlanBest {
   int64_t value;
   int32_t plan[3];
   int32_t leaves;
+  bool alive;  // a maximal sequence ended in an afterstate that is not dead (bb_plan_values' safe)
 };
 
 void plan_dfs(uint64_t B, uint32_t hand, int combo, int depth, int ply, int64_t sum, int32_t* seq,
@@ -399,6 +400,7 @@ void plan_dfs(uint64_t B, uint32_t hand, int combo, int depth, int ply, int64_t 
       seq[ply] = act;
       if (depth == 1 || a.refill || a.dead) {
         const int64_t v = s + state_terms(w, a);
+        best.alive |= !a.dead;
         if (best.leaves++ == 0 || v > best.value) {
           best.value = v;
           for (int k = 0; k < 3; ++k) best.plan[k] = k <= ply ? seq[k] : -1;
@@ -414,7 +416,7 @@ void plan_host(const uint64_t* board, const uint32_t* hand, const int32_t* combo
                const bb_greedy_weights& w, int depth, const bb_plan_out& out) {
 #pragma omp parallel for schedule(dynamic, 1)  // the trees differ by orders of magnitude
   for (int32_t i = 0; i < n; ++i) {
-    PlanBest best{INT64_MIN, {-1, -1, -1}, 0};
+    PlanBest best{INT64_MIN, {-1, -1, -1}, 0, false};
     int32_t seq[3];
     plan_dfs(board[i], hand[i], combo ? combo[i] : 0, depth, 0, 0, seq, w, best);
     out.action[i] = best.leaves ? best.plan[0] : 0;
@@ -422,6 +424,36 @@ void plan_host(const uint64_t* board, const uint32_t* hand, const int32_t* combo
     if (out.plan)
       for (int k = 0; k < 3; ++k) out.plan[3 * (size_t)i + k] = best.plan[k];
     if (out.leaves) out.leaves[i] = best.leaves;
+  }
+}
+
+// bbvec.h bb_plan_values (the host twin of plan_values_kernel): the same DFS, started below each first move
+void plan_values_host(const uint64_t* board, const uint32_t* hand, const int32_t* combo, int32_t n,
+                      const bb_greedy_weights& w, int depth, const bb_plan_values_out& out) {
+  if (depth == 3 && !out.q && !out.rest && !out.leaves) depth = 2;  // the same safe set (bbvec.h)
+#pragma omp parallel for schedule(dynamic, 1)
+  for (int32_t i = 0; i < n; ++i) {
+    const int cb = combo ? combo[i] : 0;
+    uint64_t safe[3] = {0, 0, 0};
+    for (int act = 0; act < 192; ++act) {
+      const After a = eval_action(board[i], hand[i], cb, act);
+      PlanBest best{INT64_MIN, {-1, -1, -1}, 0, false};
+      if (a.legal) {
+        int32_t seq[3] = {act, -1, -1};
+        if (depth == 1 || a.refill || a.dead) {
+          best = PlanBest{move_terms(w, a) + state_terms(w, a), {act, -1, -1}, 1, !a.dead};
+        } else {
+          plan_dfs(a.board, hand_use(hand[i], act >> 6), a.combo1, depth - 1, 1, move_terms(w, a), seq, w, best);
+        }
+      }
+      const size_t o = (size_t)i * 192 + (size_t)act;
+      if (out.q) out.q[o] = best.value;
+      if (out.rest) out.rest[o] = a.legal ? (best.plan[1] & 0xFF) | ((best.plan[2] & 0xFF) << 8) : -1;
+      if (out.leaves) out.leaves[o] = best.leaves;
+      if (best.alive) safe[act >> 6] |= 1ull << (act & 63);
+    }
+    if (out.safe)
+      for (int p = 0; p < 3; ++p) out.safe[3 * (size_t)i + p] = safe[p];
   }
 }
 
@@ -720,6 +752,35 @@ int bb_plan_actions(bb_env* env, const bb_greedy_weights* w, int32_t depth, cons
   if (!w || !out || !out->action || depth < 1 || depth > 3)
     return fail(env, BB_ERR_ARG, "bb_plan_actions: weights, depth in 1..3 and out->action are required");
   plan_host(env->board.data(), env->hand.data(), env->combo.data(), env->n, *w, depth, *out);
+  return BB_OK;
+}
+
+// the rule an argument set breaks, or NULL (the rules of csrc/bb_capi.cpp)
+static const char* plan_values_rule(const bb_greedy_weights* w, int32_t depth, const bb_plan_values_out* out) {
+  if (!w) return "weights are NULL";
+  if (!out) return "out is NULL";
+  if (!out->q && !out->rest && !out->leaves && !out->safe) return "all four outputs are NULL";
+  if (depth < 1 || depth > 3) return "depth must be 1..3";
+  return nullptr;
+}
+
+int bb_plan_values_pos(const bb_positions* pos, int32_t n, const bb_greedy_weights* w, int32_t depth,
+                       const bb_plan_values_out* out, void* stream) {
+  (void)stream;
+  const char* rule = !pos || !pos->board || !pos->hand ? "positions (board, hand) are NULL"
+                     : n < 0                           ? "n is negative"
+                                                       : plan_values_rule(w, depth, out);
+  if (rule) return fail(nullptr, BB_ERR_ARG, std::string("bb_plan_values_pos: ") + rule);
+  plan_values_host(pos->board, pos->hand, pos->combo, n, *w, depth, *out);
+  return BB_OK;
+}
+
+int bb_plan_values(bb_env* env, const bb_greedy_weights* w, int32_t depth, const bb_plan_values_out* out, void* stream) {
+  (void)stream;
+  if (!env) return BB_ERR_ARG;
+  if (const char* rule = plan_values_rule(w, depth, out))
+    return fail(env, BB_ERR_ARG, std::string("bb_plan_values: ") + rule);
+  plan_values_host(env->board.data(), env->hand.data(), env->combo.data(), env->n, *w, depth, *out);
   return BB_OK;
 }
 

@@ -292,6 +292,134 @@ plan_kernel(LookTable t, LookPos pos, int n, bb_greedy_weights w, int depth, bb_
   }
 }
 
+// ---------------------------------------------------------------------------
+// Per-action full-hand values (bbvec.h bb_plan_values): plan_kernel's search with the maximum kept per first move.
+//
+// Same layout as plan_kernel: one workgroup of four waves per position, ply 1 compacted into the LDS record
+// list, one record per wave and turn at ply 2, the per-lane loop at ply 3.  A record is one first move, so the
+// best (value, key16 = a2 << 8 | a3), the leaf count and "some leaf is not dead" start fresh with every record
+// and are joined across the wave (shuffles, one ballot) at the end of the record's turn.  Results are staged in
+// LDS arrays indexed by action: a ply-1 lane fills its own action's entry when the action is illegal or ends its
+// sequence there, lane 0 of the owning wave fills an open record's.  After one barrier threads 0..191 store the
+// rows, 64 consecutive elements per wave and output, and waves 0..2 make the three safe words by ballot.
+//
+// Unlike plan_kernel this one needs a barrier at the end of a position: the next position's ply-1 lanes write
+// the staging arrays as their first act, while slower waves may still be reading them for the stores.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kRestNone = 0xFFFFu;  // rest of a sequence that ends at ply 1
+
+__global__ void __launch_bounds__(kPlanBlock)
+plan_values_kernel(LookTable t, LookPos pos, int n, bb_greedy_weights w, int depth, bb_plan_values_out out) {
+  __shared__ PlanRecord s_rec[kPlanRecords];
+  __shared__ int s_cnt[kHand];
+  __shared__ int64_t s_q[BB_ACTIONS];
+  __shared__ int32_t s_rest[BB_ACTIONS];
+  __shared__ int32_t s_leaves[BB_ACTIONS];
+  __shared__ uint8_t s_safe[BB_ACTIONS];
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int cell = (int)(threadIdx.x & 63u);
+  for (int64_t i = blockIdx.x; i < (int64_t)n; i += gridDim.x) {
+    const uint64_t B = uniform64(pos.board[i]);
+    const uint32_t hand = uniform32(pos.hand[i]);
+    const int combo = (int)uniform32(pos.combo ? (uint32_t)pos.combo[i] : 0u);
+
+    // ---- ply 1: threadIdx.x is the action of waves 0..2
+    bool open1 = false;  // legal and not the end of its sequence
+    After a1;
+    if (wave < kHand) {
+      a1 = eval_action(t, B, hand, combo, wave, cell);
+      const bool end1 = depth == 1 || a1.refill || a1.dead;
+      open1 = a1.legal && !end1;
+      if (!open1) {  // illegal, or a sequence of one move
+        s_q[threadIdx.x] = a1.legal ? move_terms(w, a1) + state_terms(w, a1) : INT64_MIN;
+        s_rest[threadIdx.x] = a1.legal ? (int32_t)kRestNone : -1;
+        s_leaves[threadIdx.x] = a1.legal ? 1 : 0;
+        s_safe[threadIdx.x] = (uint8_t)(a1.legal && !a1.dead);
+      }
+    }
+    const uint64_t open1_mask = __ballot(open1);
+    if (wave < kHand && cell == 0) s_cnt[wave] = __popcll(open1_mask);
+    __syncthreads();
+    const int c0 = s_cnt[0], c1 = s_cnt[1], c2 = s_cnt[2];
+    const int total = __builtin_amdgcn_readfirstlane(c0 + c1 + c2);  // <= 192
+    if (open1) {
+      const int before = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(open1_mask >> 32),
+                                                        __builtin_amdgcn_mbcnt_lo((uint32_t)open1_mask, 0u));
+      const int slot = (wave > 0 ? c0 : 0) + (wave > 1 ? c1 : 0) + before;  // < total <= kPlanRecords
+      s_rec[slot] = PlanRecord{a1.board, move_terms(w, a1), a1.combo1, wave * 64 + cell};
+    }
+    __syncthreads();
+
+    // ---- ply 2 (and 3): one record = one first move per wave and turn
+    for (int r = wave; r < total; r += kPlanWaves) {
+      const uint64_t B1 = uniform64(s_rec[r].board);
+      const int64_t sum1 = (int64_t)uniform64((uint64_t)s_rec[r].sum);
+      const int combo1 = (int)uniform32((uint32_t)s_rec[r].combo);
+      const int act1 = (int)uniform32((uint32_t)s_rec[r].action);  // < 192: an index of the staging arrays
+      const uint32_t hand1 = hand_use(hand, act1 >> 6);
+      int64_t best = INT64_MIN;  // below every legal value (see greedy_kernel)
+      uint32_t best_key = kPlanNoKey;
+      int leaves = 0;
+      bool alive = false;  // a leaf with dead == 0
+#pragma unroll 1
+      for (int q = 0; q < kHand; ++q) {
+        if ((hand_used(hand1) >> q) & 1u) continue;  // wave-uniform
+        const After a2 = eval_action(t, B1, hand1, combo1, q, cell);
+        const bool end2 = depth == 2 || a2.refill || a2.dead;
+        const int64_t sum2 = sum1 + move_terms(w, a2);
+        const uint32_t key2 = (uint32_t)(q * 64 + cell) << 8;
+        if (a2.legal && end2) {
+          take_plan(best, best_key, sum2 + state_terms(w, a2), key2 | 0xFFu);
+          ++leaves;
+          alive |= !a2.dead;
+        }
+        // ply 3, as in plan_kernel: the last piece fits somewhere and placing it is a refill, never dead
+        if (a2.legal && !end2) {
+          const uint32_t hand2 = hand_use(hand1, q);
+          const int q3 = __ffs((int)(~hand_used(hand2) & 7u)) - 1;  // wave-uniform; >= 0 here
+          const uint32_t id3 = hand_id(hand2, q3);
+          uint64_t m3 = anchors_of(t.row[id3 < (uint32_t)kPieces ? id3 : 0u], a2.board);  // != 0: not dead
+          alive = true;
+          for (int it = 0; it < 64 && m3 != 0ull; ++it) {
+            const int c3 = __ffsll((unsigned long long)m3) - 1;
+            m3 &= m3 - 1ull;
+            const After a3 = eval_action(t, a2.board, hand2, a2.combo1, q3, c3);  // legal by construction
+            take_plan(best, best_key, sum2 + move_terms(w, a3) + state_terms(w, a3), key2 | (uint32_t)(q3 * 64 + c3));
+            ++leaves;
+          }
+        }
+      }
+      // the record's turn ends: join the lanes (the whole wave is here, the loops above are wave-uniform)
+#pragma unroll
+      for (int d = 32; d >= 1; d >>= 1) {
+        const int64_t v2 = __shfl_xor(best, d, 64);
+        const uint32_t k2 = (uint32_t)__shfl_xor((int)best_key, d, 64);
+        take_plan(best, best_key, v2, k2);
+        leaves += __shfl_xor(leaves, d, 64);
+      }
+      const bool any_alive = __ballot(alive) != 0ull;
+      if (cell == 0) {  // an open record has a leaf: its afterstate is not dead
+        s_q[act1] = best;
+        s_rest[act1] = (int32_t)(((best_key >> 8) & 0xFFu) | ((best_key & 0xFFu) << 8));
+        s_leaves[act1] = leaves;
+        s_safe[act1] = (uint8_t)any_alive;
+      }
+    }
+    __syncthreads();
+
+    // ---- store the rows: thread = action
+    if (wave < kHand) {
+      const int64_t o = i * BB_ACTIONS + (int64_t)threadIdx.x;
+      if (out.q) out.q[o] = s_q[threadIdx.x];
+      if (out.rest) out.rest[o] = s_rest[threadIdx.x];
+      if (out.leaves) out.leaves[o] = s_leaves[threadIdx.x];
+      const uint64_t safe = __ballot(s_safe[threadIdx.x] != 0);
+      if (out.safe && cell == 0) out.safe[i * kHand + wave] = safe;
+    }
+    __syncthreads();  // the staging arrays are rewritten by the first lanes to reach the workgroup's next position
+  }
+}
+
 const LookTable& look_table() {
   static const LookTable t = [] {
     LookTable x;
@@ -326,6 +454,16 @@ hipError_t launch_plan(const uint64_t* board, const uint32_t* hand, const int32_
   const LookPos pos{board, hand, combo, nullptr};
   const dim3 grid((unsigned)((int64_t)n < kPlanMaxGrid ? (int64_t)n : kPlanMaxGrid));
   hipLaunchKernelGGL(plan_kernel, grid, dim3(kPlanBlock), 0, s, look_table(), pos, n, w, depth, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_plan_values(const uint64_t* board, const uint32_t* hand, const int32_t* combo, int n,
+                              const bb_greedy_weights& w, int depth, const bb_plan_values_out& out, hipStream_t s) {
+  const LookPos pos{board, hand, combo, nullptr};
+  const dim3 grid((unsigned)((int64_t)n < kPlanMaxGrid ? (int64_t)n : kPlanMaxGrid));
+  // the safe set of depth 3 is that of depth 2 (bbvec.h): asked for alone, the third ply is not searched
+  if (depth == 3 && !out.q && !out.rest && !out.leaves) depth = 2;
+  hipLaunchKernelGGL(plan_values_kernel, grid, dim3(kPlanBlock), 0, s, look_table(), pos, n, w, depth, out);
   return hipGetLastError();
 }
 

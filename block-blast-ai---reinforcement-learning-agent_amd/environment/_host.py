@@ -93,6 +93,16 @@ def afterstates_dict(out: dict) -> dict:
     return res
 
 
+def plan_values_dict(out: dict) -> dict:
+    """Device outputs of bb_plan_values -> numpy arrays of shape (N, 192): q i64 (INT64_MIN: illegal), a2 / a3 i32
+    (the rest of the best sequence, -1 for a ply not played or an illegal action), leaves i32, safe bool."""
+    from runtime.kernels import mask_bits_to_bool, unpack_rest
+
+    a2, a3 = unpack_rest(out["rest"].cpu().numpy())
+    return {"q": out["q"].cpu().numpy(), "a2": a2.astype(np.int32), "a3": a3.astype(np.int32),
+            "leaves": out["leaves"].cpu().numpy(), "safe": mask_bits_to_bool(out["safe"].cpu().numpy())}
+
+
 def reset_info() -> dict:
     """Info right after a reset (empty board, zero counters)."""
     return {

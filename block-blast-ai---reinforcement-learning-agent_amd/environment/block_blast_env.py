@@ -115,6 +115,20 @@ class BlockBlastEnv(Env):
         mobility.  The state and the piece stream are not touched."""
         return {k: v[0] for k, v in _host.afterstates_dict(self._dev.afterstates()).items()}
 
+    def plan_values(self, weights: Optional[Dict[str, int]] = None, depth: int = 3) -> Dict[str, np.ndarray]:
+        """Per action, what playing out the hand after it is worth (bb_plan_values; the reference has no
+        counterpart): arrays of shape (192,) -- q (int64, INT64_MIN for an illegal action), a2 / a3 (the rest of
+        the best sequence, -1 for a ply not played), leaves, safe.  ``weights``: bb_greedy_weights fields, default
+        ``agents.DEFAULT_WEIGHTS``.  The state and the piece stream are not touched."""
+        from agents.greedy import DEFAULT_WEIGHTS
+
+        out = self._dev.plan_values(DEFAULT_WEIGHTS if weights is None else weights, depth)
+        return {k: v[0] for k, v in _host.plan_values_dict(out).items()}
+
+    def safe_action_mask(self, depth: int = 3) -> np.ndarray:
+        """bool (192,): the legal actions after which the rest of the hand can still be placed in some order."""
+        return self.plan_values({}, depth)["safe"]
+
     def sample_valid_action(self) -> int:
         valid = self.get_valid_actions()
         if not valid:

@@ -127,6 +127,22 @@ class VectorizedBlockBlastEnv:
         (fp64), score_gained, legal, dead, refill, lines, holes, centre, mobility."""
         return _host.afterstates_dict(self.dev.afterstates())
 
+    def plan_values(self, weights: Optional[Dict[str, int]] = None, depth: int = 3) -> Dict[str, np.ndarray]:
+        """Per action of every env, what playing out the hand after it is worth (bb_plan_values, one launch; the
+        reference has no counterpart): arrays of shape (num_envs, 192) -- q (int64, INT64_MIN for an illegal
+        action), a2 / a3 (the rest of the best sequence, -1 for a ply not played), leaves, safe.  ``weights``:
+        bb_greedy_weights fields, default ``agents.DEFAULT_WEIGHTS``."""
+        from agents.greedy import DEFAULT_WEIGHTS
+
+        return _host.plan_values_dict(self.dev.plan_values(DEFAULT_WEIGHTS if weights is None else weights, depth))
+
+    def safe_action_mask(self, depth: int = 3) -> np.ndarray:
+        """bool (num_envs, 192): the legal actions after which the rest of the hand can still be placed in some
+        order (all False where no legal action is safe)."""
+        from runtime.kernels import mask_bits_to_bool
+
+        return mask_bits_to_bool(self.dev.safe_mask(torch.zeros_like(self._mask_bits), depth).cpu().numpy())
+
     def sample_valid_actions(self) -> np.ndarray:
         """Per-env uniform choice among legal actions with numpy's global RNG,
         like BlockBlastEnv.sample_valid_action (block_blast_env.py:318-323)."""

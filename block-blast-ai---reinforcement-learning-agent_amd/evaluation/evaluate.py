@@ -14,6 +14,11 @@ Beyond the reference: ``--agent greedy`` / ``--agent plan`` / ``--agent random``
 ``agents/greedy.py`` on the same seeds (no checkpoint needed), so a checkpoint's scores have something to be
 compared with.  An agent with ``act_env(env_batch, out)`` picks its actions from the device env itself (the
 fused one-ply kernel); every other agent goes through ``act_device`` as before.
+
+``--safe-mask`` (off by default) restricts the policy to hand-safe actions: the legal moves after which the rest of
+the hand can still be placed in some order (``bb_plan_values``' safe words, one more launch per move).  For
+``--agent ppo`` they are AND-ed into the mask the policy samples under, for ``--agent random`` the agent draws from
+them; a position without a safe move keeps its legal mask.
 """
 from __future__ import annotations
 
@@ -69,10 +74,13 @@ def _evaluate_sequential(agent, num_episodes: int, deterministic: bool, render: 
 
 
 def evaluate_agent(agent, num_episodes: int = 100, deterministic: bool = True, render: bool = False,
-                   seed: int = 42, max_moves: int = 100_000, record_actions: bool = False) -> Dict[str, Any]:
+                   seed: int = 42, max_moves: int = 100_000, record_actions: bool = False,
+                   safe_mask: bool = False) -> Dict[str, Any]:
     """evaluate.py:23-90 (same keys in the returned dict).  record_actions: also return every episode's
     action sequence under "actions" (for replaying the games elsewhere, e.g. through the oracle).  A game still
-    running after max_moves moves is cut off there and reports its score, lines and max combo so far."""
+    running after max_moves moves is cut off there and reports its score, lines and max combo so far.
+    safe_mask: an ``act_device`` agent samples under the legal mask AND the hand-safe mask (the legal mask alone
+    where no move is safe); an ``act_env`` agent chooses its own mask (``RandomAgent(safe=True)``)."""
     agent.eval()
     if render:
         return _evaluate_sequential(agent, num_episodes, deterministic, render, seed, record_actions)
@@ -84,6 +92,7 @@ def evaluate_agent(agent, num_episodes: int = 100, deterministic: bool = True, r
     env.reset()
     x = torch.zeros((n, 4, 8, 8), dtype=torch.float32, device=dev)
     mb = torch.zeros((n, 3), dtype=torch.int64, device=dev)
+    safe_bits = torch.zeros_like(mb) if safe_mask else None
     act = torch.zeros(n, dtype=torch.int32, device=dev)
     alive = torch.ones(n, dtype=torch.bool, device=dev)
     length = torch.zeros(n, dtype=torch.int64, device=dev)
@@ -97,6 +106,10 @@ def evaluate_agent(agent, num_episodes: int = 100, deterministic: bool = True, r
             act_env(env, act)
         else:
             env.obs(x=x, mask_bits=mb)
+            if safe_mask:
+                from agents.greedy import apply_safe_mask
+
+                apply_safe_mask(env, mb, safe_bits)
             a, _, _ = agent.act_device(x, mb, deterministic=deterministic)
             act.copy_(a)
         if record_actions:
@@ -164,6 +177,9 @@ def main() -> None:
     ap.add_argument("--weights", type=str, default=None,
                     help="--agent greedy / plan: a JSON file the agent's save wrote")
     ap.add_argument("--device", type=str, default=None, help="baselines only: cpu = the host backend")
+    ap.add_argument("--safe-mask", action="store_true",
+                    help="--agent ppo / random: choose among hand-safe actions only (the legal moves after which "
+                         "the rest of the hand still fits), among the legal ones where none is safe")
     args = ap.parse_args()
     if args.agent == "ppo":
         if args.checkpoint is None:
@@ -183,14 +199,15 @@ def main() -> None:
         if args.agent == "plan":
             agent = HandPlanAgent(device=args.device)
         else:
-            agent = GreedyAgent(device=args.device) if args.agent == "greedy" else RandomAgent(device=args.device)
+            agent = (GreedyAgent(device=args.device) if args.agent == "greedy"
+                     else RandomAgent(device=args.device, safe=args.safe_mask))
         if args.weights:
             agent.load(args.weights)
         if args.agent == "plan":
             agent.depth = args.depth
-        print(f"Baseline agent: {args.agent}")
+        print(f"Baseline agent: {args.agent}" + (" (hand-safe actions)" if getattr(agent, "safe", False) else ""))
     res = evaluate_agent(agent, num_episodes=args.episodes, deterministic=args.deterministic, render=args.render,
-                         seed=args.seed, max_moves=args.max_moves)
+                         seed=args.seed, max_moves=args.max_moves, safe_mask=args.safe_mask)
     print_results(res)
     if args.output:
         with open(args.output, "w") as f:

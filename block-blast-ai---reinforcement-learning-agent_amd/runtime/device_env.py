@@ -279,6 +279,27 @@ class DeviceEnvBatch:
                 "bb_plan_actions", self.handle, self.lib)
         return out
 
+    def plan_values(self, weights, depth: int = 3, out: Optional[dict] = None) -> dict:
+        """bb_plan_values on the live state: the search of ``plan_actions`` kept per first move.  ``out``: a dict
+        with any of "q" i64 / "rest" i32 / "leaves" i32 [N, 192] and "safe" i64 [N, 3] tensors to write (missing
+        = not computed); None = all four, freshly allocated (see ``runtime.kernels.plan_values``).  Reads the
+        state and changes nothing, the piece stream included."""
+        from . import kernels as K
+
+        out = K.plan_value_outputs(self.num_envs, self.device) if out is None else out
+        o = K._plan_values_out(out, self.num_envs, self.device)
+        w = weights if isinstance(weights, L.GreedyWeights) else L.greedy_weights(weights)
+        L.check(self.lib.bb_plan_values(self.handle, C.byref(w), int(depth), C.byref(o), _stream(self.device)),
+                "bb_plan_values", self.handle, self.lib)
+        return out
+
+    def safe_mask(self, out: torch.Tensor, depth: int = 3) -> torch.Tensor:
+        """The hand-safe action mask into out (int64 [N, 3], the layout of ``obs(mask_bits=)``): the legal actions
+        after which the rest of the hand can still be placed in some order.  All zeros where no legal action is
+        safe (or none is legal).  One launch, nothing else written."""
+        self.plan_values({}, depth, out={"safe": out})
+        return out
+
     # ------------------------------------------------------------ host copies
     def state(self) -> dict:
         n = self.num_envs

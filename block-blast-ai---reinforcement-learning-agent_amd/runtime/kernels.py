@@ -267,6 +267,77 @@ def plan_actions(board: torch.Tensor, hand: torch.Tensor, weights, depth: int = 
     return res
 
 
+PLAN_VALUE_OUTPUTS = {"q": (torch.int64, 192), "rest": (torch.int32, 192), "leaves": (torch.int32, 192),
+                      "safe": (torch.int64, 3)}
+
+
+def plan_value_outputs(n: int, dev, want=("q", "rest", "leaves", "safe")) -> dict:
+    """Fresh output tensors for ``plan_values``: q int64 / rest int32 / leaves int32 [n, 192], safe int64 [n, 3]
+    (the bit patterns of the u64 mask words, as ``DeviceEnvBatch.obs(mask_bits=)`` holds them)."""
+    unknown = set(want) - set(PLAN_VALUE_OUTPUTS)
+    if unknown:
+        raise ValueError(f"unknown plan_values outputs {sorted(unknown)}; they are {tuple(PLAN_VALUE_OUTPUTS)}")
+    return {k: torch.empty((n, PLAN_VALUE_OUTPUTS[k][1]), dtype=PLAN_VALUE_OUTPUTS[k][0], device=dev) for k in want}
+
+
+def _plan_values_out(out: dict, n: int, dev) -> L.PlanValuesOut:
+    """bb_plan_values_out from a dict with any of "q", "rest", "leaves", "safe" (missing or None = NULL)."""
+    o = L.PlanValuesOut()
+    unknown = set(out) - set(PLAN_VALUE_OUTPUTS)
+    if unknown:
+        raise L.BBNativeError(f"plan_values: unknown outputs {sorted(unknown)}")
+    for k, (dt, width) in PLAN_VALUE_OUTPUTS.items():
+        t = out.get(k)
+        if t is None:
+            continue
+        if not (t.dtype == dt and t.device == dev and t.is_contiguous() and t.numel() == n * width):
+            raise L.BBNativeError(f"plan_values: {k} must be a contiguous {dt} [{n}, {width}] on {dev}")
+        setattr(o, k, t.data_ptr())
+    if not any(out.get(k) is not None for k in PLAN_VALUE_OUTPUTS):
+        raise L.BBNativeError("plan_values: at least one of q, rest, leaves, safe is required")
+    return o
+
+
+def plan_values(board: torch.Tensor, hand: torch.Tensor, weights, depth: int = 3,
+                combo: Optional[torch.Tensor] = None, want=("q", "rest", "leaves", "safe"),
+                out: Optional[dict] = None) -> dict:
+    """bb_plan_values_pos: the full-hand search of ``plan_actions`` with its result kept per first move, in one
+    fused launch (bbvec.h "per-action full-hand values").  Returns a dict of the outputs named in ``want`` (or the
+    tensors of ``out``, written in place): "q" int64 [n, 192] the best value of the sequences that start with
+    each action (INT64_MIN: illegal), "rest" int32 [n, 192] a2 | a3 << 8 of that sequence (0xFF: ply not played,
+    -1: illegal), "leaves" int32 [n, 192] their number, "safe" int64 [n, 3] the mask words (layout of mask_bits)
+    of the legal actions after which the rest of the hand can still be placed some way; ``safe`` does not depend
+    on the weights.  ``unpack_rest`` / ``mask_bits_to_bool`` decode."""
+    pos, n, dev = _positions(board, hand, combo, None)
+    w = weights if isinstance(weights, L.GreedyWeights) else L.greedy_weights(weights)
+    out = plan_value_outputs(n, dev, want) if out is None else out
+    o = _plan_values_out(out, n, dev)
+    lib, stream = _look_lib(dev)
+    L.check(lib.bb_plan_values_pos(C.byref(pos), n, C.byref(w), int(depth), C.byref(o), stream),
+            "bb_plan_values_pos", lib=lib)
+    return out
+
+
+def unpack_rest(rest):
+    """(a2, a3) of bb_plan_values' rest words (torch or numpy), -1 for a ply not played or an illegal action."""
+    a2, a3 = rest & 0xFF, (rest >> 8) & 0xFF
+    if isinstance(rest, torch.Tensor):
+        return torch.where((rest < 0) | (a2 == 0xFF), -1, a2), torch.where((rest < 0) | (a3 == 0xFF), -1, a3)
+    import numpy as np
+
+    return np.where((rest < 0) | (a2 == 0xFF), -1, a2), np.where((rest < 0) | (a3 == 0xFF), -1, a3)
+
+
+def mask_bits_to_bool(bits):
+    """Mask words [n, 3] (int64 / uint64 bit patterns, torch or numpy) -> bool [n, 192]."""
+    if isinstance(bits, torch.Tensor):
+        return ((bits.unsqueeze(-1) >> torch.arange(64, device=bits.device)) & 1).bool().reshape(bits.shape[0], 192)
+    import numpy as np
+
+    b = np.asarray(bits).view(np.uint64)
+    return ((b[..., None] >> np.arange(64, dtype=np.uint64)) & np.uint64(1)).astype(bool).reshape(b.shape[0], 192)
+
+
 def unpack_aux(aux) -> dict:
     """The fields of the afterstate aux word (bbvec.h): works on a torch tensor or a numpy array."""
     a = aux.to(torch.int64) & 0xFFFFFFFF if isinstance(aux, torch.Tensor) else (aux.astype("int64") & 0xFFFFFFFF)

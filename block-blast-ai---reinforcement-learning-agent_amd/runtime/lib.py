@@ -141,6 +141,12 @@ class PlanOut(C.Structure):
     _fields_ = [("action", C.c_void_p), ("value", C.c_void_p), ("plan", C.c_void_p), ("leaves", C.c_void_p)]
 
 
+class PlanValuesOut(C.Structure):
+    """bb_plan_values_out: device arrays q i64 / rest i32 / leaves i32 [n][192], safe u64 [n][3]; any may be NULL,
+    not all four."""
+    _fields_ = [("q", C.c_void_p), ("rest", C.c_void_p), ("leaves", C.c_void_p), ("safe", C.c_void_p)]
+
+
 _P = C.c_void_p
 _I32 = C.c_int32
 _U64 = C.c_uint64
@@ -206,6 +212,9 @@ SIGNATURES = {
     "bb_greedy_actions": (C.c_int, [_P, C.POINTER(GreedyWeights), _P, _P, _P]),
     "bb_plan_actions_pos": (C.c_int, [C.POINTER(Positions), _I32, C.POINTER(GreedyWeights), _I32, C.POINTER(PlanOut), _P]),
     "bb_plan_actions": (C.c_int, [_P, C.POINTER(GreedyWeights), _I32, C.POINTER(PlanOut), _P]),
+    "bb_plan_values_pos": (C.c_int, [C.POINTER(Positions), _I32, C.POINTER(GreedyWeights), _I32,
+                                     C.POINTER(PlanValuesOut), _P]),
+    "bb_plan_values": (C.c_int, [_P, C.POINTER(GreedyWeights), _I32, C.POINTER(PlanValuesOut), _P]),
     "bb_masked_sample": (C.c_int, [_P, _P, _I32, _P, _U64, _U64, _U64, _I32, _P, _P, _P, _P, _P]),
     "bb_masked_sample_dstep": (C.c_int, [_P, _P, _I32, _U64, _P, _U64, _U64, _I32, _P, _P, _P, _P]),
     "bb_gae": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _F, _F, _P, _P, _P]),
@@ -258,7 +267,8 @@ SIGNATURES = {
 HOST_SYMBOLS = ("bb_abi_version", "bb_build_id", "bb_create", "bb_destroy", "bb_last_error", "bb_num_envs", "bb_pcg64_seed",
                 "bb_seed", "bb_reset", "bb_step", "bb_rollout", "bb_sync", "bb_obs", "bb_device_ptrs", "bb_snapshot",
                 "bb_get_state", "bb_set_state", "bb_random_actions", "bb_afterstates_pos", "bb_afterstates",
-                "bb_greedy_actions_pos", "bb_greedy_actions", "bb_plan_actions_pos", "bb_plan_actions")
+                "bb_greedy_actions_pos", "bb_greedy_actions", "bb_plan_actions_pos", "bb_plan_actions",
+                "bb_plan_values_pos", "bb_plan_values")
 
 _lib = None
 _host = None

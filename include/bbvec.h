@@ -52,7 +52,9 @@ extern "C" {
                               9: bb_bn_fwd / bb_bn_bwd / bb_wgrad_reduce / bb_ppo_loss_args: bb_bn_forward, bb_bn_backward
                                  and bb_ppo_loss_forward / _backward / _fused take one argument struct;
                                  bb_bn_forward_res / _part, bb_bn_backward_red / _part / _res and
-                                 bb_ppo_loss_forward_bf16 / _backward_bf16 removed (fields of the structs) */
+                                 bb_ppo_loss_forward_bf16 / _backward_bf16 removed (fields of the structs);
+                                 (additive, still 9) bb_plan_values_out with bb_plan_values(_pos): per-action
+                                 full-hand values and the hand-safe mask */
 
 #define BB_OK 0
 #define BB_ERR_ARG (-1)
@@ -372,6 +374,50 @@ typedef struct bb_plan_out {
 int bb_plan_actions_pos(const bb_positions* pos, int32_t n, const bb_greedy_weights* w, int32_t depth,
                         const bb_plan_out* out, void* stream);
 int bb_plan_actions(bb_env* env, const bb_greedy_weights* w, int32_t depth, const bb_plan_out* out, void* stream);
+
+/* ---- per-action full-hand values and the hand-safe mask -----------------------
+ * What bb_plan_actions folds into one maximum, kept per first move.  The search
+ * is search(P, depth) above, move for move (engine.py:326-346, 390-431, 348-362;
+ * the hand is dealt together, engine.py:155-172, and refilled only after its
+ * third piece, engine.py:432-437); the reference has no such call.  For action
+ * a of position i, over the maximal sequences whose first move is a:
+ *   q      [n][192] the largest value (move terms summed along the sequence +
+ *                   state terms of its last afterstate, int64); INT64_MIN when
+ *                   a is illegal
+ *   rest   [n][192] a_2 | a_3 << 8 of the best such sequence, ties to the
+ *                   lexicographically lowest (a_2, a_3); 0xFF stands for a ply
+ *                   not played (a sequence that ends at ply 1: 0xFFFF); -1 when
+ *                   a is illegal
+ *   leaves [n][192] the number of such sequences; 0 when a is illegal
+ *   safe   [n][3]   mask word of hand slot p: bit c is set iff action p*64 + c
+ *                   is legal and at least one maximal sequence that starts with
+ *                   it ends in an afterstate with dead == 0.  The layout is
+ *                   that of bb_obs / bb_snapshot mask_bits, so the words go
+ *                   straight into bb_random_actions and bb_masked_sample.  safe
+ *                   does not depend on w.  At depth 1 it is legal & !dead.  At
+ *                   depth 2 and depth 3 it is the same set: a ply-2 afterstate
+ *                   that is neither a refill nor dead means the hand was whole
+ *                   and its last piece fits, so a third move exists, and that
+ *                   move is a refill, which is never dead.
+ * With the same w and depth, bb_plan_actions' value is max_a q, its action the
+ * lowest a attaining it, its plan[1:] the decoded rest[action] and its leaves
+ * the sum of leaves over a.  Any output may be NULL, not all four.  depth is
+ * 1..3; n == 0 does nothing.  BB_ERR_ARG (the rule named in bb_last_error,
+ * before any HIP call) for a NULL pos / pos->board / pos->hand / w / out, all
+ * four outputs NULL, n < 0 and depth outside 1..3.  The handle form reads the
+ * live columns and changes nothing, the RNG included, and refuses a handle in
+ * BB_ERR_DEVICE / BB_ERR_STATE.  Asynchronous on `stream`, no allocation, no
+ * sync (graph-capturable from the first call); indexing is 64-bit. */
+typedef struct bb_plan_values_out {
+  int64_t*  q;       /* [n][192] */
+  int32_t*  rest;    /* [n][192] */
+  int32_t*  leaves;  /* [n][192] */
+  uint64_t* safe;    /* [n][3]   */
+} bb_plan_values_out;   /* device pointers; any may be NULL, not all four */
+
+int bb_plan_values_pos(const bb_positions* pos, int32_t n, const bb_greedy_weights* w, int32_t depth,
+                       const bb_plan_values_out* out, void* stream);
+int bb_plan_values(bb_env* env, const bb_greedy_weights* w, int32_t depth, const bb_plan_values_out* out, void* stream);
 
 /* Fused masked-categorical tail of BlockBlastNetwork.get_action_and_value
  * (network.py:173-180, 210-262; Categorical clamp semantics of torch 2.10):
