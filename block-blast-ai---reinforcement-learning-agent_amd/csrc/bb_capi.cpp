@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "bb_env_internal.h"
+#include "bb_look_rules.h"
 
 using namespace bb;
 
@@ -138,6 +139,28 @@ StepArgs base_args(const bb_env* env) {
   a.dbg = env->dbg;
   a.dbg_out = env->dbg_out;
   return a;
+}
+
+// The lookahead entry points (csrc/bb_lookahead.hip).  `rule` is the argument rule the call breaks
+// (bb_look_rules.h) or NULL; `launch` launches the kernel and returns its hipError_t.  The _pos forms are stateless
+// and run on the current device; the handle forms refuse, in this order, a NULL env, a broken rule, a raised
+// status word and a handle left broken by a failed bb_step.
+template <typename Launch>
+int look_pos_call(const char* name, const char* rule, Launch launch) {
+  if (rule) return fail(nullptr, BB_ERR_ARG, std::string(name) + ": " + rule);
+  hipError_t st = launch();
+  return st == hipSuccess ? BB_OK : hip_fail(nullptr, st, name);
+}
+
+template <typename Launch>
+int look_env_call(bb_env* env, const char* name, const char* rule, Launch launch) {
+  if (!env) return BB_ERR_ARG;
+  if (rule) return fail(env, BB_ERR_ARG, std::string(name) + ": " + rule);
+  if (status_fail(env, name) != BB_OK) return BB_ERR_DEVICE;  // the state an incomplete launch left
+  if (env->broken) return broken_fail(env, name);
+  DeviceGuard g(env->device);
+  hipError_t st = launch();
+  return st == hipSuccess ? BB_OK : hip_fail(env, st, name);
 }
 
 }  // namespace
@@ -567,108 +590,62 @@ int bb_random_actions(const uint64_t* d_mask_bits, int32_t n, uint64_t seed, uin
   return BB_OK;
 }
 
-// One-ply lookahead (csrc/bb_lookahead.hip).  The _pos forms are stateless and run on the current device.
+// Lookahead (csrc/bb_lookahead.hip): the _pos forms are stateless and run on the current device.
 int bb_afterstates_pos(const bb_positions* pos, int32_t n, const bb_reward_cfg* cfg, const bb_afterstate_out* out,
                        void* stream) {
-  if (!pos || !pos->board || !pos->hand || n <= 0 || !cfg || !out)
-    return fail(nullptr, BB_ERR_ARG, "bb_afterstates_pos: positions (board, hand), n > 0, cfg and out are required");
-  hipError_t st = launch_afterstates(pos->board, pos->hand, pos->combo, pos->prev, n, *cfg, *out, (hipStream_t)stream);
-  if (st != hipSuccess) return fail(nullptr, BB_ERR_HIP, std::string("bb_afterstates_pos: ") + hipGetErrorString(st));
-  return BB_OK;
+  return look_pos_call("bb_afterstates_pos", bb_look_rules::afterstates_pos(pos, n, cfg, out), [&] {
+    return launch_afterstates(pos->board, pos->hand, pos->combo, pos->prev, n, *cfg, *out, (hipStream_t)stream);
+  });
 }
 
 int bb_afterstates(bb_env* env, const bb_afterstate_out* out, void* stream) {
-  if (!env) return BB_ERR_ARG;
-  if (!out) return fail(env, BB_ERR_ARG, "bb_afterstates: out is NULL");
-  if (status_fail(env, "bb_afterstates") != BB_OK) return BB_ERR_DEVICE;  // the state an incomplete launch left
-  if (env->broken) return broken_fail(env, "bb_afterstates");
-  DeviceGuard g(env->device);
-  hipError_t st = launch_afterstates(env->d.board, env->d.hand, env->d.combo, env->d.prev, env->n, env->cfg, *out,
-                                     (hipStream_t)stream);
-  if (st != hipSuccess) return hip_fail(env, st, "bb_afterstates");
-  return BB_OK;
+  return look_env_call(env, "bb_afterstates", bb_look_rules::afterstates(out), [&] {
+    return launch_afterstates(env->d.board, env->d.hand, env->d.combo, env->d.prev, env->n, env->cfg, *out,
+                              (hipStream_t)stream);
+  });
 }
 
 int bb_greedy_actions_pos(const bb_positions* pos, int32_t n, const bb_greedy_weights* w, int32_t* d_action,
                           int64_t* d_value, void* stream) {
-  if (!pos || !pos->board || !pos->hand || n <= 0 || !w || !d_action)
-    return fail(nullptr, BB_ERR_ARG,
-                "bb_greedy_actions_pos: positions (board, hand), n > 0, weights and d_action are required");
-  hipError_t st = launch_greedy(pos->board, pos->hand, pos->combo, n, *w, d_action, d_value, (hipStream_t)stream);
-  if (st != hipSuccess)
-    return fail(nullptr, BB_ERR_HIP, std::string("bb_greedy_actions_pos: ") + hipGetErrorString(st));
-  return BB_OK;
+  return look_pos_call("bb_greedy_actions_pos", bb_look_rules::greedy_actions_pos(pos, n, w, d_action), [&] {
+    return launch_greedy(pos->board, pos->hand, pos->combo, n, *w, d_action, d_value, (hipStream_t)stream);
+  });
 }
 
 int bb_greedy_actions(bb_env* env, const bb_greedy_weights* w, int32_t* d_action, int64_t* d_value, void* stream) {
-  if (!env) return BB_ERR_ARG;
-  if (!w || !d_action) return fail(env, BB_ERR_ARG, "bb_greedy_actions: weights and d_action are required");
-  if (status_fail(env, "bb_greedy_actions") != BB_OK) return BB_ERR_DEVICE;
-  if (env->broken) return broken_fail(env, "bb_greedy_actions");
-  DeviceGuard g(env->device);
-  hipError_t st = launch_greedy(env->d.board, env->d.hand, env->d.combo, env->n, *w, d_action, d_value,
-                                (hipStream_t)stream);
-  if (st != hipSuccess) return hip_fail(env, st, "bb_greedy_actions");
-  return BB_OK;
+  return look_env_call(env, "bb_greedy_actions", bb_look_rules::greedy_actions(w, d_action), [&] {
+    return launch_greedy(env->d.board, env->d.hand, env->d.combo, env->n, *w, d_action, d_value, (hipStream_t)stream);
+  });
 }
 
-// Full-hand lookahead (plan_kernel in csrc/bb_lookahead.hip).
+// Full-hand lookahead (plan_kernel)
 int bb_plan_actions_pos(const bb_positions* pos, int32_t n, const bb_greedy_weights* w, int32_t depth,
                         const bb_plan_out* out, void* stream) {
-  if (!pos || !pos->board || !pos->hand || n <= 0 || !w || !out || !out->action || depth < 1 || depth > 3)
-    return fail(nullptr, BB_ERR_ARG,
-                "bb_plan_actions_pos: positions (board, hand), n > 0, weights, depth in 1..3 and out->action are "
-                "required");
-  hipError_t st = launch_plan(pos->board, pos->hand, pos->combo, n, *w, depth, *out, (hipStream_t)stream);
-  if (st != hipSuccess) return fail(nullptr, BB_ERR_HIP, std::string("bb_plan_actions_pos: ") + hipGetErrorString(st));
-  return BB_OK;
+  return look_pos_call("bb_plan_actions_pos", bb_look_rules::plan_actions_pos(pos, n, w, depth, out), [&] {
+    return launch_plan(pos->board, pos->hand, pos->combo, n, *w, depth, *out, (hipStream_t)stream);
+  });
 }
 
 int bb_plan_actions(bb_env* env, const bb_greedy_weights* w, int32_t depth, const bb_plan_out* out, void* stream) {
-  if (!env) return BB_ERR_ARG;
-  if (!w || !out || !out->action || depth < 1 || depth > 3)
-    return fail(env, BB_ERR_ARG, "bb_plan_actions: weights, depth in 1..3 and out->action are required");
-  if (status_fail(env, "bb_plan_actions") != BB_OK) return BB_ERR_DEVICE;
-  if (env->broken) return broken_fail(env, "bb_plan_actions");
-  DeviceGuard g(env->device);
-  hipError_t st = launch_plan(env->d.board, env->d.hand, env->d.combo, env->n, *w, depth, *out, (hipStream_t)stream);
-  if (st != hipSuccess) return hip_fail(env, st, "bb_plan_actions");
-  return BB_OK;
+  return look_env_call(env, "bb_plan_actions", bb_look_rules::plan_actions(w, depth, out), [&] {
+    return launch_plan(env->d.board, env->d.hand, env->d.combo, env->n, *w, depth, *out, (hipStream_t)stream);
+  });
 }
 
-// Per-action full-hand values (plan_values_kernel in csrc/bb_lookahead.hip).  The rule an argument set breaks,
-// or NULL: checked before any HIP call.
-static const char* plan_values_rule(const bb_greedy_weights* w, int32_t depth, const bb_plan_values_out* out) {
-  if (!w) return "weights are NULL";
-  if (!out) return "out is NULL";
-  if (!out->q && !out->rest && !out->leaves && !out->safe) return "all four outputs are NULL";
-  if (depth < 1 || depth > 3) return "depth must be 1..3";
-  return nullptr;
-}
-
+// Per-action full-hand values (plan_values_kernel)
 int bb_plan_values_pos(const bb_positions* pos, int32_t n, const bb_greedy_weights* w, int32_t depth,
                        const bb_plan_values_out* out, void* stream) {
-  const char* rule = !pos || !pos->board || !pos->hand ? "positions (board, hand) are NULL"
-                     : n < 0                           ? "n is negative"
-                                                       : plan_values_rule(w, depth, out);
-  if (rule) return fail(nullptr, BB_ERR_ARG, std::string("bb_plan_values_pos: ") + rule);
-  if (n == 0) return BB_OK;
-  hipError_t st = launch_plan_values(pos->board, pos->hand, pos->combo, n, *w, depth, *out, (hipStream_t)stream);
-  if (st != hipSuccess) return fail(nullptr, BB_ERR_HIP, std::string("bb_plan_values_pos: ") + hipGetErrorString(st));
-  return BB_OK;
+  const char* rule = bb_look_rules::plan_values_pos(pos, n, w, depth, out);
+  if (!rule && n == 0) return BB_OK;  // accepted, and nothing to do
+  return look_pos_call("bb_plan_values_pos", rule, [&] {
+    return launch_plan_values(pos->board, pos->hand, pos->combo, n, *w, depth, *out, (hipStream_t)stream);
+  });
 }
 
 int bb_plan_values(bb_env* env, const bb_greedy_weights* w, int32_t depth, const bb_plan_values_out* out, void* stream) {
-  if (!env) return BB_ERR_ARG;
-  if (const char* rule = plan_values_rule(w, depth, out))
-    return fail(env, BB_ERR_ARG, std::string("bb_plan_values: ") + rule);
-  if (status_fail(env, "bb_plan_values") != BB_OK) return BB_ERR_DEVICE;
-  if (env->broken) return broken_fail(env, "bb_plan_values");
-  DeviceGuard g(env->device);
-  hipError_t st =
-      launch_plan_values(env->d.board, env->d.hand, env->d.combo, env->n, *w, depth, *out, (hipStream_t)stream);
-  if (st != hipSuccess) return hip_fail(env, st, "bb_plan_values");
-  return BB_OK;
+  return look_env_call(env, "bb_plan_values", bb_look_rules::plan_values(w, depth, out), [&] {
+    return launch_plan_values(env->d.board, env->d.hand, env->d.combo, env->n, *w, depth, *out, (hipStream_t)stream);
+  });
 }
 
 int bb_masked_sample(const float* d_logits, const uint64_t* d_mask_bits, int32_t n, const float* d_uniform,

@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "../../include/bbvec.h"
+#include "bb_look_rules.h"
 #include "bb_rules.h"
 #include "bb_seed.h"
 
@@ -211,6 +212,13 @@ int fail(bb_env* e, int code, const std::string& msg) {
   if (e) e->err = msg;
   else g_create_err = msg;
   return code;
+}
+
+// a lookahead call's broken argument rule (bb_look_rules.h) as BB_ERR_ARG with the text "<entry point>: <rule>";
+// BB_OK (0) when no rule is broken
+namespace R = bb_look_rules;
+int refused(bb_env* e, const char* name, const char* rule) {
+  return rule ? fail(e, BB_ERR_ARG, std::string(name) + ": " + rule) : BB_OK;
 }
 
 void masks_of(uint64_t B, uint32_t hand, uint64_t m[3]) {  // engine.py:364-380 (status not consulted)
@@ -700,11 +708,12 @@ int bb_random_actions(const uint64_t* d_mask_bits, int32_t n, uint64_t seed, uin
   return BB_OK;
 }
 
+// Lookahead.  The argument rules are those of csrc/bb_capi.cpp, from the same header (bb_look_rules.h).
+
 int bb_afterstates_pos(const bb_positions* pos, int32_t n, const bb_reward_cfg* cfg, const bb_afterstate_out* out,
                        void* stream) {
   (void)stream;
-  if (!pos || !pos->board || !pos->hand || n <= 0 || !cfg || !out)
-    return fail(nullptr, BB_ERR_ARG, "bb_afterstates_pos: positions (board, hand), n > 0, cfg and out are required");
+  if (int rc = refused(nullptr, "bb_afterstates_pos", R::afterstates_pos(pos, n, cfg, out))) return rc;
   afterstates_host(pos->board, pos->hand, pos->combo, pos->prev, n, *cfg, *out);
   return BB_OK;
 }
@@ -712,7 +721,7 @@ int bb_afterstates_pos(const bb_positions* pos, int32_t n, const bb_reward_cfg* 
 int bb_afterstates(bb_env* env, const bb_afterstate_out* out, void* stream) {
   (void)stream;
   if (!env) return BB_ERR_ARG;
-  if (!out) return fail(env, BB_ERR_ARG, "bb_afterstates: out is NULL");
+  if (int rc = refused(env, "bb_afterstates", R::afterstates(out))) return rc;
   afterstates_host(env->board.data(), env->hand.data(), env->combo.data(), env->prev.data(), env->n, env->cfg, *out);
   return BB_OK;
 }
@@ -720,9 +729,7 @@ int bb_afterstates(bb_env* env, const bb_afterstate_out* out, void* stream) {
 int bb_greedy_actions_pos(const bb_positions* pos, int32_t n, const bb_greedy_weights* w, int32_t* d_action,
                           int64_t* d_value, void* stream) {
   (void)stream;
-  if (!pos || !pos->board || !pos->hand || n <= 0 || !w || !d_action)
-    return fail(nullptr, BB_ERR_ARG,
-                "bb_greedy_actions_pos: positions (board, hand), n > 0, weights and d_action are required");
+  if (int rc = refused(nullptr, "bb_greedy_actions_pos", R::greedy_actions_pos(pos, n, w, d_action))) return rc;
   greedy_host(pos->board, pos->hand, pos->combo, n, *w, d_action, d_value);
   return BB_OK;
 }
@@ -730,7 +737,7 @@ int bb_greedy_actions_pos(const bb_positions* pos, int32_t n, const bb_greedy_we
 int bb_greedy_actions(bb_env* env, const bb_greedy_weights* w, int32_t* d_action, int64_t* d_value, void* stream) {
   (void)stream;
   if (!env) return BB_ERR_ARG;
-  if (!w || !d_action) return fail(env, BB_ERR_ARG, "bb_greedy_actions: weights and d_action are required");
+  if (int rc = refused(env, "bb_greedy_actions", R::greedy_actions(w, d_action))) return rc;
   greedy_host(env->board.data(), env->hand.data(), env->combo.data(), env->n, *w, d_action, d_value);
   return BB_OK;
 }
@@ -738,10 +745,7 @@ int bb_greedy_actions(bb_env* env, const bb_greedy_weights* w, int32_t* d_action
 int bb_plan_actions_pos(const bb_positions* pos, int32_t n, const bb_greedy_weights* w, int32_t depth,
                         const bb_plan_out* out, void* stream) {
   (void)stream;
-  if (!pos || !pos->board || !pos->hand || n <= 0 || !w || !out || !out->action || depth < 1 || depth > 3)
-    return fail(nullptr, BB_ERR_ARG,
-                "bb_plan_actions_pos: positions (board, hand), n > 0, weights, depth in 1..3 and out->action are "
-                "required");
+  if (int rc = refused(nullptr, "bb_plan_actions_pos", R::plan_actions_pos(pos, n, w, depth, out))) return rc;
   plan_host(pos->board, pos->hand, pos->combo, n, *w, depth, *out);
   return BB_OK;
 }
@@ -749,28 +753,15 @@ int bb_plan_actions_pos(const bb_positions* pos, int32_t n, const bb_greedy_weig
 int bb_plan_actions(bb_env* env, const bb_greedy_weights* w, int32_t depth, const bb_plan_out* out, void* stream) {
   (void)stream;
   if (!env) return BB_ERR_ARG;
-  if (!w || !out || !out->action || depth < 1 || depth > 3)
-    return fail(env, BB_ERR_ARG, "bb_plan_actions: weights, depth in 1..3 and out->action are required");
+  if (int rc = refused(env, "bb_plan_actions", R::plan_actions(w, depth, out))) return rc;
   plan_host(env->board.data(), env->hand.data(), env->combo.data(), env->n, *w, depth, *out);
   return BB_OK;
-}
-
-// the rule an argument set breaks, or NULL (the rules of csrc/bb_capi.cpp)
-static const char* plan_values_rule(const bb_greedy_weights* w, int32_t depth, const bb_plan_values_out* out) {
-  if (!w) return "weights are NULL";
-  if (!out) return "out is NULL";
-  if (!out->q && !out->rest && !out->leaves && !out->safe) return "all four outputs are NULL";
-  if (depth < 1 || depth > 3) return "depth must be 1..3";
-  return nullptr;
 }
 
 int bb_plan_values_pos(const bb_positions* pos, int32_t n, const bb_greedy_weights* w, int32_t depth,
                        const bb_plan_values_out* out, void* stream) {
   (void)stream;
-  const char* rule = !pos || !pos->board || !pos->hand ? "positions (board, hand) are NULL"
-                     : n < 0                           ? "n is negative"
-                                                       : plan_values_rule(w, depth, out);
-  if (rule) return fail(nullptr, BB_ERR_ARG, std::string("bb_plan_values_pos: ") + rule);
+  if (int rc = refused(nullptr, "bb_plan_values_pos", R::plan_values_pos(pos, n, w, depth, out))) return rc;
   plan_values_host(pos->board, pos->hand, pos->combo, n, *w, depth, *out);
   return BB_OK;
 }
@@ -778,8 +769,7 @@ int bb_plan_values_pos(const bb_positions* pos, int32_t n, const bb_greedy_weigh
 int bb_plan_values(bb_env* env, const bb_greedy_weights* w, int32_t depth, const bb_plan_values_out* out, void* stream) {
   (void)stream;
   if (!env) return BB_ERR_ARG;
-  if (const char* rule = plan_values_rule(w, depth, out))
-    return fail(env, BB_ERR_ARG, std::string("bb_plan_values: ") + rule);
+  if (int rc = refused(env, "bb_plan_values", R::plan_values(w, depth, out))) return rc;
   plan_values_host(env->board.data(), env->hand.data(), env->combo.data(), env->n, *w, depth, *out);
   return BB_OK;
 }

@@ -1,0 +1,63 @@
+// bb_look_rules.h -- the argument rules of the eight lookahead entry points of include/bbvec.h, one copy for
+// both backends (csrc/bb_capi.cpp and csrc/bb_host.cpp).  Plain C++, nothing from HIP.
+//
+// Each function returns the rule an argument set breaks, as the text that follows "<entry point>: " in
+// bb_last_error, or nullptr when the call is accepted.  A refusal is BB_ERR_ARG and comes before any HIP call.
+// The handle forms check the handle themselves, first: a NULL env is a bare BB_ERR_ARG with no text.
+//
+// Asymmetries that are part of the ABI as it stands: bb_afterstates_pos, bb_greedy_actions_pos and
+// bb_plan_actions_pos refuse n == 0 and answer every broken rule with one text; bb_plan_values_pos accepts n == 0
+// (and does nothing) and names the rule that broke.
+#pragma once
+#include <stdint.h>
+
+#include "../../include/bbvec.h"
+
+namespace bb_look_rules {
+
+inline bool no_positions(const bb_positions* pos) { return !pos || !pos->board || !pos->hand; }
+inline bool bad_depth(int32_t depth) { return depth < 1 || depth > 3; }
+
+inline const char* afterstates(const bb_afterstate_out* out) { return out ? nullptr : "out is NULL"; }
+inline const char* afterstates_pos(const bb_positions* pos, int32_t n, const bb_reward_cfg* cfg,
+                                   const bb_afterstate_out* out) {
+  return no_positions(pos) || n <= 0 || !cfg || !out ? "positions (board, hand), n > 0, cfg and out are required"
+                                                     : nullptr;
+}
+
+inline const char* greedy_actions(const bb_greedy_weights* w, const int32_t* d_action) {
+  return !w || !d_action ? "weights and d_action are required" : nullptr;
+}
+inline const char* greedy_actions_pos(const bb_positions* pos, int32_t n, const bb_greedy_weights* w,
+                                      const int32_t* d_action) {
+  return no_positions(pos) || n <= 0 || !w || !d_action
+             ? "positions (board, hand), n > 0, weights and d_action are required"
+             : nullptr;
+}
+
+inline const char* plan_actions(const bb_greedy_weights* w, int32_t depth, const bb_plan_out* out) {
+  return !w || !out || !out->action || bad_depth(depth) ? "weights, depth in 1..3 and out->action are required"
+                                                        : nullptr;
+}
+inline const char* plan_actions_pos(const bb_positions* pos, int32_t n, const bb_greedy_weights* w, int32_t depth,
+                                    const bb_plan_out* out) {
+  return no_positions(pos) || n <= 0 || !w || !out || !out->action || bad_depth(depth)
+             ? "positions (board, hand), n > 0, weights, depth in 1..3 and out->action are required"
+             : nullptr;
+}
+
+inline const char* plan_values(const bb_greedy_weights* w, int32_t depth, const bb_plan_values_out* out) {
+  if (!w) return "weights are NULL";
+  if (!out) return "out is NULL";
+  if (!out->q && !out->rest && !out->leaves && !out->safe) return "all four outputs are NULL";
+  if (bad_depth(depth)) return "depth must be 1..3";
+  return nullptr;
+}
+inline const char* plan_values_pos(const bb_positions* pos, int32_t n, const bb_greedy_weights* w, int32_t depth,
+                                   const bb_plan_values_out* out) {
+  if (no_positions(pos)) return "positions (board, hand) are NULL";
+  if (n < 0) return "n is negative";
+  return plan_values(w, depth, out);
+}
+
+}  // namespace bb_look_rules

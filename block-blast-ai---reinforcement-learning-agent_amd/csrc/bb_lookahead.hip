@@ -75,18 +75,27 @@ struct LookPos {
   const uint16_t* prev;
 };
 
+// position i of the columns (i is wave-uniform), in scalar registers; a NULL combo column reads as 0
+struct Position {
+  uint64_t B;
+  uint32_t hand;
+  int combo;
+};
+__device__ __forceinline__ Position load_position(const LookPos& pos, int64_t i) {
+  return Position{uniform64(pos.board[i]), uniform32(pos.hand[i]),
+                  (int)uniform32(pos.combo ? (uint32_t)pos.combo[i] : 0u)};
+}
+
 __global__ void __launch_bounds__(kLookBlock)
 afterstates_kernel(LookTable t, LookPos pos, int n, bb_reward_cfg cfg, double center_tenth, bb_afterstate_out out) {
   const int p = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // hand slot: one per wave
   const int cell = (int)(threadIdx.x & 63u);
   for (int64_t i = blockIdx.x; i < (int64_t)n; i += gridDim.x) {
-    const uint64_t B = uniform64(pos.board[i]);
-    const uint32_t hand = uniform32(pos.hand[i]);
-    const int combo = (int)uniform32(pos.combo ? (uint32_t)pos.combo[i] : 0u);
+    const Position P = load_position(pos, i);
     const uint32_t prev = uniform32(pos.prev ? pos.prev[i] : 0u);
-    const After a = eval_action(t, B, hand, combo, p, cell);
+    const After a = eval_action(t, P.B, P.hand, P.combo, p, cell);
     const int64_t o = i * 192 + (int64_t)(p * 64 + cell);
-    if (out.board) out.board[o] = a.legal ? a.board : B;
+    if (out.board) out.board[o] = a.legal ? a.board : P.B;
     if (out.reward_f64) out.reward_f64[o] = a.legal ? after_reward(a, cfg, center_tenth, prev) : -10.0;
     if (out.score_gained) out.score_gained[o] = a.legal ? (int32_t)a.gained : 0;
     if (out.aux) out.aux[o] = a.legal ? pack_aux(a) : 0u;
@@ -108,8 +117,8 @@ greedy_kernel(LookTable t, LookPos pos, int n, bb_greedy_weights w, int32_t* __r
   const int p = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int cell = (int)(threadIdx.x & 63u);
   for (int64_t i = blockIdx.x; i < (int64_t)n; i += gridDim.x) {
-    const After a = eval_action(t, uniform64(pos.board[i]), uniform32(pos.hand[i]),
-                                (int)uniform32(pos.combo ? (uint32_t)pos.combo[i] : 0u), p, cell);
+    const Position P = load_position(pos, i);
+    const After a = eval_action(t, P.B, P.hand, P.combo, p, cell);
     // an illegal lane carries (INT64_MIN, 0): every legal value is above INT64_MIN (|weight| < 2^31, every
     // feature < 2^15), so it never wins over a legal lane, and with no legal lane the result is action 0
     int64_t v = a.legal ? move_terms(w, a) + state_terms(w, a) : INT64_MIN;
@@ -176,6 +185,105 @@ __device__ __forceinline__ void take_plan(int64_t& v, uint32_t& key, int64_t v2,
   key = better ? key2 : key;
 }
 
+// ---- the search body shared by plan_kernel and plan_values_kernel ----
+
+// Ply 1, evaluation: wave p < 3 takes hand slot p, lane = anchor cell.  `open`: legal and not the end of its
+// sequence (goes to the record list); `closed`: legal and the end (depth 1, refill or dead).  Wave 3 gets a zeroed
+// afterstate and neither flag: left indeterminate there, `a` costs each kernel 12 VGPRs (65 / 69 against 53 / 57).
+struct Ply1 {
+  After a;
+  bool open, closed;
+};
+__device__ __forceinline__ Ply1 plan_ply1(const LookTable& t, const Position& P, int depth, int wave, int cell) {
+  Ply1 r{};
+  if (wave < kHand) {
+    r.a = eval_action(t, P.B, P.hand, P.combo, wave, cell);
+    const bool end1 = depth == 1 || r.a.refill || r.a.dead;
+    r.open = r.a.legal && !end1;
+    r.closed = r.a.legal && end1;
+  }
+  return r;
+}
+
+// Ply 1, compaction: the open lanes of waves 0..2 become the records s_rec[0..total), in action order (ballot,
+// prefix popcount).  Returns total <= kPlanRecords; both barriers have passed.  The kernels call this after the
+// lanes that are not open have used their afterstate (scored themselves, filled their staging entry): from here
+// on only an open lane's board, move terms and combo' are needed, so nothing else of it is live across the barriers.
+__device__ __forceinline__ int plan_compact(PlanRecord* s_rec, int* s_cnt, const bb_greedy_weights& w,
+                                            const Ply1& p1, int wave, int cell) {
+  const uint64_t open_mask = __ballot(p1.open);
+  if (wave < kHand && cell == 0) s_cnt[wave] = __popcll(open_mask);
+  __syncthreads();
+  const int c0 = s_cnt[0], c1 = s_cnt[1], c2 = s_cnt[2];
+  const int total = __builtin_amdgcn_readfirstlane(c0 + c1 + c2);  // <= 192
+  if (p1.open) {
+    const int before = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(open_mask >> 32),
+                                                      __builtin_amdgcn_mbcnt_lo((uint32_t)open_mask, 0u));
+    const int slot = (wave > 0 ? c0 : 0) + (wave > 1 ? c1 : 0) + before;  // < total <= kPlanRecords
+    s_rec[slot] = PlanRecord{p1.a.board, move_terms(w, p1.a), p1.a.combo1, wave * 64 + cell};
+  }
+  __syncthreads();
+  return total;
+}
+
+// Plies 2 and 3 below one record, by one wave: the record is wave-uniform (read back through readfirstlane into
+// scalar registers); for each slot still unused, lane = ply-2 cell, and ply 3 is the per-lane loop.  Every leaf
+// goes into the lane's (best, best_key, leaves).  kPerFirstMove = false (plan_kernel): the key carries a1,
+// key = a1 << 16 | a2 << 8 | a3, and `alive` is not touched.  true (plan_values_kernel): key = a2 << 8 | a3, and
+// `alive` is set by a leaf that is not dead.  Returns a1, the record's action (< 192).
+template <bool kPerFirstMove>
+__device__ __forceinline__ int plan_record_turn(const LookTable& t, const PlanRecord& rec, uint32_t hand,
+                                                const bb_greedy_weights& w, int depth, int cell, int64_t& best,
+                                                uint32_t& best_key, int& leaves, bool& alive) {
+  const uint64_t B1 = uniform64(rec.board);
+  const int64_t sum1 = (int64_t)uniform64((uint64_t)rec.sum);
+  const int combo1 = (int)uniform32((uint32_t)rec.combo);
+  const int act1 = (int)uniform32((uint32_t)rec.action);
+  const uint32_t hand1 = hand_use(hand, act1 >> 6);
+#pragma unroll 1
+  for (int q = 0; q < kHand; ++q) {
+    if ((hand_used(hand1) >> q) & 1u) continue;  // wave-uniform
+    const After a2 = eval_action(t, B1, hand1, combo1, q, cell);
+    const bool end2 = depth == 2 || a2.refill || a2.dead;
+    const int64_t sum2 = sum1 + move_terms(w, a2);
+    const uint32_t key2 = (kPerFirstMove ? 0u : (uint32_t)act1 << 16) | ((uint32_t)(q * 64 + cell) << 8);
+    if (a2.legal && end2) {
+      take_plan(best, best_key, sum2 + state_terms(w, a2), key2 | 0xFFu);
+      ++leaves;
+      if (kPerFirstMove) alive |= !a2.dead;
+    }
+    // ply 3.  An unfinished ply-2 afterstate means the hand was whole: one slot is left, its piece fits
+    // somewhere and placing it ends the sequence (refill, never dead).  Each such lane walks the set bits of its
+    // own ply-3 anchor mask; the lanes' trip counts differ, the bound is the 64 bits.
+    if (a2.legal && !end2) {
+      const uint32_t hand2 = hand_use(hand1, q);
+      const int q3 = __ffs((int)(~hand_used(hand2) & 7u)) - 1;  // wave-uniform; >= 0 here
+      const uint32_t id3 = hand_id(hand2, q3);
+      uint64_t m3 = anchors_of(t.row[id3 < (uint32_t)kPieces ? id3 : 0u], a2.board);  // != 0: not dead
+      if (kPerFirstMove) alive = true;
+      for (int it = 0; it < 64 && m3 != 0ull; ++it) {
+        const int c3 = __ffsll((unsigned long long)m3) - 1;
+        m3 &= m3 - 1ull;
+        const After a3 = eval_action(t, a2.board, hand2, a2.combo1, q3, c3);  // legal by construction
+        take_plan(best, best_key, sum2 + move_terms(w, a3) + state_terms(w, a3), key2 | (uint32_t)(q3 * 64 + c3));
+        ++leaves;
+      }
+    }
+  }
+  return act1;
+}
+
+// the wave's lanes joined: every lane ends with the wave's best (value, key) and its leaf count
+__device__ __forceinline__ void plan_wave_join(int64_t& best, uint32_t& best_key, int& leaves) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    const int64_t v2 = __shfl_xor(best, d, 64);
+    const uint32_t k2 = (uint32_t)__shfl_xor((int)best_key, d, 64);
+    take_plan(best, best_key, v2, k2);
+    leaves += __shfl_xor(leaves, d, 64);
+  }
+}
+
 __global__ void __launch_bounds__(kPlanBlock)
 plan_kernel(LookTable t, LookPos pos, int n, bb_greedy_weights w, int depth, bb_plan_out out) {
   __shared__ PlanRecord s_rec[kPlanRecords];
@@ -186,84 +294,27 @@ plan_kernel(LookTable t, LookPos pos, int n, bb_greedy_weights w, int depth, bb_
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int cell = (int)(threadIdx.x & 63u);
   for (int64_t i = blockIdx.x; i < (int64_t)n; i += gridDim.x) {
-    const uint64_t B = uniform64(pos.board[i]);
-    const uint32_t hand = uniform32(pos.hand[i]);
-    const int combo = (int)uniform32(pos.combo ? (uint32_t)pos.combo[i] : 0u);
+    const Position P = load_position(pos, i);
     int64_t best = INT64_MIN;  // below every legal value (see greedy_kernel)
     uint32_t best_key = kPlanNoKey;
     int leaves = 0;
+    bool unused = false;  // `alive` is plan_values_kernel's
 
-    // ---- ply 1
-    bool open1 = false;  // legal and not the end of its sequence
-    After a1;
-    if (wave < kHand) {
-      a1 = eval_action(t, B, hand, combo, wave, cell);
-      const bool end1 = depth == 1 || a1.refill || a1.dead;
-      open1 = a1.legal && !end1;
-      if (a1.legal && end1) {
-        best = move_terms(w, a1) + state_terms(w, a1);
-        best_key = ((uint32_t)(wave * 64 + cell) << 16) | 0xFFFFu;
-        leaves = 1;
-      }
+    // ---- ply 1: a closed lane scores itself, then the open ones are compacted
+    const Ply1 ply1 = plan_ply1(t, P, depth, wave, cell);
+    if (ply1.closed) {
+      best = move_terms(w, ply1.a) + state_terms(w, ply1.a);
+      best_key = ((uint32_t)(wave * 64 + cell) << 16) | 0xFFFFu;
+      leaves = 1;
     }
-    const uint64_t open1_mask = __ballot(open1);
-    if (wave < kHand && cell == 0) s_cnt[wave] = __popcll(open1_mask);
-    __syncthreads();
-    const int c0 = s_cnt[0], c1 = s_cnt[1], c2 = s_cnt[2];
-    const int total = __builtin_amdgcn_readfirstlane(c0 + c1 + c2);  // <= 192
-    if (open1) {
-      const int before = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(open1_mask >> 32),
-                                                        __builtin_amdgcn_mbcnt_lo((uint32_t)open1_mask, 0u));
-      const int slot = (wave > 0 ? c0 : 0) + (wave > 1 ? c1 : 0) + before;  // < total <= kPlanRecords
-      s_rec[slot] = PlanRecord{a1.board, move_terms(w, a1), a1.combo1, wave * 64 + cell};
-    }
-    __syncthreads();
+    const int total = plan_compact(s_rec, s_cnt, w, ply1, wave, cell);
 
-    // ---- ply 2 (and 3): one record per wave and turn
-    for (int r = wave; r < total; r += kPlanWaves) {
-      const uint64_t B1 = uniform64(s_rec[r].board);
-      const int64_t sum1 = (int64_t)uniform64((uint64_t)s_rec[r].sum);
-      const int combo1 = (int)uniform32((uint32_t)s_rec[r].combo);
-      const int act1 = (int)uniform32((uint32_t)s_rec[r].action);
-      const uint32_t hand1 = hand_use(hand, act1 >> 6);
-#pragma unroll 1
-      for (int q = 0; q < kHand; ++q) {
-        if ((hand_used(hand1) >> q) & 1u) continue;  // wave-uniform
-        const After a2 = eval_action(t, B1, hand1, combo1, q, cell);
-        const bool end2 = depth == 2 || a2.refill || a2.dead;
-        const int64_t sum2 = sum1 + move_terms(w, a2);
-        const uint32_t key2 = ((uint32_t)act1 << 16) | ((uint32_t)(q * 64 + cell) << 8);
-        if (a2.legal && end2) {
-          take_plan(best, best_key, sum2 + state_terms(w, a2), key2 | 0xFFu);
-          ++leaves;
-        }
-        // ply 3.  An unfinished ply-2 afterstate means the hand was whole: one slot is left, its piece fits
-        // somewhere and placing it ends the sequence (refill).  Each such lane walks the set bits of its own
-        // ply-3 anchor mask; the lanes' trip counts differ, the bound is the 64 bits.
-        if (a2.legal && !end2) {
-          const uint32_t hand2 = hand_use(hand1, q);
-          const int q3 = __ffs((int)(~hand_used(hand2) & 7u)) - 1;  // wave-uniform; >= 0 here
-          const uint32_t id3 = hand_id(hand2, q3);
-          uint64_t m3 = anchors_of(t.row[id3 < (uint32_t)kPieces ? id3 : 0u], a2.board);  // != 0: not dead
-          for (int it = 0; it < 64 && m3 != 0ull; ++it) {
-            const int c3 = __ffsll((unsigned long long)m3) - 1;
-            m3 &= m3 - 1ull;
-            const After a3 = eval_action(t, a2.board, hand2, a2.combo1, q3, c3);  // legal by construction
-            take_plan(best, best_key, sum2 + move_terms(w, a3) + state_terms(w, a3), key2 | (uint32_t)(q3 * 64 + c3));
-            ++leaves;
-          }
-        }
-      }
-    }
+    // ---- ply 2 (and 3): one record per wave and turn, the accumulators kept across the records
+    for (int r = wave; r < total; r += kPlanWaves)
+      plan_record_turn<false>(t, s_rec[r], P.hand, w, depth, cell, best, best_key, leaves, unused);
 
     // ---- join the lanes, then the waves
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-      const int64_t v2 = __shfl_xor(best, d, 64);
-      const uint32_t k2 = (uint32_t)__shfl_xor((int)best_key, d, 64);
-      take_plan(best, best_key, v2, k2);
-      leaves += __shfl_xor(leaves, d, 64);
-    }
+    plan_wave_join(best, best_key, leaves);
     if (cell == 0) {
       s_v[wave] = best;
       s_key[wave] = best_key;
@@ -295,13 +346,12 @@ plan_kernel(LookTable t, LookPos pos, int n, bb_greedy_weights w, int depth, bb_
 // ---------------------------------------------------------------------------
 // Per-action full-hand values (bbvec.h bb_plan_values): plan_kernel's search with the maximum kept per first move.
 //
-// Same layout as plan_kernel: one workgroup of four waves per position, ply 1 compacted into the LDS record
-// list, one record per wave and turn at ply 2, the per-lane loop at ply 3.  A record is one first move, so the
-// best (value, key16 = a2 << 8 | a3), the leaf count and "some leaf is not dead" start fresh with every record
-// and are joined across the wave (shuffles, one ballot) at the end of the record's turn.  Results are staged in
-// LDS arrays indexed by action: a ply-1 lane fills its own action's entry when the action is illegal or ends its
-// sequence there, lane 0 of the owning wave fills an open record's.  After one barrier threads 0..191 store the
-// rows, 64 consecutive elements per wave and output, and waves 0..2 make the three safe words by ballot.
+// Same layout and the same search body as plan_kernel.  A record is one first move, so the best (value,
+// key16 = a2 << 8 | a3), the leaf count and "some leaf is not dead" start fresh with every record and are joined
+// across the wave (shuffles, one ballot) at the end of the record's turn.  Results are staged in LDS arrays
+// indexed by action: a ply-1 lane fills its own action's entry when the action is illegal or ends its sequence
+// there, lane 0 of the owning wave fills an open record's.  After one barrier threads 0..191 store the rows, 64
+// consecutive elements per wave and output, and waves 0..2 make the three safe words by ballot.
 //
 // Unlike plan_kernel this one needs a barrier at the end of a position: the next position's ply-1 lanes write
 // the staging arrays as their first act, while slower waves may still be reading them for the stores.
@@ -319,86 +369,30 @@ plan_values_kernel(LookTable t, LookPos pos, int n, bb_greedy_weights w, int dep
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int cell = (int)(threadIdx.x & 63u);
   for (int64_t i = blockIdx.x; i < (int64_t)n; i += gridDim.x) {
-    const uint64_t B = uniform64(pos.board[i]);
-    const uint32_t hand = uniform32(pos.hand[i]);
-    const int combo = (int)uniform32(pos.combo ? (uint32_t)pos.combo[i] : 0u);
+    const Position P = load_position(pos, i);
 
-    // ---- ply 1: threadIdx.x is the action of waves 0..2
-    bool open1 = false;  // legal and not the end of its sequence
-    After a1;
-    if (wave < kHand) {
-      a1 = eval_action(t, B, hand, combo, wave, cell);
-      const bool end1 = depth == 1 || a1.refill || a1.dead;
-      open1 = a1.legal && !end1;
-      if (!open1) {  // illegal, or a sequence of one move
-        s_q[threadIdx.x] = a1.legal ? move_terms(w, a1) + state_terms(w, a1) : INT64_MIN;
-        s_rest[threadIdx.x] = a1.legal ? (int32_t)kRestNone : -1;
-        s_leaves[threadIdx.x] = a1.legal ? 1 : 0;
-        s_safe[threadIdx.x] = (uint8_t)(a1.legal && !a1.dead);
-      }
+    // ---- ply 1: threadIdx.x is the action of waves 0..2.  A lane that is not open (illegal, or a sequence of
+    // one move) fills its staging entry, then the open ones are compacted
+    const Ply1 ply1 = plan_ply1(t, P, depth, wave, cell);
+    if (wave < kHand && !ply1.open) {
+      s_q[threadIdx.x] = ply1.closed ? move_terms(w, ply1.a) + state_terms(w, ply1.a) : INT64_MIN;
+      s_rest[threadIdx.x] = ply1.closed ? (int32_t)kRestNone : -1;
+      s_leaves[threadIdx.x] = ply1.closed ? 1 : 0;
+      s_safe[threadIdx.x] = (uint8_t)(ply1.closed && !ply1.a.dead);
     }
-    const uint64_t open1_mask = __ballot(open1);
-    if (wave < kHand && cell == 0) s_cnt[wave] = __popcll(open1_mask);
-    __syncthreads();
-    const int c0 = s_cnt[0], c1 = s_cnt[1], c2 = s_cnt[2];
-    const int total = __builtin_amdgcn_readfirstlane(c0 + c1 + c2);  // <= 192
-    if (open1) {
-      const int before = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(open1_mask >> 32),
-                                                        __builtin_amdgcn_mbcnt_lo((uint32_t)open1_mask, 0u));
-      const int slot = (wave > 0 ? c0 : 0) + (wave > 1 ? c1 : 0) + before;  // < total <= kPlanRecords
-      s_rec[slot] = PlanRecord{a1.board, move_terms(w, a1), a1.combo1, wave * 64 + cell};
-    }
-    __syncthreads();
+    const int total = plan_compact(s_rec, s_cnt, w, ply1, wave, cell);
 
-    // ---- ply 2 (and 3): one record = one first move per wave and turn
+    // ---- ply 2 (and 3): one record = one first move per wave and turn, the accumulators fresh for each
     for (int r = wave; r < total; r += kPlanWaves) {
-      const uint64_t B1 = uniform64(s_rec[r].board);
-      const int64_t sum1 = (int64_t)uniform64((uint64_t)s_rec[r].sum);
-      const int combo1 = (int)uniform32((uint32_t)s_rec[r].combo);
-      const int act1 = (int)uniform32((uint32_t)s_rec[r].action);  // < 192: an index of the staging arrays
-      const uint32_t hand1 = hand_use(hand, act1 >> 6);
       int64_t best = INT64_MIN;  // below every legal value (see greedy_kernel)
       uint32_t best_key = kPlanNoKey;
       int leaves = 0;
       bool alive = false;  // a leaf with dead == 0
-#pragma unroll 1
-      for (int q = 0; q < kHand; ++q) {
-        if ((hand_used(hand1) >> q) & 1u) continue;  // wave-uniform
-        const After a2 = eval_action(t, B1, hand1, combo1, q, cell);
-        const bool end2 = depth == 2 || a2.refill || a2.dead;
-        const int64_t sum2 = sum1 + move_terms(w, a2);
-        const uint32_t key2 = (uint32_t)(q * 64 + cell) << 8;
-        if (a2.legal && end2) {
-          take_plan(best, best_key, sum2 + state_terms(w, a2), key2 | 0xFFu);
-          ++leaves;
-          alive |= !a2.dead;
-        }
-        // ply 3, as in plan_kernel: the last piece fits somewhere and placing it is a refill, never dead
-        if (a2.legal && !end2) {
-          const uint32_t hand2 = hand_use(hand1, q);
-          const int q3 = __ffs((int)(~hand_used(hand2) & 7u)) - 1;  // wave-uniform; >= 0 here
-          const uint32_t id3 = hand_id(hand2, q3);
-          uint64_t m3 = anchors_of(t.row[id3 < (uint32_t)kPieces ? id3 : 0u], a2.board);  // != 0: not dead
-          alive = true;
-          for (int it = 0; it < 64 && m3 != 0ull; ++it) {
-            const int c3 = __ffsll((unsigned long long)m3) - 1;
-            m3 &= m3 - 1ull;
-            const After a3 = eval_action(t, a2.board, hand2, a2.combo1, q3, c3);  // legal by construction
-            take_plan(best, best_key, sum2 + move_terms(w, a3) + state_terms(w, a3), key2 | (uint32_t)(q3 * 64 + c3));
-            ++leaves;
-          }
-        }
-      }
-      // the record's turn ends: join the lanes (the whole wave is here, the loops above are wave-uniform)
-#pragma unroll
-      for (int d = 32; d >= 1; d >>= 1) {
-        const int64_t v2 = __shfl_xor(best, d, 64);
-        const uint32_t k2 = (uint32_t)__shfl_xor((int)best_key, d, 64);
-        take_plan(best, best_key, v2, k2);
-        leaves += __shfl_xor(leaves, d, 64);
-      }
+      const int act1 = plan_record_turn<true>(t, s_rec[r], P.hand, w, depth, cell, best, best_key, leaves, alive);
+      // the record's turn ends: join the lanes (the whole wave is here, the loops of the turn are wave-uniform)
+      plan_wave_join(best, best_key, leaves);
       const bool any_alive = __ballot(alive) != 0ull;
-      if (cell == 0) {  // an open record has a leaf: its afterstate is not dead
+      if (cell == 0) {  // an open record has a leaf: its afterstate is not dead.  act1 indexes the staging arrays
         s_q[act1] = best;
         s_rest[act1] = (int32_t)(((best_key >> 8) & 0xFFu) | ((best_key & 0xFFu) << 8));
         s_leaves[act1] = leaves;
@@ -431,6 +425,7 @@ const LookTable& look_table() {
 }
 
 inline dim3 look_grid(int n) { return dim3((unsigned)((int64_t)n < kLookMaxGrid ? (int64_t)n : kLookMaxGrid)); }
+inline dim3 plan_grid(int n) { return dim3((unsigned)((int64_t)n < kPlanMaxGrid ? (int64_t)n : kPlanMaxGrid)); }
 
 }  // namespace
 
@@ -452,18 +447,16 @@ hipError_t launch_greedy(const uint64_t* board, const uint32_t* hand, const int3
 hipError_t launch_plan(const uint64_t* board, const uint32_t* hand, const int32_t* combo, int n,
                        const bb_greedy_weights& w, int depth, const bb_plan_out& out, hipStream_t s) {
   const LookPos pos{board, hand, combo, nullptr};
-  const dim3 grid((unsigned)((int64_t)n < kPlanMaxGrid ? (int64_t)n : kPlanMaxGrid));
-  hipLaunchKernelGGL(plan_kernel, grid, dim3(kPlanBlock), 0, s, look_table(), pos, n, w, depth, out);
+  hipLaunchKernelGGL(plan_kernel, plan_grid(n), dim3(kPlanBlock), 0, s, look_table(), pos, n, w, depth, out);
   return hipGetLastError();
 }
 
 hipError_t launch_plan_values(const uint64_t* board, const uint32_t* hand, const int32_t* combo, int n,
                               const bb_greedy_weights& w, int depth, const bb_plan_values_out& out, hipStream_t s) {
   const LookPos pos{board, hand, combo, nullptr};
-  const dim3 grid((unsigned)((int64_t)n < kPlanMaxGrid ? (int64_t)n : kPlanMaxGrid));
   // the safe set of depth 3 is that of depth 2 (bbvec.h): asked for alone, the third ply is not searched
   if (depth == 3 && !out.q && !out.rest && !out.leaves) depth = 2;
-  hipLaunchKernelGGL(plan_values_kernel, grid, dim3(kPlanBlock), 0, s, look_table(), pos, n, w, depth, out);
+  hipLaunchKernelGGL(plan_values_kernel, plan_grid(n), dim3(kPlanBlock), 0, s, look_table(), pos, n, w, depth, out);
   return hipGetLastError();
 }
 

@@ -10,7 +10,7 @@ from .lib import HOST_LIB_PATH, LIB_PATH, PKG_DIR, REPO_DIR
 
 CSRC = os.path.join(PKG_DIR, "csrc")
 SOURCES = ["bb_env.hip", "bb_lookahead.hip", "bb_ppo.hip", "bb_nn.hip", "bb_loss.hip", "bb_conv.hip", "bb_conv32.hip", "bb_optim.hip", "bb_capi.cpp", "bb_tables.cpp"]
-HEADERS = ["bb_device.h", "bb_rules.h", "bb_solver.h", "bb_env_internal.h", "bb_seed.h"]
+HEADERS = ["bb_device.h", "bb_rules.h", "bb_look_rules.h", "bb_solver.h", "bb_env_internal.h", "bb_seed.h"]
 ARCH = os.environ.get("BB_OFFLOAD_ARCH", "gfx950")
 
 HIPCC_FLAGS = [
@@ -91,7 +91,7 @@ def build_lib(force: bool = False, verbose: bool = True) -> str:
 
 # the host backend of the env entry points (csrc/bb_host.cpp): plain C++, OpenMP over envs
 HOST_SOURCES = ["bb_host.cpp"]
-HOST_HEADERS = ["bb_rules.h", "bb_seed.h"]
+HOST_HEADERS = ["bb_rules.h", "bb_look_rules.h", "bb_seed.h"]
 HOST_FLAGS = ["-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-fopenmp", "-Wall", "-Wextra"]
 
 

@@ -257,10 +257,12 @@ class DeviceEnvBatch:
         """bb_greedy_actions on the live state: out (int32 [N]) receives every env's best legal action under
         the one-ply greedy value of ``weights`` (a dict of bb_greedy_weights fields or an L.GreedyWeights), ties
         to the lowest action, 0 where nothing is legal; value (int64 [N], optional) that value."""
+        from . import kernels as K
+
         n = self.num_envs
         for t, dt in ((out, torch.int32), (value, torch.int64)):
             assert t is None or (t.dtype == dt and t.device == self.device and t.is_contiguous() and t.numel() == n)
-        w = weights if isinstance(weights, L.GreedyWeights) else L.greedy_weights(weights)
+        w = K._weights(weights)
         L.check(self.lib.bb_greedy_actions(self.handle, C.byref(w), _ptr(out), _ptr(value), _stream(self.device)),
                 "bb_greedy_actions", self.handle, self.lib)
         return out
@@ -274,7 +276,7 @@ class DeviceEnvBatch:
         from . import kernels as K
 
         o = K._plan_out({"action": out, "value": value, "plan": plan, "leaves": leaves}, self.num_envs, self.device)
-        w = weights if isinstance(weights, L.GreedyWeights) else L.greedy_weights(weights)
+        w = K._weights(weights)
         L.check(self.lib.bb_plan_actions(self.handle, C.byref(w), int(depth), C.byref(o), _stream(self.device)),
                 "bb_plan_actions", self.handle, self.lib)
         return out
@@ -288,7 +290,7 @@ class DeviceEnvBatch:
 
         out = K.plan_value_outputs(self.num_envs, self.device) if out is None else out
         o = K._plan_values_out(out, self.num_envs, self.device)
-        w = weights if isinstance(weights, L.GreedyWeights) else L.greedy_weights(weights)
+        w = K._weights(weights)
         L.check(self.lib.bb_plan_values(self.handle, C.byref(w), int(depth), C.byref(o), _stream(self.device)),
                 "bb_plan_values", self.handle, self.lib)
         return out

@@ -168,16 +168,37 @@ def afterstate_outputs(n: int, dev, want=("board", "reward", "score_gained", "au
     return {k: torch.empty((n, 192), dtype=AFTERSTATE_DTYPES[k], device=dev) for k in want}
 
 
-def _afterstate_out(out: dict, n: int, dev) -> L.AfterstateOut:
-    o = L.AfterstateOut()
-    for k, field in (("board", "board"), ("reward", "reward_f64"), ("score_gained", "score_gained"), ("aux", "aux")):
-        t = out.get(k)
+def _look_out(cls, call: str, table: dict, tensors: dict, n: int, dev, shape: str = "[{n}, {width}]",
+              required=(), at_least_one: bool = False, known_only: bool = False):
+    """The ctypes output struct ``cls`` of a lookahead call from a dict of tensors (missing or None = NULL).
+    ``table``: {key: (field, dtype, width)}, a key's tensor holding n * width elements (``shape`` words that in the
+    error text); ``required`` keys must be there, ``at_least_one`` asks for any, ``known_only`` refuses other keys."""
+    o = cls()
+    if known_only and set(tensors) - set(table):
+        raise L.BBNativeError(f"{call}: unknown outputs {sorted(set(tensors) - set(table))}")
+    for k, (field, dt, width) in table.items():
+        t = tensors.get(k)
         if t is None:
+            if k in required:
+                raise L.BBNativeError(f"{call}: the {k} output is required")
             continue
-        if not (t.dtype == AFTERSTATE_DTYPES[k] and t.device == dev and t.is_contiguous() and t.numel() == n * 192):
-            raise L.BBNativeError(f"afterstates: {k} must be a contiguous {AFTERSTATE_DTYPES[k]} [{n}, 192] on {dev}")
+        if not (t.dtype == dt and t.device == dev and t.is_contiguous() and t.numel() == n * width):
+            what = shape.format(n=n, width=width, numel=n * width)
+            raise L.BBNativeError(f"{call}: {k} must be a contiguous {dt} {what} on {dev}")
         setattr(o, field, t.data_ptr())
+    if at_least_one and all(tensors.get(k) is None for k in table):
+        raise L.BBNativeError(f"{call}: at least one of {', '.join(table)} is required")
     return o
+
+
+def _weights(w) -> "L.GreedyWeights":
+    """bb_greedy_weights from a dict of its fields, or the struct itself."""
+    return w if isinstance(w, L.GreedyWeights) else L.greedy_weights(w)
+
+
+def _afterstate_out(out: dict, n: int, dev) -> L.AfterstateOut:
+    table = {k: ("reward_f64" if k == "reward" else k, dt, 192) for k, dt in AFTERSTATE_DTYPES.items()}
+    return _look_out(L.AfterstateOut, "afterstates", table, out, n, dev)
 
 
 def afterstates(board: torch.Tensor, hand: torch.Tensor, combo: Optional[torch.Tensor] = None,
@@ -209,7 +230,7 @@ def greedy_actions(board: torch.Tensor, hand: torch.Tensor, weights, combo: Opti
     lowest action; no legal action: 0 and INT64_MIN), fused.  weights: a dict of bb_greedy_weights fields or an
     ``L.GreedyWeights``.  Returns (action int32 [n], value int64 [n] or None)."""
     pos, n, dev = _positions(board, hand, combo, None)
-    w = weights if isinstance(weights, L.GreedyWeights) else L.greedy_weights(weights)
+    w = _weights(weights)
     action = torch.empty(n, dtype=torch.int32, device=dev) if action is None else action
     if value is None and want_value:
         value = torch.empty(n, dtype=torch.int64, device=dev)
@@ -228,17 +249,9 @@ PLAN_OUTPUTS = {"action": (torch.int32, 1), "value": (torch.int64, 1), "plan": (
 
 def _plan_out(tensors: dict, n: int, dev) -> L.PlanOut:
     """bb_plan_out from {"action", "value", "plan", "leaves"} tensors (None = NULL; action is required)."""
-    o = L.PlanOut()
-    for k, (dt, width) in PLAN_OUTPUTS.items():
-        t = tensors.get(k)
-        if t is None:
-            if k == "action":
-                raise L.BBNativeError("plan_actions: the action output is required")
-            continue
-        if not (t.dtype == dt and t.device == dev and t.is_contiguous() and t.numel() == n * width):
-            raise L.BBNativeError(f"plan_actions: {k} must be a contiguous {dt} tensor of {n * width} elements on {dev}")
-        setattr(o, k, t.data_ptr())
-    return o
+    table = {k: (k, dt, width) for k, (dt, width) in PLAN_OUTPUTS.items()}
+    return _look_out(L.PlanOut, "plan_actions", table, tensors, n, dev, shape="tensor of {numel} elements",
+                     required=("action",))
 
 
 def plan_actions(board: torch.Tensor, hand: torch.Tensor, weights, depth: int = 3,
@@ -253,7 +266,7 @@ def plan_actions(board: torch.Tensor, hand: torch.Tensor, weights, depth: int = 
     legal action), and when asked for or passed in "value" int64 [n] (INT64_MIN without a legal action), "plan"
     int32 [n, 3] (-1 for plies not played) and "leaves" int32 [n] (the number of maximal sequences)."""
     pos, n, dev = _positions(board, hand, combo, None)
-    w = weights if isinstance(weights, L.GreedyWeights) else L.greedy_weights(weights)
+    w = _weights(weights)
     res = {"action": torch.empty(n, dtype=torch.int32, device=dev) if action is None else action}
     for k, given, want in (("value", value, want_value), ("plan", plan, want_plan), ("leaves", leaves, want_leaves)):
         if given is not None:
@@ -282,20 +295,8 @@ def plan_value_outputs(n: int, dev, want=("q", "rest", "leaves", "safe")) -> dic
 
 def _plan_values_out(out: dict, n: int, dev) -> L.PlanValuesOut:
     """bb_plan_values_out from a dict with any of "q", "rest", "leaves", "safe" (missing or None = NULL)."""
-    o = L.PlanValuesOut()
-    unknown = set(out) - set(PLAN_VALUE_OUTPUTS)
-    if unknown:
-        raise L.BBNativeError(f"plan_values: unknown outputs {sorted(unknown)}")
-    for k, (dt, width) in PLAN_VALUE_OUTPUTS.items():
-        t = out.get(k)
-        if t is None:
-            continue
-        if not (t.dtype == dt and t.device == dev and t.is_contiguous() and t.numel() == n * width):
-            raise L.BBNativeError(f"plan_values: {k} must be a contiguous {dt} [{n}, {width}] on {dev}")
-        setattr(o, k, t.data_ptr())
-    if not any(out.get(k) is not None for k in PLAN_VALUE_OUTPUTS):
-        raise L.BBNativeError("plan_values: at least one of q, rest, leaves, safe is required")
-    return o
+    table = {k: (k, dt, width) for k, (dt, width) in PLAN_VALUE_OUTPUTS.items()}
+    return _look_out(L.PlanValuesOut, "plan_values", table, out, n, dev, at_least_one=True, known_only=True)
 
 
 def plan_values(board: torch.Tensor, hand: torch.Tensor, weights, depth: int = 3,
@@ -309,7 +310,7 @@ def plan_values(board: torch.Tensor, hand: torch.Tensor, weights, depth: int = 3
     of the legal actions after which the rest of the hand can still be placed some way; ``safe`` does not depend
     on the weights.  ``unpack_rest`` / ``mask_bits_to_bool`` decode."""
     pos, n, dev = _positions(board, hand, combo, None)
-    w = weights if isinstance(weights, L.GreedyWeights) else L.greedy_weights(weights)
+    w = _weights(weights)
     out = plan_value_outputs(n, dev, want) if out is None else out
     o = _plan_values_out(out, n, dev)
     lib, stream = _look_lib(dev)

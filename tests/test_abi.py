@@ -161,6 +161,97 @@ def test_argument_structs_are_validated_before_any_hip_call(lib, fn, args, msg):
     assert msg in L.last_error()
 
 
+# The lookahead entry points: the arguments of an accepted call by name (None = NULL; pos / out name the fields of
+# their struct), the order they are passed in, and every refusal rule as (entry point, overrides, the text after
+# "<entry point>: ").  The rules live in csrc/bb_look_rules.h, which both libraries include.
+_POS = dict(board=FAKE, hand=FAKE)
+_LOOK_GOOD = dict(pos=_POS, n=4, cfg=True, w=True, depth=3, d_action=FAKE, d_value=None)
+_LOOK_OUT = {"afterstates": (L.AfterstateOut, dict(board=FAKE)), "greedy_actions": (None, None),
+             "plan_actions": (L.PlanOut, dict(action=FAKE)), "plan_values": (L.PlanValuesOut, dict(safe=FAKE))}
+_LOOK_ARGS = {"afterstates": ("cfg", "out"), "greedy_actions": ("w", "d_action", "d_value"),
+              "plan_actions": ("w", "depth", "out"), "plan_values": ("w", "depth", "out")}
+_NO_POS = [dict(pos=None), dict(pos=dict(board=None, hand=FAKE)), dict(pos=dict(board=FAKE, hand=None))]
+_T_AFTER = "positions (board, hand), n > 0, cfg and out are required"
+_T_GREEDY = "positions (board, hand), n > 0, weights and d_action are required"
+_T_PLAN = "positions (board, hand), n > 0, weights, depth in 1..3 and out->action are required"
+_VALUES_RULES = [(dict(w=None), "weights are NULL"), (dict(out=None), "out is NULL"),
+                 (dict(out={}), "all four outputs are NULL"), (dict(depth=0), "depth must be 1..3"),
+                 (dict(depth=4), "depth must be 1..3")]
+LOOK_POS_REFUSALS = (
+    [("afterstates", kw, _T_AFTER) for kw in _NO_POS + [dict(n=-1), dict(n=0), dict(cfg=None), dict(out=None)]]
+    + [("greedy_actions", kw, _T_GREEDY) for kw in _NO_POS + [dict(n=-1), dict(n=0), dict(w=None), dict(d_action=None)]]
+    + [("plan_actions", kw, _T_PLAN) for kw in _NO_POS + [dict(n=-1), dict(n=0), dict(w=None), dict(out=None),
+                                                          dict(out={}), dict(depth=0), dict(depth=4)]]
+    + [("plan_values", kw, "positions (board, hand) are NULL") for kw in _NO_POS]
+    + [("plan_values", dict(n=-1), "n is negative")] + [("plan_values", kw, msg) for kw, msg in _VALUES_RULES])
+_T_PLAN_ENV = "weights, depth in 1..3 and out->action are required"
+LOOK_ENV_REFUSALS = (
+    [("afterstates", dict(out=None), "out is NULL")]
+    + [("greedy_actions", kw, "weights and d_action are required") for kw in (dict(w=None), dict(d_action=None))]
+    + [("plan_actions", kw, _T_PLAN_ENV) for kw in (dict(w=None), dict(out=None), dict(out={}), dict(depth=0),
+                                                    dict(depth=4))]
+    + [("plan_values", kw, msg) for kw, msg in _VALUES_RULES])
+
+
+def _look_call(lib, family, kw, env_form=False, handle=None):
+    """Call bb_<family>_pos, or bb_<family> with a handle, with the accepted arguments overridden by kw."""
+    from runtime.device_env import DEFAULT_REWARDS
+
+    cls, fields = _LOOK_OUT[family]
+    a = {**_LOOK_GOOD, "out": fields, **kw}
+    keep = {"pos": L.Positions(**a["pos"]) if a["pos"] is not None else None,  # alive until the call returns
+            "cfg": L.reward_cfg(DEFAULT_REWARDS) if a["cfg"] else None,
+            "w": L.greedy_weights({"lines": 1}) if a["w"] else None,
+            "out": cls(**a["out"]) if cls is not None and a["out"] is not None else None}
+    ref = {k: C.byref(v) if v is not None else None for k, v in keep.items()}
+    names = [k for k in _LOOK_ARGS[family] if not (env_form and k == "cfg")]  # a handle carries its reward config
+    rest = [ref[k] if k in ref else a[k] for k in names] + [None]  # stream
+    if env_form:
+        return getattr(lib, f"bb_{family}")(handle, *rest)
+    return getattr(lib, f"bb_{family}_pos")(ref["pos"], a["n"], *rest)
+
+
+def _look_ids(rows):
+    return [f"{i}-{fam}-{'-'.join(f'{k}={v}' for k, v in kw.items())}" for i, (fam, kw, _) in enumerate(rows)]
+
+
+@pytest.mark.parametrize("family,kw,text", LOOK_POS_REFUSALS, ids=_look_ids(LOOK_POS_REFUSALS))
+def test_lookahead_pos_rules_are_one_set_for_both_backends(lib, family, kw, text):
+    """Every refusal rule of the four stateless lookahead entry points: libbbvec.so answers BB_ERR_ARG before any
+    HIP call (so this passes without a GPU), the host library answers the same code, and bb_last_error(NULL) is
+    the same string from both."""
+    want = f"bb_{family}_pos: {text}"
+    for backend in (lib, L.load_host()):
+        assert _look_call(backend, family, kw) == -1  # BB_ERR_ARG
+        assert L.last_error(lib=backend) == want
+
+
+def test_plan_values_pos_alone_accepts_no_positions(lib):
+    """The asymmetry bb_look_rules.h records: n == 0 is refused by three of the _pos forms (rows above) and accepted
+    by bb_plan_values_pos, which then does nothing (no HIP call either)."""
+    for backend in (lib, L.load_host()):
+        assert _look_call(backend, "plan_values", dict(n=0)) == 0
+
+
+@pytest.fixture(scope="module")
+def host_env():
+    from runtime.device_env import DeviceEnvBatch
+
+    env = DeviceEnvBatch(4, [1, 2, 3, 4], autoreset=False, device="cpu")
+    yield env
+    env.close()
+
+
+@pytest.mark.parametrize("family,kw,text", LOOK_ENV_REFUSALS, ids=_look_ids(LOOK_ENV_REFUSALS))
+def test_lookahead_handle_rules_on_the_host_backend(host_env, family, kw, text):
+    """The handle forms' rules, from the same header, on a host env: BB_ERR_ARG with the rule as the handle's error;
+    a NULL handle is a bare BB_ERR_ARG.  (On libbbvec.so a handle needs a device: the GPU tests cover it.)"""
+    host = L.load_host()
+    assert _look_call(host, family, kw, env_form=True, handle=host_env.handle) == -1  # BB_ERR_ARG
+    assert L.last_error(host_env.handle, host) == f"bb_{family}: {text}"
+    assert _look_call(host, family, {}, env_form=True, handle=None) == -1
+
+
 @pytest.mark.parametrize("seed", [0, 1, 42, 43, 2 ** 32 - 1, 2 ** 32, 2 ** 40 + 7, 2 ** 63, 2 ** 64 - 1])
 def test_pcg64_seeding_matches_numpy(lib, seed):
     w = L.pcg64_seed(seed)
