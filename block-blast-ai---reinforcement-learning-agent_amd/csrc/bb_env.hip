@@ -109,12 +109,16 @@ __device__ __forceinline__ uint32_t lower_half_bcast(uint32_t x) {
 }
 
 
+// The three slots' legal anchors, 0 for a used slot.  Without branches: every slot's row is read (the id of a
+// used slot is still a piece id, so the read is in the table) and the used bits select afterwards, so the three
+// rows' LDS reads are issued together and waited for once instead of one round trip per slot.
 __device__ __forceinline__ void masks_of(const Tables& t, uint64_t B, uint32_t hand, uint64_t m[3]) {
   const uint32_t used = hand_used(hand);
+  uint64_t an[3];
 #pragma unroll
-  for (int s = 0; s < 3; ++s) {
-    m[s] = (used >> s) & 1u ? 0ull : anchors_of(t.row[hand_id(hand, s)], B);
-  }
+  for (int s = 0; s < 3; ++s) an[s] = anchors_of(t.row[hand_id(hand, s)], B);
+#pragma unroll
+  for (int s = 0; s < 3; ++s) m[s] = (used >> s) & 1u ? 0ull : an[s];
 }
 
 // Everything the finalisation of one env's step needs.
@@ -192,11 +196,14 @@ __device__ __forceinline__ bool apply_move_bf(const Tables& t, StepCtx& s, int a
   const int p = inrange ? (act >> 6) : 0;
   const int cell = act & 63;
   const uint32_t used0 = hand_used(s.hand);
+  // the row's three fields are read up front, ahead of every test: a field first read behind a short-circuit
+  // && is a load the compiler may not hoist, which put it in an exec-masked region with a wait of its own
   const PieceRow& pr = t.row[hand_id(s.hand, p)];
-  const uint64_t placed = pr.shape << cell;
-  const bool valid = inrange && !hand_over(s.hand) && !((used0 >> p) & 1u) && ((pr.anchors >> cell) & 1ull) &&
-                     (placed & s.B) == 0ull;
+  const uint64_t shape = pr.shape, anchors = pr.anchors;
   const int nblk = (int)ncells_of(pr);
+  const uint64_t placed = shape << cell;
+  const bool valid = (int)inrange & (int)!hand_over(s.hand) & (int)!((used0 >> p) & 1u) &
+                     (int)((anchors >> cell) & 1ull) & (int)((placed & s.B) == 0ull);
   int rows, cols;
   const uint64_t B2 = clear_full(s.B | placed, rows, cols);
   const int lines = rows + cols;
@@ -217,7 +224,8 @@ __device__ __forceinline__ bool apply_move_bf(const Tables& t, StepCtx& s, int a
   const uint32_t used = used0 | (1u << p);
   const bool drew = valid && used == 7u;
   s.drew = drew;
-  s.hand = !valid ? s.hand : (drew ? hand_clear_used(s.hand) : hand_with_used(s.hand, used));
+  // a legal move's hand is not over, so hand_clear_used(h) == hand_with_used(h, 0): one expression, two selects
+  s.hand = valid ? hand_with_used(s.hand, drew ? 0u : used) : s.hand;
   return drew;
 }
 
@@ -908,11 +916,17 @@ __global__ void __launch_bounds__(kABlock, 1) rollout_async_kernel(EnvDev e, con
   __shared__ ARecs arec;
   __shared__ uint32_t astat[kAEnvs];  // 0 idle, 1 posted, 3 claimed, 2 answered
   __shared__ uint32_t afin[kAEW];
+  __shared__ double rhead[kRewardHeads];  // reward_head by reward_head_index(cells, lines)
   const int lane = threadIdx.x & 63;
   const int wv = threadIdx.x >> 6;
   uint32_t* lds = scratch + (threadIdx.x & ~63);
   if (threadIdx.x < kAEnvs) astat[threadIdx.x] = 0u;
   if (threadIdx.x < kAEW) afin[threadIdx.x] = 0u;
+  // the reward's head for every (cell count, lines) of this launch's config (bb_rules.h reward_head): a.cfg is a
+  // kernel argument, so the table is rebuilt by every workgroup of every launch and nothing outlives the launch
+  if (threadIdx.x < kRewardHeads)
+    rhead[threadIdx.x] = reward_head(a.cfg, (int)threadIdx.x / kRewardLines, (int)threadIdx.x % kRewardLines,
+                                     combo_multiplier((int)threadIdx.x % kRewardLines));
   stage_tables<true>(t, g_rows, g_d, jt, a.jump);  // ends with __syncthreads (also orders the inits above)
 
   if (wv >= kAEW) {
@@ -1182,23 +1196,27 @@ __global__ void __launch_bounds__(kABlock, 1) rollout_async_kernel(EnvDev e, con
     // 4. finalize every env whose hand is known: game over, reward, outputs, auto-reset, mask, policy
     const bool fin = live && ph == 2;
     if (fin) {
+      // Up to the stores this is straight-line code for the fin lanes: the three rows' reads (masks_of) come
+      // first, the ten Philox rounds have no memory operand and run while the reads are in flight, and the
+      // invalid action (reward -10, nothing else changes: block_blast_env.py:240-245) is a select, not a region.
+      masks_of(t, s.B, s.hand, m);
+      // an invalid action has nblk = lines = 0: entry 0, in the table like every other
+      const double rew_head = rhead[reward_head_index(s.nblk, s.lines)];
+      BB_ENV_STAMP(4)
 #if !BB_ASYNC_PHILOX_EARLY
-      const uint32_t u_next = policy_uniform(a.policy_seed, a.env_offset + (uint64_t)i, r.policy_step0 + st + 1);
+      uint32_t u_next = policy_uniform(a.policy_seed, a.env_offset + (uint64_t)i, r.policy_step0 + st + 1);
+      // the value's only use is random_policy_u after the reset block, and the compiler sinks the ten rounds to
+      // it; the empty statement takes the value here, so the rounds stay in this block, beside the row reads
+      asm volatile("" : "+v"(u_next));
 #endif
       BB_ENV_STAMP(3)
-      masks_of(t, s.B, s.hand, m);
-      BB_ENV_STAMP(4)
-      double rew = -10.0;  // invalid action (block_blast_env.py:240-245)
-      bool term = false;
-      int holes = 0;
-      if (s.valid) {
-        const bool over = (m[0] | m[1] | m[2]) == 0ull;  // engine.py:440-441
-        if (over) s.hand = hand_set_over(s.hand);
-        int center;
-        rew = move_reward(s, a, over, holes, center);
-        s.prev = (uint32_t)(holes | (center << 8));
-        term = over;
-      }
+      const bool over = (m[0] | m[1] | m[2]) == 0ull;  // engine.py:440-441
+      const int holes = count_holes(s.B), center = __popcll(s.B & kCenter);
+      const double rew_move = reward_tail(a.cfg, a.center_tenth, rew_head, over, holes, center, s.prev);
+      const double rew = s.valid ? rew_move : -10.0;
+      const bool term = s.valid && over;
+      s.hand = term ? hand_set_over(s.hand) : s.hand;
+      s.prev = s.valid ? (uint32_t)(holes | (center << 8)) : s.prev;
       BB_ENV_STAMP(5)
       const size_t o = (size_t)st * N + (size_t)i;
       r.reward[o] = (float)rew;

@@ -82,30 +82,56 @@ BB_RULE int combo_after(int lines, int combo) { return lines > 0 ? combo_next(co
 BB_RULE int64_t score_gained(int ncells, int lines, int combo1) {
   const int cm = line_cap(lines);
   const int streak = combo1 + 1 < 8 ? combo1 + 1 : 8;  // post-increment combo (engine.py:261)
-  // blocks_in_lines = lines * 8 (engine.py:427)
-  return lines > 0 ? ncells + (int64_t)(lines * 8 * 10) * cm * streak : (int64_t)ncells;
+  // blocks_in_lines = lines * 8 (engine.py:427).  No select: without a clear the product is 0 by its factor
+  // `lines`, and with at most 16 lines, cm <= 4 and streak <= 8 it fits 32 bits (a 64-bit product made the
+  // compiler split the branch-free move into a diamond).
+  return (int64_t)ncells + (int64_t)(lines * 8 * 10 * cm * streak);
 }
 
 // _calculate_reward of a legal move (block_blast_env.py:158-193) in fp64.  The operation order is the
 // contract (it is the reference's, and the results are compared bit for bit); both libraries are built with
 // -ffp-contract=off, so none of these pairs is fused.  center_tenth = cfg.center_bonus * 0.1; holes / centre
 // are the post-move hole and filled-centre counts, prev the pre-move ones (_prev_holes | centre << 8).
-BB_RULE double move_reward(const bb_reward_cfg& cfg, double center_tenth, int ncells, int lines, int cm, bool over,
-                           int holes, int centre, uint32_t prev) {
+// Select-only like score_gained, so that the rollout kernel's finalize stays one basic block: every term is
+// computed, and a conditional step commits as R = cond ? R + term : R.  The sum is selected, never a zero
+// addend, so a step that is taken performs exactly the reference's addition and one that is not leaves R's bits
+// alone (R + 0.0 would turn -0.0 into +0.0).
+//
+// In two parts.  The head runs up to and including the combo bonus and depends only on the config, the piece's
+// cell count (0..9) and the lines cleared (0..6, cm = combo_multiplier(lines)): kRewardHeads values per config,
+// which the rollout kernel tabulates once per launch with this same function.  The tail adds the rest to it.
+constexpr int kRewardLines = 7, kRewardHeads = 10 * kRewardLines;
+BB_RULE int reward_head_index(int ncells, int lines) { return ncells * kRewardLines + lines; }
+
+BB_RULE double reward_head(const bb_reward_cfg& cfg, int ncells, int lines, int cm) {
   double R = 0.0;
   R += (double)ncells * cfg.block_placed;
   R += cfg.survival_bonus;
-  if (lines > 0) {
-    double lr = (double)lines * cfg.line_clear_base;
-    lr *= (double)cm;
-    R += lr;
-    if (cm > 1) R += (double)(cm - 1) * cfg.combo_multiplier_bonus;
-  }
-  if (over) R += cfg.game_over_penalty;
-  const int dh = holes - (int)(prev & 0xFFu);
-  if (dh > 0) R += (double)dh * cfg.hole_penalty;
-  if (centre <= (int)(prev >> 8)) R += center_tenth;  // openness >= previous
+  const bool cleared = lines > 0;
+  double lr = (double)lines * cfg.line_clear_base;
+  lr *= (double)cm;
+  const double r_lines = R + lr;
+  R = cleared ? r_lines : R;
+  const double r_combo = R + (double)(cm - 1) * cfg.combo_multiplier_bonus;
+  R = cleared && cm > 1 ? r_combo : R;
   return R;
+}
+
+BB_RULE double reward_tail(const bb_reward_cfg& cfg, double center_tenth, double R, bool over, int holes, int centre,
+                           uint32_t prev) {
+  const double r_over = R + cfg.game_over_penalty;
+  R = over ? r_over : R;
+  const int dh = holes - (int)(prev & 0xFFu);
+  const double r_holes = R + (double)dh * cfg.hole_penalty;
+  R = dh > 0 ? r_holes : R;
+  const double r_centre = R + center_tenth;
+  R = centre <= (int)(prev >> 8) ? r_centre : R;  // openness >= previous
+  return R;
+}
+
+BB_RULE double move_reward(const bb_reward_cfg& cfg, double center_tenth, int ncells, int lines, int cm, bool over,
+                           int holes, int centre, uint32_t prev) {
+  return reward_tail(cfg, center_tenth, reward_head(cfg, ncells, lines, cm), over, holes, centre, prev);
 }
 
 // --------------------------------------------------------------------------
