@@ -181,17 +181,20 @@ __device__ __forceinline__ int pair_quick(uint64_t B1, const PieceRow& pb, const
   return 2;
 }
 
-// pair_quick without branches: 0 reject, 1 accept, 2 undecided, A2 / A3 out.
+// pair_quick without branches: 0 reject, 1 accept, 2 undecided, A2 / A3 out.  Both shapes are read before
+// anything tests A2 or A3 and the leaves are combined with &, so no table read sits behind a short-circuit
+// (a load the compiler may not hoist: it stayed in an exec-masked region with a wait of its own).
 __device__ __forceinline__ int pair_quick_bf(uint64_t B1, const PieceRow& pb, const PieceRow& pc, uint32_t dbc,
                                              uint64_t& A2, uint64_t& A3) {
+  const uint64_t bshape = pb.shape, cshape = pc.shape;
   A2 = anchors_of(pb, B1);
   A3 = anchors_of(pc, B1);
   const bool dacc = (A2 && (uint32_t)__popcll(A3) > dbc) || (A3 && (uint32_t)__popcll(A2) > dbc);
   const int q = __ffsll((unsigned long long)A2) - 1;
   const int r = __ffsll((unsigned long long)A3) - 1;
-  const bool leaf2 = A2 && anchors_of(pc, clear_full(B1 | (pb.shape << (q & 63)))) != 0ull;
-  const bool leaf3 = A3 && anchors_of(pb, clear_full(B1 | (pc.shape << (r & 63)))) != 0ull;
-  return (A2 | A3) == 0ull ? 0 : ((dacc || leaf2 || leaf3) ? 1 : 2);
+  const bool leaf2 = (A2 != 0ull) & (anchors_of(pc, clear_full(B1 | (bshape << (q & 63)))) != 0ull);
+  const bool leaf3 = (A3 != 0ull) & (anchors_of(pb, clear_full(B1 | (cshape << (r & 63)))) != 0ull);
+  return (A2 | A3) == 0ull ? 0 : ((dacc | leaf2 | leaf3) ? 1 : 2);
 }
 
 // In-lane quick test of fixed level-1 slot k of the drawn hand (x0, x1, x2) on
@@ -210,6 +213,7 @@ __device__ __forceinline__ bool quick_slot_bf(uint64_t B, uint32_t x0, uint32_t 
   const PieceRow& pb = tbl[bi];
   const PieceRow& pc = tbl[ci];
   const uint32_t dbc = dtab[bi * kPieces + ci];
+  const uint64_t bshape = pb.shape, cshape = pc.shape;  // read with the rows, not behind the leaves' A2 / A3 tests
   const uint64_t Af = anchors_of(pf, B);
   const int p = k < 3 ? __ffsll((unsigned long long)Af) - 1 : 63 - __clzll((long long)(Af | 1ull));
   const uint64_t B1 = clear_full(B | (pf.shape << (p & 63)));
@@ -218,9 +222,9 @@ __device__ __forceinline__ bool quick_slot_bf(uint64_t B, uint32_t x0, uint32_t 
   const bool dacc = (A2 && (uint32_t)__popcll(A3) > dbc) || (A3 && (uint32_t)__popcll(A2) > dbc);
   const int q = __ffsll((unsigned long long)A2) - 1;
   const int r = __ffsll((unsigned long long)A3) - 1;
-  const bool leaf2 = A2 && anchors_of(pc, clear_full(B1 | (pb.shape << (q & 63)))) != 0ull;
-  const bool leaf3 = A3 && anchors_of(pb, clear_full(B1 | (pc.shape << (r & 63)))) != 0ull;
-  return Af != 0ull && (dacc || leaf2 || leaf3);
+  const bool leaf2 = (A2 != 0ull) & (anchors_of(pc, clear_full(B1 | (bshape << (q & 63)))) != 0ull);
+  const bool leaf3 = (A3 != 0ull) & (anchors_of(pb, clear_full(B1 | (cshape << (r & 63)))) != 0ull);
+  return (Af != 0ull) & (dacc | leaf2 | leaf3);
 }
 
 // quick_slot_bf's test on the level-1 slot whose first piece is the hand's
@@ -247,16 +251,17 @@ __device__ __forceinline__ bool quick_rank_bf(uint64_t B, uint32_t x0, uint32_t 
   const PieceRow& pb = tbl[bi];
   const PieceRow& pc = tbl[ci];
   const uint32_t dbc = dtab[bi * kPieces + ci];
+  const uint64_t fshape = tbl[fi].shape, bshape = pb.shape, cshape = pc.shape;  // with the rows (see pair_quick_bf)
   const int p = __ffsll((unsigned long long)Af) - 1;
-  const uint64_t B1 = clear_full(B | (tbl[fi].shape << (p & 63)));
+  const uint64_t B1 = clear_full(B | (fshape << (p & 63)));
   const uint64_t A2 = anchors_of(pb, B1);
   const uint64_t A3 = anchors_of(pc, B1);
   const bool dacc = (A2 && (uint32_t)__popcll(A3) > dbc) || (A3 && (uint32_t)__popcll(A2) > dbc);
   const int q = __ffsll((unsigned long long)A2) - 1;
   const int r = __ffsll((unsigned long long)A3) - 1;
-  const bool leaf2 = A2 && anchors_of(pc, clear_full(B1 | (pb.shape << (q & 63)))) != 0ull;
-  const bool leaf3 = A3 && anchors_of(pb, clear_full(B1 | (pc.shape << (r & 63)))) != 0ull;
-  return Af != 0ull && (dacc || leaf2 || leaf3);
+  const bool leaf2 = (A2 != 0ull) & (anchors_of(pc, clear_full(B1 | (bshape << (q & 63)))) != 0ull);
+  const bool leaf3 = (A3 != 0ull) & (anchors_of(pb, clear_full(B1 | (cshape << (r & 63)))) != 0ull);
+  return (Af != 0ull) & (dacc | leaf2 | leaf3);
 }
 
 // In-lane quick test of the first attempt (step_kernel): draw its three
@@ -384,10 +389,27 @@ __device__ __forceinline__ uint32_t lds_flag_load_acquire(uint32_t* f) {
 #ifndef BB_SLOW_LINE_MIN
 #define BB_SLOW_LINE_MIN 512
 #endif
-template <bool kLineOnly = false>
+//
+// kLeavesDone: the caller's quick test (pair_quick, pair_quick_bf) has already run the first leaf of each
+// order -- b at A2's lowest anchor, c at A3's -- and a needed slot is one where both failed (or the list
+// was empty).  Those are this phase's own task 0 of each order, so they leave the lists: A & (A - 1), and 0
+// stays 0.  A needed slot may then have no task at all; its verdict is "no success" and `pending` drops it
+// with the slots whose tasks are done.  The line-only filter stays exact on the shorter lists: a leaf it
+// drops implies a leaf of the other order, and if that one is a removed first leaf it is known to have failed.
+//
+// The trip itself keeps its `t < total` region: with the two row reads issued for every lane ahead of
+// select_bit and the result gated instead, the line did not move (tools/patches/r13_exact_trip_early_rows.diff).
+#ifndef BB_SLOW_SKIP_LEAVES
+#define BB_SLOW_SKIP_LEAVES 1  // what every caller below passes as kLeavesDone (each runs both first leaves)
+#endif
+template <bool kLineOnly = false, bool kLeavesDone = false>
 __device__ __forceinline__ bool slow_phase_wave(bool need, uint64_t B1, uint32_t bi, uint32_t ci, uint64_t A2,
                                                 uint64_t A3, const PieceRow* tbl, int lane, uint32_t* lds,
                                                 uint32_t key) {
+  if constexpr (kLeavesDone) {
+    A2 &= A2 - 1ull;
+    A3 &= A3 - 1ull;
+  }
   if constexpr (kLineOnly && 1) {
   const uint32_t all = need ? (uint32_t)(__popcll(A2) + __popcll(A3)) : 0u;
   const uint32_t all_tot = (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_add(all), 63);  // every lane
@@ -486,6 +508,9 @@ constexpr int kPack = 32;
 #define BB_MULTI_PASSES 3  // gen_hands_multi: a round packs attempts for up to this many 64-slot passes
 #endif
 constexpr int kMultiPasses = BB_MULTI_PASSES;
+#ifndef BB_QUICK_EARLY_ROWS
+#define BB_QUICK_EARLY_ROWS 1  // 0: the round-12 pass (the slot's table reads where the scheduler put them)
+#endif
 static_assert(3 * kPack / 2 + 2 <= kJumpMax, "jump table too short for the batch size");
 
 __device__ __forceinline__ void mul128(uint64_t alo, uint64_t ahi, uint64_t blo, uint64_t bhi, uint64_t& lo,
@@ -650,7 +675,8 @@ __device__ __forceinline__ void gen_hand_wave(uint64_t B, Pcg& rng, uint32_t& id
       if (stats) stats[4] += (uint32_t)(tq1 - tq0);
       if (needs) {
         const uint64_t tq2 = stats ? __builtin_amdgcn_s_memtime() : 0;
-        ok |= slow_phase_wave(need, B1, bi, ci, A2, A3, tbl, lane, lds, (uint32_t)j);  // one env: attempt j
+        ok |= slow_phase_wave<false, (bool)BB_SLOW_SKIP_LEAVES>(need, B1, bi, ci, A2, A3, tbl, lane, lds,
+                                                                    (uint32_t)j);  // one env: attempt j
         if (stats) {
           const uint64_t tq3 = __builtin_amdgcn_s_memtime();
           stats[5] += (uint32_t)(tq2 - tq1);
@@ -817,13 +843,25 @@ __device__ __forceinline__ void gen_hands_multi(uint64_t parked, uint64_t eB, Pc
         const int rem0 = slot - joff;
         const int c0 = __popcll(jA0), c1 = __popcll(jA1);
         const int f = rem0 < c0 ? 0 : (rem0 < c0 + c1 ? 1 : 2);
+        bi = hand_id(jid, f == 0 ? 1 : 0);
+        ci = hand_id(jid, f == 2 ? 1 : 2);
+#if BB_QUICK_EARLY_ROWS
+        // the slot's table reads as one cluster ahead of select_bit (see gen_hands_quota)
+        const uint64_t fshape = tbl[hand_id(jid, f)].shape;
+        const PieceRow pb = tbl[bi], pc = tbl[ci];
+        const uint32_t dbc = dtab[bi * kPieces + ci];
+        __builtin_amdgcn_sched_barrier(0);
+#endif
         const uint64_t Af = f == 0 ? jA0 : (f == 1 ? jA1 : jA2);
         const int rem = rem0 - (f == 0 ? 0 : (f == 1 ? c0 : c0 + c1));
         const int p = select_bit(Af, (uint32_t)rem) & 63;
-        bi = hand_id(jid, f == 0 ? 1 : 0);
-        ci = hand_id(jid, f == 2 ? 1 : 2);
+#if BB_QUICK_EARLY_ROWS
+        B1 = clear_full(jB | (fshape << p));
+        q = pair_quick_bf(B1, pb, pc, dbc, A2, A3);
+#else
         B1 = clear_full(jB | (tbl[hand_id(jid, f)].shape << p));
         q = pair_quick_bf(B1, tbl[bi], tbl[ci], dtab[bi * kPieces + ci], A2, A3);
+#endif
         if (slot >= total) q = 0;
       }
       // attempt lanes with a quick accept: attempt lane L owns the pass's slot
@@ -839,8 +877,8 @@ __device__ __forceinline__ void gen_hands_multi(uint64_t parked, uint64_t eB, Pc
       const bool need = q == 2 && !((qam | okm) & jenv & ((2ull << j) - 1ull));
       BB_MT(q1);
       if (__ballot(need))  // attempt lane j = env slot j % E, its attempt j / E
-        ok |= slow_phase_wave<kLineOnly>(need, B1, bi, ci, A2, A3, tbl, lane, lds,
-                                         (uint32_t)((j % E) << 8 | (j / E)));
+        ok |= slow_phase_wave<kLineOnly, (bool)BB_SLOW_SKIP_LEAVES>(need, B1, bi, ci, A2, A3, tbl, lane, lds,
+                                                                        (uint32_t)((j % E) << 8 | (j / E)));
       BB_MT(q2);
       pq += q1 - q0;
       ps += q2 - q1;
@@ -1035,22 +1073,35 @@ __device__ __forceinline__ void gen_hands_quota(uint64_t parked, uint64_t eB, Pc
       wave_lds_fence();
       const int j = (int)wave_incl_max(lds[lane]);
       const uint32_t jid = __shfl(e_ids, j);
+      const int jrem0 = __shfl(done - off, j) + lane;  // slot index within attempt j
       const uint64_t jA0 = __shfl(eA0, j), jA1 = __shfl(eA1, j), jA2 = __shfl(eA2, j);
       const uint64_t jB = __shfl(B, j);
-      const int jrem0 = __shfl(done - off, j) + lane;  // slot index within attempt j
       int q = 0;
       uint64_t B1 = 0, A2 = 0, A3 = 0;
       uint32_t bi = 0, ci = 0;
       {  // every lane computes its slot (lanes past `total` a dummy one) and drops it by select
         const int c0 = __popcll(jA0), c1 = __popcll(jA1);
         const int f = jrem0 < c0 ? 0 : (jrem0 < c0 + c1 ? 1 : 2);
+        bi = hand_id(jid, f == 0 ? 1 : 0);
+        ci = hand_id(jid, f == 2 ? 1 : 2);
+#if BB_QUICK_EARLY_ROWS
+        // f needs two popcounts; every table read of the slot follows from it.  They are issued here, as
+        // one cluster, and are in flight while select_bit finds the anchor
+        const uint64_t fshape = tbl[hand_id(jid, f)].shape;
+        const PieceRow pb = tbl[bi], pc = tbl[ci];  // by value: read here
+        const uint32_t dbc = dtab[bi * kPieces + ci];
+        __builtin_amdgcn_sched_barrier(0);  // without it the scheduler sinks four of the reads behind select_bit
+#endif
         const uint64_t Af = f == 0 ? jA0 : (f == 1 ? jA1 : jA2);
         const int rem = jrem0 - (f == 0 ? 0 : (f == 1 ? c0 : c0 + c1));
         const int p = select_bit(Af, (uint32_t)rem) & 63;
-        bi = hand_id(jid, f == 0 ? 1 : 0);
-        ci = hand_id(jid, f == 2 ? 1 : 2);
+#if BB_QUICK_EARLY_ROWS
+        B1 = clear_full(jB | (fshape << p));
+        q = pair_quick_bf(B1, pb, pc, dbc, A2, A3);
+#else
         B1 = clear_full(jB | (tbl[hand_id(jid, f)].shape << p));
         q = pair_quick_bf(B1, tbl[bi], tbl[ci], dtab[bi * kPieces + ci], A2, A3);
+#endif
         if (lane >= total) q = 0;
       }
       // attempt lane L owns the pass's slot bits [off, off + c)
@@ -1061,8 +1112,8 @@ __device__ __forceinline__ void gen_hands_quota(uint64_t parked, uint64_t eB, Pc
       const bool need = q == 2 && !((qam | okm) & jenv & ((2ull << j) - 1ull));
       BB_MT(q1);
       if (__ballot(need))
-        ok |= slow_phase_wave<kLineOnly>(need, B1, bi, ci, A2, A3, tbl, lane, lds,
-                                         (uint32_t)((j % E) << 8 | (j / E)));
+        ok |= slow_phase_wave<kLineOnly, (bool)BB_SLOW_SKIP_LEAVES>(need, B1, bi, ci, A2, A3, tbl, lane, lds,
+                                                                        (uint32_t)((j % E) << 8 | (j / E)));
       BB_MT(q2);
       pq += q1 - q0;
       ps += q2 - q1;

@@ -97,6 +97,13 @@ VARIANTS = {
     "alo128": ["-DBB_ASYNC_LINEONLY=1", "-DBB_SLOW_LINE_MIN=128"],
     "alo512": ["-DBB_ASYNC_LINEONLY=1"],
     "aloff": ["-DBB_ASYNC_LINEONLY=0"],
+    # round 13, one item off each: the quick pass's table reads where the scheduler puts them, the exact phase
+    # with the two first leaves the quick test already ran; both off leaves the quick tests' select form alone.
+    # The exact trip's row reads ahead of select_bit (arm "ser0" of profiles/r13/r13loo_*) did not separate:
+    # tools/patches/r13_exact_trip_early_rows.diff
+    "sqe0": ["-DBB_QUICK_EARLY_ROWS=0"],
+    "ssl0": ["-DBB_SLOW_SKIP_LEAVES=0"],
+    "r13sel": ["-DBB_QUICK_EARLY_ROWS=0", "-DBB_SLOW_SKIP_LEAVES=0"],
     # fp32 board convolutions (csrc/bb_conv32.hip): input channels per weight stage, LDS ring slots
     "c32s64": ["-DBB_CONV32_SCI=64"],
     "c32r3": ["-DBB_CONV32_RING=3"],
