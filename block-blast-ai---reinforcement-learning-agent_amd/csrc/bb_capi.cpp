@@ -648,6 +648,21 @@ int bb_plan_values(bb_env* env, const bb_greedy_weights* w, int32_t depth, const
   });
 }
 
+// The hand-safe mask alone (safe_mask_kernel)
+int bb_safe_mask_pos(const bb_positions* pos, int32_t n, int32_t mode, uint64_t* d_mask, void* stream) {
+  const char* rule = bb_look_rules::safe_mask_pos(pos, n, mode, d_mask);
+  if (!rule && n == 0) return BB_OK;  // accepted, and nothing to do
+  return look_pos_call("bb_safe_mask_pos", rule, [&] {
+    return launch_safe_mask(pos->board, pos->hand, n, mode, d_mask, (hipStream_t)stream);
+  });
+}
+
+int bb_safe_mask(bb_env* env, int32_t mode, uint64_t* d_mask, void* stream) {
+  return look_env_call(env, "bb_safe_mask", bb_look_rules::safe_mask(mode, d_mask), [&] {
+    return launch_safe_mask(env->d.board, env->d.hand, env->n, mode, d_mask, (hipStream_t)stream);
+  });
+}
+
 int bb_masked_sample(const float* d_logits, const uint64_t* d_mask_bits, int32_t n, const float* d_uniform,
                      uint64_t seed, uint64_t step, uint64_t env_offset, int32_t deterministic,
                      const int64_t* d_action_in, int64_t* d_action, float* d_logp, float* d_entropy,

@@ -106,6 +106,9 @@ hipError_t launch_plan(const uint64_t* board, const uint32_t* hand, const int32_
 // the same search per first move (bb_lookahead.hip): depth 1..3, n > 0, at least one output
 hipError_t launch_plan_values(const uint64_t* board, const uint32_t* hand, const int32_t* combo, int n,
                               const bb_greedy_weights& w, int depth, const bb_plan_values_out& out, hipStream_t s);
+// the hand-safe mask alone (bb_lookahead.hip): n > 0, mode BB_SAFE_WORDS / BB_SAFE_OR_LEGAL, mask [n][3]
+hipError_t launch_safe_mask(const uint64_t* board, const uint32_t* hand, int n, int mode, uint64_t* mask,
+                            hipStream_t s);
 hipError_t launch_masked_sample(const float* logits, const uint64_t* mbits, int n, const float* uniform,
                                 uint64_t seed, uint64_t step, const uint64_t* d_step, uint64_t offset,
                                 int deterministic, const int64_t* action_in, int64_t* action, float* logp,

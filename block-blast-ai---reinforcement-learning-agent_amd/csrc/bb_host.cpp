@@ -465,6 +465,40 @@ void plan_values_host(const uint64_t* board, const uint32_t* hand, const int32_t
   }
 }
 
+// bbvec.h bb_safe_mask (the host twin of safe_mask_kernel): an existence search of its own on clear_full /
+// anchors_of, not plan_dfs -- no values, no After.  Can the unused pieces of `hand` be placed on B in some order?
+bool rest_fits(uint64_t B, uint32_t hand) {
+  const uint32_t left = ~hand_used(hand) & 7u;
+  if (!left) return true;  // the move before was a refill
+  for (int q = 0; q < 3; ++q) {
+    const uint32_t id = hand_id(hand, q);
+    if (!((left >> q) & 1u) || id >= (uint32_t)kPieces) continue;
+    for (uint64_t m = anchors_of((int)id, B); m; m &= m - 1)
+      if (rest_fits(clear_full(B | (T().p[id].shape << __builtin_ctzll(m))), hand_use(hand, q))) return true;
+  }
+  return false;
+}
+
+void safe_mask_host(const uint64_t* board, const uint32_t* hand, int32_t n, int mode, uint64_t* mask) {
+#pragma omp parallel for schedule(dynamic, 64)
+  for (int32_t i = 0; i < n; ++i) {
+    uint64_t safe[3] = {0, 0, 0}, legal[3] = {0, 0, 0};
+    const uint64_t B = board[i];
+    const uint32_t h = hand[i];
+    for (int p = 0; p < 3 && !hand_over(h); ++p) {
+      const uint32_t id = hand_id(h, p);
+      if (((hand_used(h) >> p) & 1u) || id >= (uint32_t)kPieces) continue;
+      legal[p] = anchors_of((int)id, B);
+      for (uint64_t m = legal[p]; m; m &= m - 1) {
+        const int cell = __builtin_ctzll(m);
+        if (rest_fits(clear_full(B | (T().p[id].shape << cell)), hand_use(h, p))) safe[p] |= 1ull << cell;
+      }
+    }
+    const bool keep = mode == BB_SAFE_WORDS || (safe[0] | safe[1] | safe[2]) != 0ull;
+    for (int p = 0; p < 3; ++p) mask[3 * (size_t)i + p] = keep ? safe[p] : legal[p];
+  }
+}
+
 }  // namespace
 
 #ifndef BB_BUILD_ID
@@ -771,6 +805,21 @@ int bb_plan_values(bb_env* env, const bb_greedy_weights* w, int32_t depth, const
   if (!env) return BB_ERR_ARG;
   if (int rc = refused(env, "bb_plan_values", R::plan_values(w, depth, out))) return rc;
   plan_values_host(env->board.data(), env->hand.data(), env->combo.data(), env->n, *w, depth, *out);
+  return BB_OK;
+}
+
+int bb_safe_mask_pos(const bb_positions* pos, int32_t n, int32_t mode, uint64_t* d_mask, void* stream) {
+  (void)stream;
+  if (int rc = refused(nullptr, "bb_safe_mask_pos", R::safe_mask_pos(pos, n, mode, d_mask))) return rc;
+  safe_mask_host(pos->board, pos->hand, n, mode, d_mask);
+  return BB_OK;
+}
+
+int bb_safe_mask(bb_env* env, int32_t mode, uint64_t* d_mask, void* stream) {
+  (void)stream;
+  if (!env) return BB_ERR_ARG;
+  if (int rc = refused(env, "bb_safe_mask", R::safe_mask(mode, d_mask))) return rc;
+  safe_mask_host(env->board.data(), env->hand.data(), env->n, mode, d_mask);
   return BB_OK;
 }
 

@@ -1,4 +1,4 @@
-// bb_look_rules.h -- the argument rules of the eight lookahead entry points of include/bbvec.h, one copy for
+// bb_look_rules.h -- the argument rules of the ten lookahead entry points of include/bbvec.h, one copy for
 // both backends (csrc/bb_capi.cpp and csrc/bb_host.cpp).  Plain C++, nothing from HIP.
 //
 // Each function returns the rule an argument set breaks, as the text that follows "<entry point>: " in
@@ -7,7 +7,7 @@
 //
 // Asymmetries that are part of the ABI as it stands: bb_afterstates_pos, bb_greedy_actions_pos and
 // bb_plan_actions_pos refuse n == 0 and answer every broken rule with one text; bb_plan_values_pos accepts n == 0
-// (and does nothing) and names the rule that broke.
+// (and does nothing) and names the rule that broke, and so does bb_safe_mask_pos.
 #pragma once
 #include <stdint.h>
 
@@ -58,6 +58,17 @@ inline const char* plan_values_pos(const bb_positions* pos, int32_t n, const bb_
   if (no_positions(pos)) return "positions (board, hand) are NULL";
   if (n < 0) return "n is negative";
   return plan_values(w, depth, out);
+}
+
+inline const char* safe_mask(int32_t mode, const uint64_t* d_mask) {
+  if (!d_mask) return "d_mask is NULL";
+  if (mode < BB_SAFE_WORDS || mode > BB_SAFE_OR_LEGAL) return "mode must be 0..1";
+  return nullptr;
+}
+inline const char* safe_mask_pos(const bb_positions* pos, int32_t n, int32_t mode, const uint64_t* d_mask) {
+  if (no_positions(pos)) return "positions (board, hand) are NULL";
+  if (n < 0) return "n is negative";
+  return safe_mask(mode, d_mask);
 }
 
 }  // namespace bb_look_rules

@@ -414,6 +414,87 @@ plan_values_kernel(LookTable t, LookPos pos, int n, bb_greedy_weights w, int dep
   }
 }
 
+// ---------------------------------------------------------------------------
+// The hand-safe mask alone (bbvec.h bb_safe_mask): plan_values_kernel's safe words of depth >= 2 by an existence
+// search.  No values, so no weights, no combo, no record list: after first move a, can the rest of the hand still
+// be placed in some order?
+//
+// One wave64 per position, four positions per workgroup, the waves independent: no LDS, no barrier, so nothing
+// of one position can be overwritten by the next one a wave strides to.  The wave takes the three hand slots in
+// turn (a used slot is skipped by a wave-uniform branch), lane = anchor cell, the position in scalar registers and
+// the rows of the pieces that stay in the hand read through scalar loads.  A legal lane answers for its own first
+// move: nothing left -- safe; one piece left -- one anchors_of; two pieces left -- trip k of its loop tries the
+// k-th lowest anchor of either order (both leaves computed and or-ed, as pair_quick_bf does, so trip 0 is each
+// order's first leaf, which settles an open board) and the lane leaves at its first success.  Trip bound: 64 (an
+// anchor mask has 64 bits; both orders advance together).  The words are made by ballot, the "some action is safe"
+// of mode 1 is an or of three scalar words, and lanes 0..2 store one word each.  No atomics, no inline assembly.
+// ---------------------------------------------------------------------------
+constexpr int kSafeWaves = 4;                // positions per workgroup
+constexpr int kSafeBlock = 64 * kSafeWaves;
+constexpr int64_t kSafeMaxGrid = 1 << 15;    // more than 4 * this many positions: the waves stride over them
+
+// anchors of the piece in hand slot q on board X; a piece id outside the table places nowhere
+__device__ __forceinline__ uint64_t slot_anchors(const LookTable& t, uint32_t hand, int q, uint64_t X) {
+  const uint32_t id = hand_id(hand, q);
+  return id < (uint32_t)kPieces ? anchors_of(t.row[id], X) : 0ull;
+}
+
+__global__ void __launch_bounds__(kSafeBlock)
+safe_mask_kernel(LookTable t, LookPos pos, int n, int mode, uint64_t* __restrict__ mask) {
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int cell = (int)(threadIdx.x & 63u);
+  const int64_t stride = (int64_t)gridDim.x * kSafeWaves;
+  for (int64_t i = (int64_t)blockIdx.x * kSafeWaves + wave; i < (int64_t)n; i += stride) {  // i is wave-uniform
+    const uint64_t B = uniform64(pos.board[i]);
+    const uint32_t hand = uniform32(pos.hand[i]);
+    const uint32_t used0 = hand_used(hand);
+    uint64_t safe_w[kHand] = {0ull, 0ull, 0ull}, legal_w[kHand] = {0ull, 0ull, 0ull};
+#pragma unroll
+    for (int p = 0; p < kHand; ++p) {
+      const uint32_t id = hand_id(hand, p);
+      if (hand_over(hand) || ((used0 >> p) & 1u) || id >= (uint32_t)kPieces) continue;  // wave-uniform
+      const PieceRow& pr = t.row[id];
+      const bool legal = (anchors_of(pr, B) >> cell) & 1ull;
+      const uint32_t left = ~(used0 | (1u << p)) & 7u;  // the slots that stay unused: 0, 1 or 2 of them
+      bool ok = legal;
+      if (left != 0u && legal) {
+        const uint64_t B1 = clear_full(B | (pr.shape << cell));
+        const int b = __ffs((int)left) - 1;
+        const uint64_t Ab = slot_anchors(t, hand, b, B1);
+        if ((left & (left - 1u)) == 0u) {  // one piece left (wave-uniform)
+          ok = Ab != 0ull;
+        } else {  // two pieces left: some order, some anchor of its first piece
+          const int c = 31 - __clz((int)left);
+          const uint64_t Ac = slot_anchors(t, hand, c, B1);
+          // Ab != 0 / Ac != 0 implies a valid id, so the clamped rows below are the pieces' own
+          const uint32_t idb = hand_id(hand, b), idc = hand_id(hand, c);
+          const uint64_t sb = t.row[idb < (uint32_t)kPieces ? idb : 0u].shape;
+          const uint64_t sc = t.row[idc < (uint32_t)kPieces ? idc : 0u].shape;
+          uint64_t mb = Ab, mc = Ac;
+          ok = false;
+#pragma unroll 1
+          for (int it = 0; it < 64 && !ok && (mb | mc) != 0ull; ++it) {
+            const int x = (__ffsll((unsigned long long)mb) - 1) & 63;
+            const int y = (__ffsll((unsigned long long)mc) - 1) & 63;
+            const bool leaf_b = (mb != 0ull) & (slot_anchors(t, hand, c, clear_full(B1 | (sb << x))) != 0ull);
+            const bool leaf_c = (mc != 0ull) & (slot_anchors(t, hand, b, clear_full(B1 | (sc << y))) != 0ull);
+            ok = leaf_b | leaf_c;
+            mb &= mb - 1ull;  // 0 stays 0
+            mc &= mc - 1ull;
+          }
+        }
+      }
+      legal_w[p] = __ballot(legal);
+      safe_w[p] = __ballot(ok);
+    }
+    const bool keep = mode == BB_SAFE_WORDS || (safe_w[0] | safe_w[1] | safe_w[2]) != 0ull;  // wave-uniform
+    const uint64_t w0 = keep ? safe_w[0] : legal_w[0];
+    const uint64_t w1 = keep ? safe_w[1] : legal_w[1];
+    const uint64_t w2 = keep ? safe_w[2] : legal_w[2];
+    if (cell < kHand) mask[i * kHand + cell] = cell == 0 ? w0 : (cell == 1 ? w1 : w2);
+  }
+}
+
 const LookTable& look_table() {
   static const LookTable t = [] {
     LookTable x;
@@ -457,6 +538,15 @@ hipError_t launch_plan_values(const uint64_t* board, const uint32_t* hand, const
   // the safe set of depth 3 is that of depth 2 (bbvec.h): asked for alone, the third ply is not searched
   if (depth == 3 && !out.q && !out.rest && !out.leaves) depth = 2;
   hipLaunchKernelGGL(plan_values_kernel, plan_grid(n), dim3(kPlanBlock), 0, s, look_table(), pos, n, w, depth, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_safe_mask(const uint64_t* board, const uint32_t* hand, int n, int mode, uint64_t* mask,
+                            hipStream_t s) {
+  const LookPos pos{board, hand, nullptr, nullptr};
+  const int64_t blocks = ((int64_t)n + kSafeWaves - 1) / kSafeWaves;
+  const dim3 grid((unsigned)(blocks < kSafeMaxGrid ? blocks : kSafeMaxGrid));
+  hipLaunchKernelGGL(safe_mask_kernel, grid, dim3(kSafeBlock), 0, s, look_table(), pos, n, mode, mask);
   return hipGetLastError();
 }
 

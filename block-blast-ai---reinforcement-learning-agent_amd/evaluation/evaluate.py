@@ -16,7 +16,7 @@ compared with.  An agent with ``act_env(env_batch, out)`` picks its actions from
 fused one-ply kernel); every other agent goes through ``act_device`` as before.
 
 ``--safe-mask`` (off by default) restricts the policy to hand-safe actions: the legal moves after which the rest of
-the hand can still be placed in some order (``bb_plan_values``' safe words, one more launch per move).  For
+the hand can still be placed in some order (``bb_plan_values``' safe words, from ``bb_safe_mask``: one more launch per move).  For
 ``--agent ppo`` they are AND-ed into the mask the policy samples under, for ``--agent random`` the agent draws from
 them; a position without a safe move keeps its legal mask.
 """

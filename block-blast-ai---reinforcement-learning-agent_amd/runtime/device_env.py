@@ -298,8 +298,25 @@ class DeviceEnvBatch:
     def safe_mask(self, out: torch.Tensor, depth: int = 3) -> torch.Tensor:
         """The hand-safe action mask into out (int64 [N, 3], the layout of ``obs(mask_bits=)``): the legal actions
         after which the rest of the hand can still be placed in some order.  All zeros where no legal action is
-        safe (or none is legal).  One launch, nothing else written."""
+        safe (or none is legal).  One launch, nothing else written.  depth >= 2: bb_safe_mask, the existence
+        search; depth 1 (legal & !dead, another set): bb_plan_values."""
+        if int(depth) in (2, 3):  # any other depth is bb_plan_values' to answer or refuse
+            return self._safe_mask(0, out)
         self.plan_values({}, depth, out={"safe": out})
+        return out
+
+    def sampling_mask(self, out: torch.Tensor) -> torch.Tensor:
+        """The mask to sample under when training or playing hand-safe, into out (int64 [N, 3]): an env's safe words
+        (``safe_mask`` at depth >= 2) where it has a safe action, else its legal words (all zeros for a finished
+        game).  One launch (bb_safe_mask, mode BB_SAFE_OR_LEGAL); reads the state and changes nothing."""
+        return self._safe_mask(1, out)
+
+    def _safe_mask(self, mode: int, out: torch.Tensor) -> torch.Tensor:
+        from . import kernels as K
+
+        K._safe_mask_out(out, self.num_envs, self.device)
+        L.check(self.lib.bb_safe_mask(self.handle, int(mode), _ptr(out), _stream(self.device)), "bb_safe_mask",
+                self.handle, self.lib)
         return out
 
     # ------------------------------------------------------------ host copies

@@ -319,6 +319,29 @@ def plan_values(board: torch.Tensor, hand: torch.Tensor, weights, depth: int = 3
     return out
 
 
+SAFE_WORDS, SAFE_OR_LEGAL = 0, 1  # bbvec.h BB_SAFE_WORDS / BB_SAFE_OR_LEGAL
+
+
+def _safe_mask_out(out: Optional[torch.Tensor], n: int, dev) -> torch.Tensor:
+    out = torch.empty((n, 3), dtype=torch.int64, device=dev) if out is None else out
+    if not (out.dtype == torch.int64 and out.device == dev and out.is_contiguous() and out.numel() == n * 3):
+        raise L.BBNativeError(f"safe_mask: out must be a contiguous {torch.int64} [{n}, 3] on {dev}")
+    return out
+
+
+def safe_mask(board: torch.Tensor, hand: torch.Tensor, mode: int = SAFE_WORDS,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """bb_safe_mask_pos: the hand-safe mask words int64 [n, 3] (layout of mask_bits) of every position, by an
+    existence search in one launch -- ``plan_values``' "safe" at depth >= 2 without the values.  mode SAFE_WORDS
+    (0): the safe words, zeros where nothing is safe; SAFE_OR_LEGAL (1): the sampling mask, the safe words where
+    the position has a safe action, else its legal words.  Writes ``out`` when given; returns the tensor."""
+    pos, n, dev = _positions(board, hand, None, None)
+    out = _safe_mask_out(out, n, dev)
+    lib, stream = _look_lib(dev)
+    L.check(lib.bb_safe_mask_pos(C.byref(pos), n, int(mode), _p(out), stream), "bb_safe_mask_pos", lib=lib)
+    return out
+
+
 def unpack_rest(rest):
     """(a2, a3) of bb_plan_values' rest words (torch or numpy), -1 for a ply not played or an illegal action."""
     a2, a3 = rest & 0xFF, (rest >> 8) & 0xFF

@@ -215,6 +215,8 @@ SIGNATURES = {
     "bb_plan_values_pos": (C.c_int, [C.POINTER(Positions), _I32, C.POINTER(GreedyWeights), _I32,
                                      C.POINTER(PlanValuesOut), _P]),
     "bb_plan_values": (C.c_int, [_P, C.POINTER(GreedyWeights), _I32, C.POINTER(PlanValuesOut), _P]),
+    "bb_safe_mask_pos": (C.c_int, [C.POINTER(Positions), _I32, _I32, _P, _P]),
+    "bb_safe_mask": (C.c_int, [_P, _I32, _P, _P]),
     "bb_masked_sample": (C.c_int, [_P, _P, _I32, _P, _U64, _U64, _U64, _I32, _P, _P, _P, _P, _P]),
     "bb_masked_sample_dstep": (C.c_int, [_P, _P, _I32, _U64, _P, _U64, _U64, _I32, _P, _P, _P, _P]),
     "bb_gae": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _F, _F, _P, _P, _P]),
@@ -268,7 +270,7 @@ HOST_SYMBOLS = ("bb_abi_version", "bb_build_id", "bb_create", "bb_destroy", "bb_
                 "bb_seed", "bb_reset", "bb_step", "bb_rollout", "bb_sync", "bb_obs", "bb_device_ptrs", "bb_snapshot",
                 "bb_get_state", "bb_set_state", "bb_random_actions", "bb_afterstates_pos", "bb_afterstates",
                 "bb_greedy_actions_pos", "bb_greedy_actions", "bb_plan_actions_pos", "bb_plan_actions",
-                "bb_plan_values_pos", "bb_plan_values")
+                "bb_plan_values_pos", "bb_plan_values", "bb_safe_mask_pos", "bb_safe_mask")
 
 _lib = None
 _host = None

@@ -111,7 +111,8 @@ class DeviceRollout:
     """One rank's env shard + packed rollout storage + episode bookkeeping."""
 
     def __init__(self, num_envs: int, env_offset: int, global_envs: int, seed: int, reward_config,
-                 rollout_steps: int, device: torch.device):
+                 rollout_steps: int, device: torch.device, safe_mask: bool = False):
+        self.safe_mask = bool(safe_mask)  # sample under the hand-safe mask (env.sampling_mask), not the legal one
         self.n, self.offset, self.global_envs, self.T = num_envs, env_offset, global_envs, rollout_steps
         self.device = device
         self.env = DeviceEnvBatch(num_envs, [seed + env_offset + i for i in range(num_envs)], reward_config,
@@ -125,7 +126,7 @@ class DeviceRollout:
         self.ep_moves = torch.zeros((rollout_steps, num_envs), dtype=torch.int32, device=device)
         self._graph = None          # captured rollout (collect(graph=True))
         self._graph_warm = False
-        self._graph_key = None      # (agent, agent.graph_epoch, train mode) the graph was captured for
+        self._graph_key = None      # (agent, agent.graph_epoch, train mode, safe_mask) the graph was captured for
         self._step_base = None
 
     def reset(self) -> None:
@@ -145,8 +146,8 @@ class DeviceRollout:
         if not graph or not self.env.device.type == "cuda":
             self._collect_steps(agent)
             return
-        key = (id(agent), agent.graph_epoch, agent.network.training)
-        if self._graph_key != key:  # new agent, parameter storage, layout, precision or mode: recapture
+        key = (id(agent), agent.graph_epoch, agent.network.training, self.safe_mask)
+        if self._graph_key != key:  # new agent, parameter storage, layout, precision, mode or mask: recapture
             self._graph, self._graph_warm, self._graph_key = None, False, key
         if self._graph is None and not self._graph_warm:
             self._collect_steps(agent)  # eager warm-up: library algorithm selection, workspaces
@@ -167,7 +168,11 @@ class DeviceRollout:
         buf, env = self.buffer, self.env
         buf.reset()
         for t in range(self.T):
-            env.snapshot(board=buf.board[t], hand=buf.hand[t], mask_bits=buf.mask_bits[t])
+            if self.safe_mask:  # the stored words are the ones sampled under: the update sees the same mask
+                env.snapshot(board=buf.board[t], hand=buf.hand[t])
+                env.sampling_mask(buf.mask_bits[t])
+            else:
+                env.snapshot(board=buf.board[t], hand=buf.hand[t], mask_bits=buf.mask_bits[t])
             a, lp, v = agent.act_device(self.x, buf.mask_bits[t], env_offset=self.offset, step_base=step_base,
                                         step_add=t)
             buf.actions[t].copy_(a)
@@ -211,6 +216,19 @@ class DeviceRollout:
         rec = rec[np.argsort(rec[:, 0], kind="stable")][-WINDOW:]
         return int(count.item()), int(smax.item()), rec[:, 1].tolist(), rec[:, 2].tolist()
 
+    def safe_stats(self, world: int):
+        """(reward per step, mid-hand losses) of this rollout, over all ranks: the mean of the stored rewards, and
+        the episodes that ended on a move that was not the hand's third (two used bits in the stored hand word
+        before it), which is what the hand-safe mask exists to prevent.  Computed on the device, one host read."""
+        buf = self.buffer
+        used = (buf.hand.long() >> 18) & 7
+        third = (used == 3) | (used == 5) | (used == 6)
+        s = torch.stack([buf.rewards.double().sum(), ((buf.dones > 0) & ~third).sum().double()])
+        if world > 1:
+            dist.all_reduce(s)
+        s = s.tolist()
+        return s[0] / (self.T * self.global_envs), int(s[1])
+
     def close(self) -> None:
         self.env.close()
 
@@ -244,9 +262,17 @@ def train(config: Dict[str, Any], resume_path: Optional[str] = None, seed: int =
         raise ValueError(f"num_envs={num_envs} must divide evenly over {world} ranks")
     local = num_envs // world
     rollout_steps = int(train_cfg.get("rollout_steps", 128))
-    roll = DeviceRollout(local, rank * local, num_envs, seed, reward_cfg, rollout_steps, device)
+    # training.safe_mask: sample (and update) under the hand-safe mask -- the legal moves after which the rest of
+    # the hand still fits in some order, the legal mask where there is none.  Episodes then rarely end, so
+    # avg_score and best.pt, which see finished episodes only, move slowly; reward_per_step and mid_hand_losses
+    # are logged instead of changing their rules.
+    safe_mask = bool(train_cfg.get("safe_mask", False))
+    roll = DeviceRollout(local, rank * local, num_envs, seed, reward_cfg, rollout_steps, device,
+                         safe_mask=safe_mask)
     if main:
         print(f"Created {num_envs} parallel environments" + (f" ({world} shards of {local})" if world > 1 else ""))
+        if safe_mask:
+            print("Sampling under the hand-safe mask (training.safe_mask)")
 
     agent_cfg = ppo_config_from(config)
     agent = PPOAgent(agent_cfg, device)
@@ -315,6 +341,7 @@ def train(config: Dict[str, Any], resume_path: Optional[str] = None, seed: int =
                 max_episode = smax if max_episode is None else max(max_episode, smax)
                 tracker.extend("episode_score", scores)
                 tracker.extend("episode_length", moves)
+            safe_stats = roll.safe_stats(world) if safe_mask else None
             last_values = agent.values_device(roll.x)
             update_metrics = agent.update(roll.buffer, last_values, batch_size=local_batch)
             num_updates += 1
@@ -328,6 +355,8 @@ def train(config: Dict[str, Any], resume_path: Optional[str] = None, seed: int =
                 metrics = {"step": global_step, "fps": fps, "avg_score": avg_score,
                            "max_score": tracker.get_max("episode_score"), "best_score": best_score,
                            "avg_length": tracker.get_mean("episode_length"), **update_metrics}
+                if safe_stats is not None:
+                    metrics["reward_per_step"], metrics["mid_hand_losses"] = safe_stats
                 if avg_score > best_score:
                     best_score = avg_score
                     metrics["best_score"] = best_score

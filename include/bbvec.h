@@ -54,7 +54,9 @@ extern "C" {
                                  bb_bn_forward_res / _part, bb_bn_backward_red / _part / _res and
                                  bb_ppo_loss_forward_bf16 / _backward_bf16 removed (fields of the structs);
                                  (additive, still 9) bb_plan_values_out with bb_plan_values(_pos): per-action
-                                 full-hand values and the hand-safe mask */
+                                 full-hand values and the hand-safe mask;
+                                 (additive, still 9) bb_safe_mask(_pos): the hand-safe mask alone, by an
+                                 existence search, and the sampling mask (safe, else legal) */
 
 #define BB_OK 0
 #define BB_ERR_ARG (-1)
@@ -418,6 +420,35 @@ typedef struct bb_plan_values_out {
 int bb_plan_values_pos(const bb_positions* pos, int32_t n, const bb_greedy_weights* w, int32_t depth,
                        const bb_plan_values_out* out, void* stream);
 int bb_plan_values(bb_env* env, const bb_greedy_weights* w, int32_t depth, const bb_plan_values_out* out, void* stream);
+
+/* ---- the hand-safe mask alone --------------------------------------------------
+ * bb_plan_values' safe words of depth >= 2 without the values: an existence
+ * search, integers only, no weights.  Action a = p*64 + c of position (B, hand)
+ * is legal as bb_afterstates defines it (the hand's game-over bit clear, slot p
+ * unused, piece id < BB_NUM_PIECES, the piece fits at c).  With
+ * B1 = clear_full(B | shape << c), a legal a is safe iff
+ *   - it uses the last unused slot (a refill); or
+ *   - one slot q stays unused and its piece has an anchor on B1; or
+ *   - two slots b, c stay unused and for one of the orders (b, c), (c, b) the
+ *     first piece has an anchor x on B1 such that the second piece has an anchor
+ *     on clear_full(B1 | first.shape << x).
+ * (An unused slot whose piece id is >= BB_NUM_PIECES has no anchor anywhere.)
+ * This is not the depth-1 set legal & !dead.
+ *   mode BB_SAFE_WORDS    d_mask[i][p] = the safe word of slot p (zeros where
+ *                         nothing is safe)
+ *   mode BB_SAFE_OR_LEGAL the sampling mask: the safe words where position i has
+ *                         a safe action, else its legal words (as computed here)
+ * d_mask has the layout of bb_obs / bb_snapshot mask_bits.  pos->combo and
+ * pos->prev are not read.  n == 0 does nothing.  BB_ERR_ARG (the rule named in
+ * bb_last_error, before any HIP call) for a NULL pos / pos->board / pos->hand /
+ * d_mask, n < 0 and a mode outside 0..1.  The handle form reads the live columns
+ * and changes nothing, the RNG included, and refuses a handle in BB_ERR_DEVICE /
+ * BB_ERR_STATE.  Asynchronous on `stream`, no allocation, no sync
+ * (graph-capturable from the first call); indexing is 64-bit. */
+#define BB_SAFE_WORDS 0
+#define BB_SAFE_OR_LEGAL 1
+int bb_safe_mask_pos(const bb_positions* pos, int32_t n, int32_t mode, uint64_t* d_mask /* [n][3] */, void* stream);
+int bb_safe_mask(bb_env* env, int32_t mode, uint64_t* d_mask /* [N][3] */, void* stream);
 
 /* Fused masked-categorical tail of BlockBlastNetwork.get_action_and_value
  * (network.py:173-180, 210-262; Categorical clamp semantics of torch 2.10):

@@ -39,6 +39,8 @@ def main():
                     help="gather minibatches into fresh tensors and copy them into the captured step (pre-r02 path)")
     ap.add_argument("--graph-rollout", action="store_true",
                     help="BASELINE config 5: the rollout's T steps captured in one HIP graph and replayed")
+    ap.add_argument("--safe-mask", action="store_true",
+                    help="the rollout samples under the hand-safe mask (training.safe_mask: bb_safe_mask per step)")
     args = ap.parse_args()
 
     from agents import PPOAgent, PPOConfig
@@ -55,7 +57,7 @@ def main():
         agent.set_channels_last(args.layout == "channels_last")
     agent.use_graphs = not args.no_graph
     agent.train()
-    roll = DeviceRollout(args.envs, 0, args.envs, 42, {}, args.rollout, dev)
+    roll = DeviceRollout(args.envs, 0, args.envs, 42, {}, args.rollout, dev, safe_mask=args.safe_mask)
     roll.reset()
     # warm-up: a short rollout + a few optimizer steps (kernels, MIOpen tuning)
     roll_w = DeviceRollout(min(args.envs, 4096), 0, min(args.envs, 4096), 7, {}, 4, dev)
@@ -100,6 +102,7 @@ def main():
     print(json.dumps({
         "workload": "BASELINE config 3: full PPO iteration on 1 MI355X", "envs": args.envs, "rollout_steps": args.rollout,
         "miopen_find": args.miopen_find, "channels_last": agent.channels_last, "graph_rollout": args.graph_rollout,
+        "safe_mask": args.safe_mask, "rollout_step_ms": round(t_roll / args.rollout * 1e3, 3),
         "batch": args.batch, "epochs": args.epochs, "compute_dtype": "bf16 autocast" if args.autocast == "bf16" else "fp32",
         "rollout_s": round(t_roll, 4), "rollout_env_steps_per_s": round(samples / t_roll, 1),
         "rollout_cnn_tflops": round(roll_flops / 1e12, 2),
