@@ -180,10 +180,12 @@ class PackedRolloutBuffer:
     board bits, hand word, mask bits, action, log-prob, reward, done, value.
     Minibatch observations are expanded on the fly by ``bb_gather_obs``."""
 
-    def __init__(self, buffer_size: int, num_envs: int, device: torch.device):
+    def __init__(self, buffer_size: int, num_envs: int, device: torch.device, positions: bool = False):
         self.buffer_size, self.num_envs = buffer_size, num_envs
         self.device = torch.device(device)
         T, N, d = buffer_size, num_envs, self.device
+        if positions:  # with board and hand a position bb_plan_values_pos can search: get_position_minibatches
+            self.combo = torch.zeros((T, N), dtype=torch.int32, device=d)
         self.board = torch.zeros((T, N), dtype=torch.int64, device=d)
         self.hand = torch.zeros((T, N), dtype=torch.int32, device=d)
         self.mask_bits = torch.zeros((T, N, 3), dtype=torch.int64, device=d)
@@ -249,6 +251,22 @@ class PackedRolloutBuffer:
             yield x, mf, actions[b], logp[b], adv[b], ret[b]
 
 
+    def get_position_minibatches(self, batch_size: int, generator: Optional[torch.Generator] = None):
+        """Yields (x (B,4,8,8), mask_bits int64 (B,3), board int64 (B), hand int32 (B), combo int32 (B)) in a
+        random order (the permutation rules of ``get_minibatches``): the network input, the words it was sampled
+        under and the stored position for the search to label (PPOAgent.distill).  Needs ``positions=True``."""
+        if not hasattr(self, "combo"):
+            raise RuntimeError("get_position_minibatches needs PackedRolloutBuffer(..., positions=True)")
+        total = self.buffer_size * self.num_envs
+        perm = self._permutation(total, generator)
+        board, hand, mb = self.board.reshape(total), self.hand.reshape(total), self.mask_bits.reshape(total, 3)
+        combo = self.combo.reshape(total)
+        for start in range(0, total, batch_size):
+            b = perm[start:start + batch_size]
+            x, _ = K.gather_obs(board, hand, mb, b, want_mask=False)
+            yield x, mb[b], board[b], hand[b], combo[b]
+
+
 def categorical_log_prob(probs: torch.Tensor, action: torch.Tensor) -> torch.Tensor:
     """Categorical(probs).log_prob(action) without the validation sync:
     log(clamp(p / sum p, eps, 1 - eps))[action] (torch clamp_probs)."""
@@ -274,6 +292,47 @@ def ppo_loss_torch(logits, values, masks, actions, old_log_probs, advantages, re
         approx_kl = ((ratio - 1) - torch.log(ratio)).mean()
         clip_fraction = ((ratio - 1).abs() > cfg.clip_epsilon).float().mean()
         stats = torch.stack([policy_loss, value_loss, entropy.mean(), loss, approx_kl, clip_fraction]).detach()
+    return loss, stats
+
+
+_INT64_MIN = -(2 ** 63)  # bb_plan_values' q of an illegal action
+DISTILL_KEYS = ("distill_ce", "distill_kl", "distill_target_entropy", "distill_entropy", "distill_agreement")
+
+
+def distill_loss_torch(logits, mask_bits, q, tau: float):
+    """bbvec.h "policy distillation" on torch ops in fp32: the CPU path and the chain the fused
+    bb_distill_loss kernels replace.  logits [B, 192], mask_bits int64 [B, 3], q int64 [B, 192] (INT64_MIN =
+    illegal), tau >= 0.  Returns (loss = cross-entropy, 6 detached statistics: runtime.kernels.DISTILL_STATS)."""
+    logits = logits.float()
+    B = logits.shape[0]
+    ar = torch.arange(192, device=logits.device)
+    M = K.mask_bits_to_bool(mask_bits)
+    S = M & (q != _INT64_MIN)
+    has = S.any(dim=-1)
+    qs = torch.where(S, q, torch.full_like(q, _INT64_MIN))
+    qmax = qs.max(dim=-1, keepdim=True).values
+    qarg = torch.where(S & (qs == qmax), ar, 192).min(dim=-1).values  # the lowest action attaining qmax
+    if tau > 0:
+        d = torch.where(S, q - qmax, torch.zeros_like(q))  # int64: exact
+        w = torch.where(S & (d >= -(2 ** 31)), torch.exp(d.float() / tau), torch.zeros_like(logits))
+        t = w / torch.where(has, w.sum(dim=-1), torch.ones_like(w[:, 0])).unsqueeze(-1)
+    else:
+        t = ((ar == qarg.unsqueeze(-1)) & has.unsqueeze(-1)).float()
+    Me = M | ~has.unsqueeze(-1)  # an empty-S row (its M may be empty too) contributes nothing: keep it finite
+    masked = logits + torch.where(Me, torch.zeros_like(logits), torch.full_like(logits, float("-inf")))
+    logpi = torch.where(Me, F.log_softmax(masked, dim=-1), torch.zeros_like(logits))
+    pi = torch.where(Me, torch.exp(logpi), torch.zeros_like(logits))
+    zero = torch.zeros_like(logits)
+    row = lambda v: torch.where(has, v.sum(dim=-1), torch.zeros_like(v[:, 0]))  # noqa: E731
+    ce = row(-torch.where(t > 0, t * logpi, zero))
+    loss = ce.sum() / B
+    with torch.no_grad():
+        ht = row(-torch.where(t > 0, t * torch.log(torch.where(t > 0, t, torch.ones_like(t))), zero))
+        hp = row(-torch.where(pi > 0, pi * logpi, zero))
+        parg = torch.where(Me & (masked == masked.max(dim=-1, keepdim=True).values), ar, 192).min(dim=-1).values
+        agree = ((parg == qarg) & has).float()
+        stats = torch.stack([loss, (ce.sum() - ht.sum()) / B, ht.sum() / B, hp.sum() / B, agree.sum() / B,
+                             has.float().sum()]).detach()
     return loss, stats
 
 
@@ -341,6 +400,7 @@ class PPOAgent(BaseAgent):
         self.minibatch_stats: List[torch.Tensor] = []
         # update(): called as f(index, stats) after every optimizer step (logging, parity tests)
         self.minibatch_callback: Optional[Callable[[int, torch.Tensor], None]] = None
+        self._distill_q: Dict[int, torch.Tensor] = {}  # distill(): the search values' scratch per minibatch size
 
     @property
     def autocast_dtype(self) -> Optional[torch.dtype]:
@@ -540,11 +600,9 @@ class PPOAgent(BaseAgent):
             raise RuntimeError("conv-stack gradients are not a prefix of the flat buffer")
         return split
 
-    def _minibatch_loss(self, x, masks, actions, old_log_probs, advantages, returns):
-        """(loss, stats) of one minibatch.  In the segmented data-parallel mode the forward is cut at the conv
-        stack's output (self._seg): that loss must go through _optimizer_step, whose backward runs both
-        segments; a bare loss.backward() would stop at the cut."""
-        cfg = self.config
+    def _loss_forward(self, x):
+        """(logits, values) for a minibatch loss: the network's own dtype where the fused loss reads it, and in
+        the segmented data-parallel mode the forward cut at the conv stack's output (self._seg)."""
         keep = self.fused_loss and x.is_cuda
         if self._segmented():
             self.network.grad_split = []
@@ -553,8 +611,15 @@ class PPOAgent(BaseAgent):
             finally:
                 cut, self.network.grad_split = self.network.grad_split, None
             self._seg = cut[0] if len(cut) == 1 else None
-        else:
-            logits, values = self._raw(x, keep)
+            return logits, values
+        return self._raw(x, keep)
+
+    def _minibatch_loss(self, x, masks, actions, old_log_probs, advantages, returns):
+        """(loss, stats) of one minibatch.  In the segmented data-parallel mode the forward is cut at the conv
+        stack's output (self._seg): that loss must go through _optimizer_step, whose backward runs both
+        segments; a bare loss.backward() would stop at the cut."""
+        cfg = self.config
+        logits, values = self._loss_forward(x)
         if self.fused_loss and logits.is_cuda:  # bb_ppo_loss_fused (bb_ppo_loss_forward / _backward otherwise)
             seed = self._seed(logits.device) if torch.is_grad_enabled() and logits.requires_grad else None
             return K.PPOLossFunction.apply(logits, values, masks, actions, old_log_probs, advantages, returns,
@@ -876,6 +941,45 @@ class PPOAgent(BaseAgent):
         self.check_optimizer_guard()
         keys = ("policy_loss", "value_loss", "entropy", "total_loss", "approx_kl", "clip_fraction")
         return dict(zip(keys, m))
+
+    # ------------------------------------------------------- distillation
+    def distill_minibatch(self, x, mask_bits, q, tau: float) -> torch.Tensor:
+        """One optimizer step on the cross-entropy between softmax(q / tau) (``q``: bb_plan_values' per-action
+        values of the minibatch's positions) and the policy under ``mask_bits``: bb_distill_loss_fused on the
+        device, distill_loss_torch on the CPU; backward, gradient all-reduce, clip and Adam are train_minibatch's
+        (_optimizer_step).  The value head gets no gradient.  Returns the 6 statistics (K.DISTILL_STATS) on the
+        device.  Runs eagerly."""
+        logits, _ = self._loss_forward(x)
+        if self.fused_loss and logits.is_cuda:
+            seed = self._seed(logits.device) if torch.is_grad_enabled() and logits.requires_grad else None
+            loss, stats = K.DistillLossFunction.apply(logits, mask_bits, q, float(tau), seed)
+        else:
+            loss, stats = distill_loss_torch(logits, mask_bits, q, float(tau))
+        self._optimizer_step(loss)
+        return stats
+
+    def distill(self, buffer, weights, depth: int = 3, tau: float = 50.0, epochs: int = 1,
+                batch_size: Optional[int] = None) -> Dict[str, float]:
+        """Supervised epochs on the stored positions of ``buffer`` (PackedRolloutBuffer(positions=True)), labelled
+        by the full-hand search: per minibatch one bb_plan_values_pos launch (``weights``, ``depth``; q only, into
+        a scratch kept per minibatch size), the forward pass, the fused loss and the optimizer step, with no host
+        read inside the loop.  Returns the mean statistics under DISTILL_KEYS."""
+        bs = int(batch_size or self.config.batch_size)
+        w = K._weights(weights)
+        acc = torch.zeros(6, dtype=torch.float32, device=self.device)
+        n = 0
+        for _ in range(int(epochs)):
+            for x, mask_bits, board, hand, combo in buffer.get_position_minibatches(bs):
+                q = self._distill_q.get(board.numel())
+                if q is None:
+                    q = self._distill_q[board.numel()] = torch.empty((board.numel(), 192), dtype=torch.int64,
+                                                                     device=board.device)
+                K.plan_values(board, hand, w, depth, combo=combo, out={"q": q})
+                acc += self.distill_minibatch(x, mask_bits, q, tau)
+                n += 1
+        m = (acc / max(n, 1)).tolist()
+        self.check_optimizer_guard()
+        return dict(zip(DISTILL_KEYS, m))
 
     # ----------------------------------------------------------- checkpoint
     def save(self, path: str) -> None:

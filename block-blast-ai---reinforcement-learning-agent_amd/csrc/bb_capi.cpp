@@ -483,6 +483,18 @@ int bb_snapshot(bb_env* env, uint64_t* d_board, uint32_t* d_hand, uint64_t* d_ma
   return BB_OK;
 }
 
+int bb_snapshot_combo(bb_env* env, int32_t* d_combo, void* stream) {
+  if (!env) return BB_ERR_ARG;
+  if (status_fail(env, "bb_snapshot_combo") != BB_OK) return BB_ERR_DEVICE;
+  if (env->broken) return broken_fail(env, "bb_snapshot_combo");
+  DeviceGuard g(env->device);
+  hipError_t st = hipSuccess;
+  if (d_combo)
+    st = hipMemcpyAsync(d_combo, env->d.combo, (size_t)env->n * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+  if (st != hipSuccess) return hip_fail(env, st, "bb_snapshot_combo");
+  return BB_OK;
+}
+
 int bb_get_state(bb_env* env, const bb_state_view* v) {
   if (!env || !v) return BB_ERR_ARG;
   DeviceGuard g(env->device);
@@ -822,6 +834,46 @@ extern "C" int bb_ppo_loss_fused(const bb_ppo_loss_args* a, void* stream) {
   if (rc != BB_OK) return rc;
   hipError_t st = launch_ppo_loss_fused(*a, (hipStream_t)stream);
   return st == hipSuccess ? BB_OK : hip_fail(nullptr, st, "bb_ppo_loss_fused");
+}
+
+namespace {
+// stats: the forward's outputs are required; grad: the backward's.  Every rule by name, before any HIP call.
+int distill_check(const bb_distill_loss_args* a, bool stats, bool grad, const char* what) {
+  const std::string w = std::string(what) + ": ";
+  if (!a) return fail(nullptr, BB_ERR_ARG, w + "NULL argument struct");
+  if (a->B < 0) return fail(nullptr, BB_ERR_ARG, w + "B is negative");
+  if (!(a->tau >= 0.f) || a->tau > 3.402823466e38f) return fail(nullptr, BB_ERR_ARG, w + "tau must be finite and >= 0");
+  if (!a->logits || !a->mask_bits || !a->q) return fail(nullptr, BB_ERR_ARG, w + "logits, mask_bits and q are required");
+  if (stats && (!a->ws || !a->cnt || !a->stats)) return fail(nullptr, BB_ERR_ARG, w + "ws, cnt and stats are required");
+  if (grad && (!a->grad_loss || !a->dlogits)) return fail(nullptr, BB_ERR_ARG, w + "grad_loss and dlogits are required");
+  return BB_OK;
+}
+}  // namespace
+
+extern "C" int64_t bb_distill_loss_workspace_bytes(int32_t B) {
+  if (B < 0) return -1;
+  return distill_loss_workspace_bytes(B);
+}
+
+extern "C" int bb_distill_loss_forward(const bb_distill_loss_args* a, void* stream) {
+  int rc = distill_check(a, true, false, "bb_distill_loss_forward");
+  if (rc != BB_OK || a->B == 0) return rc;
+  hipError_t st = launch_distill_loss_forward(*a, (hipStream_t)stream);
+  return st == hipSuccess ? BB_OK : hip_fail(nullptr, st, "bb_distill_loss_forward");
+}
+
+extern "C" int bb_distill_loss_backward(const bb_distill_loss_args* a, void* stream) {
+  int rc = distill_check(a, false, true, "bb_distill_loss_backward");
+  if (rc != BB_OK || a->B == 0) return rc;
+  hipError_t st = launch_distill_loss_backward(*a, (hipStream_t)stream);
+  return st == hipSuccess ? BB_OK : hip_fail(nullptr, st, "bb_distill_loss_backward");
+}
+
+extern "C" int bb_distill_loss_fused(const bb_distill_loss_args* a, void* stream) {
+  int rc = distill_check(a, true, true, "bb_distill_loss_fused");
+  if (rc != BB_OK || a->B == 0) return rc;
+  hipError_t st = launch_distill_loss_fused(*a, (hipStream_t)stream);
+  return st == hipSuccess ? BB_OK : hip_fail(nullptr, st, "bb_distill_loss_fused");
 }
 
 namespace {

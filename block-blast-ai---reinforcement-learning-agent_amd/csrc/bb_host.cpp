@@ -685,6 +685,13 @@ int bb_snapshot(bb_env* env, uint64_t* d_board, uint32_t* d_hand, uint64_t* d_ma
   return BB_OK;
 }
 
+int bb_snapshot_combo(bb_env* env, int32_t* d_combo, void* stream) {
+  (void)stream;
+  if (!env) return BB_ERR_ARG;
+  if (d_combo) memcpy(d_combo, env->combo.data(), (size_t)env->n * 4);
+  return BB_OK;
+}
+
 int bb_get_state(bb_env* env, const bb_state_view* v) {
   if (!env || !v) return BB_ERR_ARG;
   const size_t n = (size_t)env->n;

@@ -232,6 +232,14 @@ class DeviceEnvBatch:
             "bb_snapshot", self.handle, self.lib,
         )
 
+    def snapshot_combo(self, out: torch.Tensor) -> None:
+        """bb_snapshot_combo: the live combo column into out (int32 [N]); with ``snapshot``'s board and hand a
+        stored position that ``runtime.kernels.plan_values`` can search later."""
+        assert out.dtype == torch.int32 and out.device == self.device and out.is_contiguous() \
+            and out.numel() == self.num_envs
+        L.check(self.lib.bb_snapshot_combo(self.handle, _ptr(out), _stream(self.device)), "bb_snapshot_combo",
+                self.handle, self.lib)
+
     def random_actions(self, mask_bits: torch.Tensor, out: torch.Tensor, seed: int = 0xB10C, step: int = 0):
         L.check(
             self.lib.bb_random_actions(_ptr(mask_bits), self.num_envs, seed, step, self.env_offset, _ptr(out),

@@ -1063,6 +1063,94 @@ class PPOLossFunction(torch.autograd.Function):
 
 
 # ---------------------------------------------------------------------------
+# Policy distillation from the full-hand search, forward and backward (csrc/bb_distill.hip)
+# ---------------------------------------------------------------------------
+DISTILL_STATS = ("cross_entropy", "kl", "target_entropy", "policy_entropy", "agreement", "rows")
+
+
+def _distill_inputs(logits, mask_bits, q):
+    """(logits f32 or bf16 [B, 192], mask_bits int64 [B, 3], q int64 [B, 192]), contiguous, and whether bf16."""
+    _need_cuda(logits, mask_bits, q)
+    if logits.dim() != 2 or logits.shape[1] != 192:
+        raise L.BBNativeError(f"distill_loss: logits must be [B, 192], got {tuple(logits.shape)}")
+    bf16 = logits.dtype == torch.bfloat16
+    logits = logits.contiguous() if bf16 else logits.contiguous().float()
+    b = logits.shape[0]
+    for t, shape, name in ((mask_bits, (b, 3), "mask_bits"), (q, (b, 192), "q")):
+        if t.dtype != torch.int64 or tuple(t.shape) != shape or t.device != logits.device:
+            raise L.BBNativeError(f"distill_loss: {name} must be int64 {list(shape)} on {logits.device}")
+    return (logits, mask_bits.contiguous(), q.contiguous()), bf16
+
+
+def _distill_args(ins, bf16: bool, tau: float, **outs) -> L.DistillLossArgs:
+    logits, mask_bits, q = ins
+    return L.DistillLossArgs(logits=_a(logits), bf16=int(bf16), mask_bits=_a(mask_bits), q=_a(q), B=logits.shape[0],
+                             tau=float(tau), **{k: _a(t) for k, t in outs.items()})
+
+
+def _distill_forward_outs(lib, b: int, dev, cnt=None) -> dict:
+    ws = torch.empty((lib.bb_distill_loss_workspace_bytes(b) + 7) // 8, dtype=torch.float64, device=dev)
+    return dict(ws=ws, cnt=_bgrad_counters(dev, 1) if cnt is None else cnt, stats=torch.empty(6, dtype=torch.float32, device=dev),
+                loss=torch.empty((), dtype=torch.float32, device=dev))
+
+
+def distill_loss(logits: torch.Tensor, mask_bits: torch.Tensor, q: torch.Tensor, tau: float,
+                 cnt: Optional[torch.Tensor] = None):
+    """bb_distill_loss_forward: the cross-entropy between softmax(q / tau) over the masked legal actions
+    (``q`` as ``plan_values`` writes it; tau == 0: the one-hot of the search's action) and the masked policy of
+    ``logits`` (f32 or bf16 [B, 192]) under ``mask_bits`` (int64 [B, 3]).  Returns (loss, stats[6] =
+    DISTILL_STATS); no gradient (DistillLossFunction has one).  ``cnt``: the hand-off counter (one zeroed int32,
+    re-armed by each launch) instead of the stream's, e.g. for a launch captured before any eager one."""
+    ins, bf16 = _distill_inputs(logits, mask_bits, q)
+    lib, dev = L.load(), ins[0].device
+    fwd = _distill_forward_outs(lib, ins[0].shape[0], dev, cnt)
+    L.check(lib.bb_distill_loss_forward(C.byref(_distill_args(ins, bf16, tau, **fwd)), _s(dev)),
+            "bb_distill_loss_forward")
+    return fwd["loss"], fwd["stats"]
+
+
+class DistillLossFunction(torch.autograd.Function):
+    """``distill_loss`` with its gradient for the logits (bb_distill_loss_*).  Returns (loss = cross-entropy,
+    stats[6]); stats carry no gradient.  ``seed``: the tensor the caller will backpropagate the loss with, as for
+    PPOLossFunction: forward and backward then run as one launch (bb_distill_loss_fused) and the backward hands
+    the gradient over when autograd passes that same tensor; any other gradient runs bb_distill_loss_backward."""
+
+    @staticmethod
+    def forward(ctx, logits, mask_bits, q, tau: float, seed: Optional[torch.Tensor] = None):
+        ins, bf16 = _distill_inputs(logits, mask_bits, q)
+        lib, dev = L.load(), ins[0].device
+        fwd = _distill_forward_outs(lib, ins[0].shape[0], dev)
+        ctx.seed, ctx.grads = None, None
+        if seed is not None and seed.is_cuda and seed.dtype == torch.float32 and seed.numel() == 1:
+            dlogits = torch.empty_like(ins[0])
+            a = _distill_args(ins, bf16, tau, grad_loss=seed, dlogits=dlogits, **fwd)
+            L.check(lib.bb_distill_loss_fused(C.byref(a), _s(dev)), "bb_distill_loss_fused")
+            ctx.seed, ctx.grads = seed, dlogits
+        else:
+            L.check(lib.bb_distill_loss_forward(C.byref(_distill_args(ins, bf16, tau, **fwd)), _s(dev)),
+                    "bb_distill_loss_forward")
+        ctx.save_for_backward(*ins)
+        ctx.tau, ctx.bf16, ctx.in_dtype = float(tau), bf16, logits.dtype
+        ctx.mark_non_differentiable(fwd["stats"])
+        ctx.set_materialize_grads(False)
+        return fwd["loss"], fwd["stats"]
+
+    @staticmethod
+    def backward(ctx, grad_loss, grad_stats):
+        if grad_loss is None:
+            return (None,) * 5
+        if ctx.grads is not None and grad_loss is ctx.seed:  # computed by the forward's launch
+            dlogits, ctx.grads = ctx.grads, None
+        else:
+            ins = ctx.saved_tensors
+            dlogits = torch.empty_like(ins[0])
+            a = _distill_args(ins, ctx.bf16, ctx.tau, grad_loss=grad_loss.float().reshape(1).contiguous(),
+                              dlogits=dlogits)
+            L.check(L.load().bb_distill_loss_backward(C.byref(a), _s(ins[0].device)), "bb_distill_loss_backward")
+        return dlogits.to(ctx.in_dtype), None, None, None, None
+
+
+# ---------------------------------------------------------------------------
 # clip_grad_norm_ + Adam, and the Linear layers' autocast casts (csrc/bb_optim.hip)
 # ---------------------------------------------------------------------------
 OPT_MAX_TENSORS = 48  # BB_OPT_MAX_TENSORS

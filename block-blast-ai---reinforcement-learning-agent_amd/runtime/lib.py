@@ -185,6 +185,12 @@ class PpoLossArgs(C.Structure):
                 ("grad_loss", _P), ("dlogits", _P), ("dvalues", _P), ("ws", _P), ("cnt", _P), ("stats", _P),
                 ("loss", _P)]
 
+class DistillLossArgs(C.Structure):
+    """bb_distill_loss_args: grad_loss / dlogits are the backward's, ws / cnt / stats / loss the forward's."""
+    _fields_ = [("logits", _P), ("bf16", _I32), ("mask_bits", _P), ("q", _P), ("B", _I32), ("tau", _F),
+                ("grad_loss", _P), ("dlogits", _P), ("ws", _P), ("cnt", _P), ("stats", _P), ("loss", _P)]
+
+
 # name -> (restype, argtypes); exactly the entry points of include/bbvec.h
 SIGNATURES = {
     "bb_abi_version": (C.c_int, []),
@@ -202,6 +208,7 @@ SIGNATURES = {
     "bb_obs": (C.c_int, [_P, _P, _P, _P, _P, _P]),
     "bb_device_ptrs": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P)]),
     "bb_snapshot": (C.c_int, [_P, _P, _P, _P, _P]),
+    "bb_snapshot_combo": (C.c_int, [_P, _P, _P]),
     "bb_get_state": (C.c_int, [_P, C.POINTER(StateView)]),
     "bb_set_state": (C.c_int, [_P, C.POINTER(StateView)]),
     "bb_debug_counters": (C.c_int, [_P, _P]),
@@ -243,6 +250,10 @@ SIGNATURES = {
     "bb_ppo_loss_forward": (C.c_int, [C.POINTER(PpoLossArgs), _P]),
     "bb_ppo_loss_backward": (C.c_int, [C.POINTER(PpoLossArgs), _P]),
     "bb_ppo_loss_fused": (C.c_int, [C.POINTER(PpoLossArgs), _P]),
+    "bb_distill_loss_workspace_bytes": (C.c_int64, [_I32]),
+    "bb_distill_loss_forward": (C.c_int, [C.POINTER(DistillLossArgs), _P]),
+    "bb_distill_loss_backward": (C.c_int, [C.POINTER(DistillLossArgs), _P]),
+    "bb_distill_loss_fused": (C.c_int, [C.POINTER(DistillLossArgs), _P]),
     "bb_adam_clip_workspace_bytes": (C.c_int64, [_I32, _P]),
     "bb_adam_clip_step": (C.c_int, [_I32, _P, _P, _P, _P, _P, _P, C.c_double, C.c_double, C.c_double, C.c_double, _F,
                                     _P, _P, _P]),
@@ -268,7 +279,8 @@ SIGNATURES = {
 # the env entry points, which the host backend (libbbvec_host.so) exports too
 HOST_SYMBOLS = ("bb_abi_version", "bb_build_id", "bb_create", "bb_destroy", "bb_last_error", "bb_num_envs", "bb_pcg64_seed",
                 "bb_seed", "bb_reset", "bb_step", "bb_rollout", "bb_sync", "bb_obs", "bb_device_ptrs", "bb_snapshot",
-                "bb_get_state", "bb_set_state", "bb_random_actions", "bb_afterstates_pos", "bb_afterstates",
+                "bb_snapshot_combo", "bb_get_state", "bb_set_state", "bb_random_actions", "bb_afterstates_pos",
+                "bb_afterstates",
                 "bb_greedy_actions_pos", "bb_greedy_actions", "bb_plan_actions_pos", "bb_plan_actions",
                 "bb_plan_values_pos", "bb_plan_values", "bb_safe_mask_pos", "bb_safe_mask")
 

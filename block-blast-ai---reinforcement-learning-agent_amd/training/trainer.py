@@ -45,7 +45,9 @@ import torch
 import torch.distributed as dist
 import yaml
 
-from agents.ppo import DP_OVERLAP_MODES, PackedRolloutBuffer, PPOAgent, PPOConfig, broadcast_parameters
+from agents.greedy import DEFAULT_WEIGHTS
+from agents.ppo import (DISTILL_KEYS, DP_OVERLAP_MODES, PackedRolloutBuffer, PPOAgent, PPOConfig,
+                        broadcast_parameters)
 from runtime.device_env import DeviceEnvBatch
 from utils.device import get_device, set_seed
 from utils.logger import Logger, MetricsTracker, TensorBoardLogger
@@ -111,13 +113,14 @@ class DeviceRollout:
     """One rank's env shard + packed rollout storage + episode bookkeeping."""
 
     def __init__(self, num_envs: int, env_offset: int, global_envs: int, seed: int, reward_config,
-                 rollout_steps: int, device: torch.device, safe_mask: bool = False):
+                 rollout_steps: int, device: torch.device, safe_mask: bool = False, positions: bool = False):
         self.safe_mask = bool(safe_mask)  # sample under the hand-safe mask (env.sampling_mask), not the legal one
+        self.positions = bool(positions)  # store each step's combo too: positions the search can label (distill)
         self.n, self.offset, self.global_envs, self.T = num_envs, env_offset, global_envs, rollout_steps
         self.device = device
         self.env = DeviceEnvBatch(num_envs, [seed + env_offset + i for i in range(num_envs)], reward_config,
                                   autoreset=True, device=device, env_offset=env_offset)
-        self.buffer = PackedRolloutBuffer(rollout_steps, num_envs, device)
+        self.buffer = PackedRolloutBuffer(rollout_steps, num_envs, device, positions=self.positions)
         self.x = torch.zeros((num_envs, 4, 8, 8), dtype=torch.float32, device=device)
         self.mask_bits = torch.zeros((num_envs, 3), dtype=torch.int64, device=device)
         self.actions32 = torch.zeros(num_envs, dtype=torch.int32, device=device)
@@ -126,7 +129,7 @@ class DeviceRollout:
         self.ep_moves = torch.zeros((rollout_steps, num_envs), dtype=torch.int32, device=device)
         self._graph = None          # captured rollout (collect(graph=True))
         self._graph_warm = False
-        self._graph_key = None      # (agent, agent.graph_epoch, train mode, safe_mask) the graph was captured for
+        self._graph_key = None      # (agent, agent.graph_epoch, train mode, positions, safe_mask) of the captured graph
         self._step_base = None
 
     def reset(self) -> None:
@@ -146,8 +149,8 @@ class DeviceRollout:
         if not graph or not self.env.device.type == "cuda":
             self._collect_steps(agent)
             return
-        key = (id(agent), agent.graph_epoch, agent.network.training, self.safe_mask)
-        if self._graph_key != key:  # new agent, parameter storage, layout, precision, mode or mask: recapture
+        key = (id(agent), agent.graph_epoch, agent.network.training, self.positions, self.safe_mask)
+        if self._graph_key != key:  # new agent, parameter storage, layout, precision, mode, columns or mask: recapture
             self._graph, self._graph_warm, self._graph_key = None, False, key
         if self._graph is None and not self._graph_warm:
             self._collect_steps(agent)  # eager warm-up: library algorithm selection, workspaces
@@ -173,6 +176,8 @@ class DeviceRollout:
                 env.sampling_mask(buf.mask_bits[t])
             else:
                 env.snapshot(board=buf.board[t], hand=buf.hand[t], mask_bits=buf.mask_bits[t])
+            if self.positions:
+                env.snapshot_combo(buf.combo[t])
             a, lp, v = agent.act_device(self.x, buf.mask_bits[t], env_offset=self.offset, step_base=step_base,
                                         step_add=t)
             buf.actions[t].copy_(a)
@@ -267,12 +272,28 @@ def train(config: Dict[str, Any], resume_path: Optional[str] = None, seed: int =
     # avg_score and best.pt, which see finished episodes only, move slowly; reward_per_step and mid_hand_losses
     # are logged instead of changing their rules.
     safe_mask = bool(train_cfg.get("safe_mask", False))
+    # training.distill: for the first `updates` iterations the rollout's stored positions are labelled by the
+    # full-hand search (bb_plan_values_pos under `weights`, `depth` moves deep) and the policy head is trained on
+    # the cross-entropy against softmax(values / tau) instead of the PPO update (PPOAgent.distill); PPO then goes
+    # on from those weights (the iterations of this call are counted: a resumed run distils again).  tau is in the
+    # units of the values: the default is half a cleared line under the default weights, a hyper-parameter nobody
+    # has tuned.
+    distill_cfg = train_cfg.get("distill") or {}
+    distill_updates = int(distill_cfg.get("updates", 0))
     roll = DeviceRollout(local, rank * local, num_envs, seed, reward_cfg, rollout_steps, device,
-                         safe_mask=safe_mask)
+                         safe_mask=safe_mask, positions=distill_updates > 0)
     if main:
         print(f"Created {num_envs} parallel environments" + (f" ({world} shards of {local})" if world > 1 else ""))
         if safe_mask:
             print("Sampling under the hand-safe mask (training.safe_mask)")
+    if distill_updates > 0:
+        distill_args = dict(weights=dict(distill_cfg.get("weights") or DEFAULT_WEIGHTS),
+                            depth=int(distill_cfg.get("depth", 3)), tau=float(distill_cfg.get("tau", 50.0)),
+                            epochs=int(distill_cfg.get("epochs", 1)))
+        if main:
+            print(f"Distilling the full-hand search into the policy for the first {distill_updates} updates "
+                  f"(training.distill: depth {distill_args['depth']}, tau {distill_args['tau']:g}, "
+                  f"{distill_args['epochs']} epoch(s))")
 
     agent_cfg = ppo_config_from(config)
     agent = PPOAgent(agent_cfg, device)
@@ -342,14 +363,19 @@ def train(config: Dict[str, Any], resume_path: Optional[str] = None, seed: int =
                 tracker.extend("episode_score", scores)
                 tracker.extend("episode_length", moves)
             safe_stats = roll.safe_stats(world) if safe_mask else None
-            last_values = agent.values_device(roll.x)
-            update_metrics = agent.update(roll.buffer, last_values, batch_size=local_batch)
+            distilling = num_updates < distill_updates
+            if distilling:
+                update_metrics = agent.distill(roll.buffer, batch_size=local_batch, **distill_args)
+            else:
+                last_values = agent.values_device(roll.x)
+                update_metrics = agent.update(roll.buffer, last_values, batch_size=local_batch)
             num_updates += 1
             elapsed = time.time() - start
             fps = global_step / elapsed if elapsed > 0 else 0.0  # train.py:214 (includes a resumed start_step)
             if main and num_updates <= 20:
+                shown = "distill_ce" if distilling else "policy_loss"
                 print(f"Update {num_updates}: step={global_step:,}, FPS={fps:.0f}, "
-                      f"policy_loss={update_metrics['policy_loss']:.4f}", flush=True)
+                      f"{shown}={update_metrics[shown]:.4f}", flush=True)
             if num_updates % log_interval == 0 or num_updates <= 10:
                 avg_score = tracker.get_mean("episode_score")
                 metrics = {"step": global_step, "fps": fps, "avg_score": avg_score,
@@ -367,8 +393,9 @@ def train(config: Dict[str, Any], resume_path: Optional[str] = None, seed: int =
                 tb.log_metrics({"performance/avg_score": avg_score, "performance/max_score": metrics["max_score"],
                                 "performance/best_score": best_score, "performance/avg_length": metrics["avg_length"],
                                 "performance/fps": fps, **{f"training/{k}": update_metrics[k] for k in
-                                                           ("policy_loss", "value_loss", "entropy", "approx_kl",
-                                                            "clip_fraction")}}, global_step)
+                                                           (DISTILL_KEYS if distilling else
+                                                            ("policy_loss", "value_loss", "entropy", "approx_kl",
+                                                             "clip_fraction"))}}, global_step)
                 if progress_callback is not None and main:
                     keep = progress_callback({"total_steps": global_step, "mean_score": avg_score,
                                               "best_score": best_score, "episodes": n_episodes, "fps": fps})

@@ -56,7 +56,9 @@ extern "C" {
                                  (additive, still 9) bb_plan_values_out with bb_plan_values(_pos): per-action
                                  full-hand values and the hand-safe mask;
                                  (additive, still 9) bb_safe_mask(_pos): the hand-safe mask alone, by an
-                                 existence search, and the sampling mask (safe, else legal) */
+                                 existence search, and the sampling mask (safe, else legal);
+                                 (additive, still 9) bb_distill_loss_args with bb_distill_loss_forward / _backward /
+                                 _fused: policy distillation from the search values; bb_snapshot_combo */
 
 #define BB_OK 0
 #define BB_ERR_ARG (-1)
@@ -241,6 +243,13 @@ int bb_device_ptrs(bb_env* env, uint64_t** d_board, uint32_t** d_hand, uint64_t*
  * buffers (the packed rollout-buffer record, ppo.py:100-102 without the f32
  * planes): board [N] u64, hand [N] u32, mask [N][3] u64.  Any may be NULL. */
 int bb_snapshot(bb_env* env, uint64_t* d_board, uint32_t* d_hand, uint64_t* d_mask_bits, void* stream);
+
+/* Async device-to-device copy of the live combo column into d_combo [N] i32:
+ * with bb_snapshot's board and hand a stored position that bb_plan_values_pos
+ * can search later (plan values carry the score along the sequence, which
+ * reads combo; prev is read by the afterstate reward only).  Handle checks and
+ * errors are bb_snapshot's. */
+int bb_snapshot_combo(bb_env* env, int32_t* d_combo, void* stream);
 
 /* Synchronous state copies (tests / info / checkpoint).  bb_set_state also
  * overwrites the pcg state when v->rng is given. */
@@ -620,6 +629,58 @@ typedef struct bb_ppo_loss_args {
 int bb_ppo_loss_forward(const bb_ppo_loss_args* a, void* stream);
 int bb_ppo_loss_backward(const bb_ppo_loss_args* a, void* stream);
 int bb_ppo_loss_fused(const bb_ppo_loss_args* a, void* stream);
+
+/* Policy distillation from the full-hand search: the cross-entropy between a
+ * softmax over bb_plan_values' per-action values and the masked policy, fused,
+ * forward and backward.  Per row i < B: logits [B][192] (raw policy head; f32,
+ * or bf16 widened exactly on load, as bb_ppo_loss_args.bf16), mask_bits [B][3]
+ * (layout of bb_obs / bb_snapshot mask_bits: the words the policy samples
+ * under) and q [B][192] (exactly what bb_plan_values writes, INT64_MIN =
+ * illegal).  With M the actions whose mask bit is set, S the a in M with
+ * q[a] != INT64_MIN and qmax the maximum of q over S:
+ *   target   tau > 0: t[a] = exp(float(q[a] - qmax) / tau) / Z over S (the
+ *            difference in int64, exact; below -2^31: t[a] = 0);
+ *            tau == 0: one-hot on the lowest a attaining qmax (bb_plan_actions'
+ *            action)
+ *   student  logpi = log_softmax(logits + where(M, 0, -inf)) by max-subtraction,
+ *            no clamp; pi = exp(logpi)
+ *   ce_i = -sum_{t[a] > 0} t[a] logpi[a]   ht_i = -sum t log t
+ *   hp_i = -sum_M pi log pi
+ *   agree_i = 1 when the lowest-index argmax of the logits over M is the
+ *            lowest-index argmax of q over S
+ * A row with empty S (a finished game, a stale mask) adds 0 to every sum and
+ * all of its gradients are 0.  Forward writes stats[6] = {cross_entropy, kl,
+ * target_entropy, policy_entropy, agreement, rows}: the first five are sums
+ * over rows divided by B, kl = cross_entropy - target_entropy, rows counts the
+ * rows with non-empty S; and, if non-NULL, loss[0] = cross_entropy.  ws, cnt
+ * and the fixed-order sum of fp64 block partials are those of bb_ppo_loss_*
+ * (ws of bb_distill_loss_workspace_bytes(B) bytes; cnt one uint32, zero before
+ * the first launch, re-armed by each), so two launches are bit-identical.
+ * Backward: dlogits[i][a] = grad_loss[0] / B * (pi[a] - t[a]) for a in M, 0
+ * outside M and in every entry of an empty-S row; f32, or bf16 rounded to
+ * nearest even.  bb_distill_loss_fused is both in one launch and equals them
+ * bit for bit.  Asynchronous on the stream, no allocation, graph-capturable
+ * from the first call.  B == 0 does nothing. */
+int64_t bb_distill_loss_workspace_bytes(int32_t B);
+
+typedef struct bb_distill_loss_args {
+  const void* logits;        /* [B][192]                                  all: required */
+  int32_t bf16;
+  const uint64_t* mask_bits; /* [B][3]                                                  */
+  const int64_t* q;          /* [B][192]                                                */
+  int32_t B;                 /* >= 0                                                    */
+  float tau;                 /* >= 0, finite; in the units of q                         */
+  const float* grad_loss;    /* [1]       backward, fused: required; forward: unused    */
+  void* dlogits;             /* [B][192]  backward, fused: required; forward: unused    */
+  double* ws;                /*           forward, fused: required; backward: unused    */
+  uint32_t* cnt;             /* [1]       forward, fused: required; backward: unused    */
+  float* stats;              /* [6]       forward, fused: required; backward: unused    */
+  float* loss;               /* [1]       forward, fused: optional; backward: unused    */
+} bb_distill_loss_args;
+
+int bb_distill_loss_forward(const bb_distill_loss_args* a, void* stream);
+int bb_distill_loss_backward(const bb_distill_loss_args* a, void* stream);
+int bb_distill_loss_fused(const bb_distill_loss_args* a, void* stream);
 
 /* The CNN's 3x3 / padding-1 convolutions over 8x8 boards (network.py:75-117,
  * ResidualBlock network.py:14-30; nn.Conv2d.forward and its autograd
