@@ -266,6 +266,33 @@ class PackedRolloutBuffer:
             x, _ = K.gather_obs(board, hand, mb, b, want_mask=False)
             yield x, mb[b], board[b], hand[b], combo[b]
 
+    def get_guided_minibatches(self, batch_size: int, generator: Optional[torch.Generator] = None, out=None):
+        """Yields (x (B,4,8,8), mask_bits int64 (B,3), actions, old log-probs, normalised advantages, returns,
+        board int64 (B), hand int32 (B), combo int32 (B)) in a random order (the permutation rules of
+        ``get_minibatches``): a PPO minibatch under the words it was sampled under, with the stored position for
+        the search to label (PPOAgent.update_guided).  ``out(B)`` may return 9 tensors to gather into (a captured
+        guided step's inputs and its position scratch, PPOAgent.guided_inputs), or None.  Needs
+        ``positions=True``."""
+        if not hasattr(self, "combo"):
+            raise RuntimeError("get_guided_minibatches needs PackedRolloutBuffer(..., positions=True)")
+        total = self.buffer_size * self.num_envs
+        adv = self.normalized_advantages()
+        perm = self._permutation(total, generator)
+        board, hand, mb = self.board.reshape(total), self.hand.reshape(total), self.mask_bits.reshape(total, 3)
+        rows = (mb, self.actions.reshape(total), self.log_probs.reshape(total), adv, self.returns.reshape(total),
+                board, hand, self.combo.reshape(total))
+        for start in range(0, total, batch_size):
+            b = perm[start:start + batch_size]
+            dst = out(b.numel()) if out is not None else None
+            if dst is not None:  # straight into the step's input buffers: no copies before the replay
+                K.gather_obs(board, hand, mb, b, want_mask=False, out_x=dst[0])
+                for src, o in zip(rows, dst[1:]):
+                    torch.index_select(src, 0, b, out=o)
+                yield tuple(dst)
+                continue
+            x, _ = K.gather_obs(board, hand, mb, b, want_mask=False)
+            yield (x, *(src[b] for src in rows))
+
 
 def categorical_log_prob(probs: torch.Tensor, action: torch.Tensor) -> torch.Tensor:
     """Categorical(probs).log_prob(action) without the validation sync:
@@ -336,6 +363,46 @@ def distill_loss_torch(logits, mask_bits, q, tau: float):
     return loss, stats
 
 
+PPO_KEYS = ("policy_loss", "value_loss", "entropy", "total_loss", "approx_kl", "clip_fraction")
+
+
+def guided_loss_torch(logits, values, mask_bits, actions, old_log_probs, advantages, returns, q, clip: float, coefs):
+    """bbvec.h "search-guided PPO" on torch ops in fp32: ppo_loss_torch's chain under the mask words and
+    distill_loss_torch's, each term with its coefficient.  The CPU path and the chain the fused bb_guided_loss
+    kernels replace.  ``coefs`` = (policy, value, entropy, distill, tau); ``q`` may be None (no distillation
+    half: its six statistics are 0).  A row with an empty mask adds nothing and gets no gradient.  Returns (loss,
+    12 detached statistics: runtime.kernels.GUIDED_STATS)."""
+    policy_coef, value_coef, entropy_coef, distill_coef, tau = (float(c) for c in coefs)
+    logits, values = logits.float(), values.float().reshape(-1)
+    B = logits.shape[0]
+    M = K.mask_bits_to_bool(mask_bits)
+    live = M.any(dim=-1)
+    Me = M | ~live.unsqueeze(-1)  # an empty-M row contributes nothing: keep its chain finite
+    masked = logits + torch.where(Me, torch.zeros_like(logits), torch.full_like(logits, float("-inf")))
+    probs = F.softmax(masked, dim=-1)
+    new_log_probs = categorical_log_prob(probs, actions)
+    entropy = masked_entropy(probs, Me)
+    ratio = torch.exp(new_log_probs - old_log_probs)
+    surr1 = ratio * advantages
+    surr2 = torch.clamp(ratio, 1 - clip, 1 + clip) * advantages
+    mean = lambda v: torch.where(live, v, torch.zeros_like(v)).sum() / B  # noqa: E731
+    policy_loss = mean(-torch.min(surr1, surr2))
+    value_loss = mean((values - returns) ** 2)
+    ent = mean(entropy)
+    loss = policy_coef * policy_loss + value_coef * value_loss + entropy_coef * -ent
+    if q is not None:
+        ce, dstats = distill_loss_torch(logits, mask_bits, q, tau)
+        loss = loss + distill_coef * ce
+    else:
+        dstats = torch.zeros(6, dtype=torch.float32, device=logits.device)
+    with torch.no_grad():
+        approx_kl = mean((ratio - 1) - torch.log(ratio))
+        clip_fraction = mean(((ratio - 1).abs() > clip).float())
+        stats = torch.cat([torch.stack([policy_loss, value_loss, ent, loss, approx_kl, clip_fraction]).detach(),
+                           dstats])
+    return loss, stats
+
+
 class PPOAgent(BaseAgent):
     """ppo.py:221-449."""
 
@@ -401,6 +468,7 @@ class PPOAgent(BaseAgent):
         # update(): called as f(index, stats) after every optimizer step (logging, parity tests)
         self.minibatch_callback: Optional[Callable[[int, torch.Tensor], None]] = None
         self._distill_q: Dict[int, torch.Tensor] = {}  # distill(): the search values' scratch per minibatch size
+        self._guided_pos: Dict[int, Tuple[torch.Tensor, ...]] = {}  # update_guided(): (board, hand, combo) scratch
 
     @property
     def autocast_dtype(self) -> Optional[torch.dtype]:
@@ -811,10 +879,12 @@ class PPOAgent(BaseAgent):
             return None
         return st
 
-    def _capture_step(self, inputs):
+    def _capture_step(self, inputs, loss_fn=None):
         """Capture one optimizer step.  The warm-up steps that graph capture
         needs would change weights, BatchNorm statistics and Adam moments, so
-        those are snapshotted first and restored after the capture."""
+        those are snapshotted first and restored after the capture.
+        ``loss_fn(*inputs)`` -> (loss, stats): the step's loss (the PPO
+        minibatch loss when None; one rank only otherwise)."""
         static_in = [t.detach().clone() for t in inputs]
         with torch.no_grad():
             params = [p.detach().clone() for p in self.network.parameters()]
@@ -833,14 +903,15 @@ class PPOAgent(BaseAgent):
         side.wait_stream(dev_stream)
         world = _world()
         try:
-            return self._capture_on(side, dev_stream, world, static_in, params, bufs, rng, rng0, opt, own)
+            return self._capture_on(side, dev_stream, world, static_in, params, bufs, rng, rng0, opt, own,
+                                    loss_fn or self._minibatch_loss)
         finally:
             own.__exit__(None, None, None)
 
-    def _capture_on(self, side, dev_stream, world, static_in, params, bufs, rng, rng0, opt, own):
+    def _capture_on(self, side, dev_stream, world, static_in, params, bufs, rng, rng0, opt, own, loss_fn):
         with torch.cuda.stream(side):
             for _ in range(3):
-                loss, _ = self._minibatch_loss(*static_in)
+                loss, _ = loss_fn(*static_in)
                 self._optimizer_step(loss)
             # no autograd graph of the warm-up may outlive it: its AccumulateGrad nodes would be reused
             # by the capture's backward and flagged as a stream mismatch
@@ -869,7 +940,7 @@ class PPOAgent(BaseAgent):
             # one graph per step; data parallel: the bucketed all-reduces issued by the backward hooks are
             # captured with it (RCCL collectives in a HIP graph)
             with torch.cuda.graph(graphs[0], stream=side):
-                loss, stats = self._minibatch_loss(*static_in)
+                loss, stats = loss_fn(*static_in)
                 self._optimizer_step(loss)
                 del loss
             flat = self._flat_grad
@@ -980,6 +1051,106 @@ class PPOAgent(BaseAgent):
         m = (acc / max(n, 1)).tolist()
         self.check_optimizer_guard()
         return dict(zip(DISTILL_KEYS, m))
+
+    # -------------------------------------------------- search-guided PPO
+    def _guided_loss(self, x, mask_bits, actions, old_log_probs, advantages, returns, q, coefs, coefs_dev=None):
+        """(loss, 12 statistics) of one guided minibatch: bb_guided_loss_fused on the device (``coefs_dev``, when
+        given, is what the kernel reads instead of ``coefs``), guided_loss_torch on the CPU."""
+        logits, values = self._loss_forward(x)
+        clip = self.config.clip_epsilon
+        if self.fused_loss and logits.is_cuda:
+            seed = self._seed(logits.device) if torch.is_grad_enabled() and logits.requires_grad else None
+            return K.GuidedLossFunction.apply(logits, values, mask_bits, actions, old_log_probs, advantages, returns,
+                                              q, clip, coefs, coefs_dev, seed)
+        return guided_loss_torch(logits, values, mask_bits, actions, old_log_probs, advantages, returns, q, clip,
+                                 coefs)
+
+    def guided_minibatch(self, x, mask_bits, actions, old_log_probs, advantages, returns, q, coefs) -> torch.Tensor:
+        """One optimizer step on policy * PPO surrogate + value * value loss - entropy * entropy + distill *
+        cross-entropy to softmax(q / tau) (bbvec.h "search-guided PPO"), ``coefs`` = (policy, value, entropy,
+        distill, tau) and the clip range the config's; backward, gradient all-reduce, clip and Adam are
+        train_minibatch's (_optimizer_step).  Returns the 12 statistics (K.GUIDED_STATS) on the device.  On a
+        single CUDA device the step is captured once per shape, autocast and mode and replayed, like
+        train_minibatch; the five coefficients live in a device tensor the kernel reads (coefs_dev) and the host
+        writes before a replay, so a schedule does not force a re-capture, and ``q`` is an input buffer of the
+        graph.  Data parallel it runs eagerly."""
+        coefs = tuple(float(c) for c in coefs)
+        inputs = (x, mask_bits, actions, old_log_probs, advantages, returns, q)
+        if not (self.use_graphs and x.is_cuda and self.fused_loss and _world() == 1):
+            loss, stats = self._guided_loss(*inputs, coefs)
+            self._optimizer_step(loss)
+            return stats
+        key = ("guided", tuple(t.shape for t in inputs), self.autocast_dtype, self.network.training)
+        ent = self._graphs.get(key)
+        if ent is None:
+            cdev = torch.tensor(coefs, dtype=torch.float32, device=self.device)
+            graphs, static_in, stats, _ = self._capture_step(
+                inputs, lambda *ins: self._guided_loss(*ins, coefs, cdev))
+            ent = self._graphs[key] = [graphs, static_in, stats, cdev, coefs]
+        graphs, static_in, static_stats, cdev, written = ent
+        for dst, src in zip(static_in, inputs):
+            if dst.data_ptr() != src.data_ptr():  # guided_inputs() buffers are the inputs already
+                dst.copy_(src)
+        if coefs != written:  # a host write, no re-capture: the kernel reads the tensor at every replay
+            cdev.copy_(torch.tensor(coefs, dtype=torch.float32))
+            ent[4] = coefs
+        graphs[0].replay()
+        return static_stats
+
+    def guided_inputs(self, batch: int):
+        """The captured guided step's input tensors for a packed minibatch of ``batch`` rows (x, mask words,
+        actions, old log-probs, advantages, returns) and the position scratch the search reads (board, hand,
+        combo), for PackedRolloutBuffer.get_guided_minibatches(out=...) to gather into; None until that step has
+        been captured (or without graphs)."""
+        ent = self._guided_entry(batch)
+        if ent is None:
+            return None
+        pos = self._guided_pos.get(batch)
+        if pos is None:
+            pos = self._guided_pos[batch] = (torch.empty(batch, dtype=torch.int64, device=self.device),
+                                             torch.empty(batch, dtype=torch.int32, device=self.device),
+                                             torch.empty(batch, dtype=torch.int32, device=self.device))
+        return (*ent[1][:6], *pos)
+
+    def _guided_entry(self, batch: int):
+        if not (self.use_graphs and self.device.type == "cuda"):
+            return None
+        shapes = ((batch, 4, 8, 8), (batch, 3), (batch,), (batch,), (batch,), (batch,), (batch, 192))
+        return self._graphs.get(("guided", tuple(torch.Size(s) for s in shapes), self.autocast_dtype,
+                                 self.network.training))
+
+    def update_guided(self, buffer, last_values, weights, depth: int, tau: float, coefs,
+                      batch_size: Optional[int] = None, epochs: Optional[int] = None) -> Dict[str, float]:
+        """``update`` with the search in the loss: GAE as ``update``, then per minibatch of ``buffer``
+        (PackedRolloutBuffer(positions=True)) one bb_plan_values_pos launch (``weights``, ``depth``; q only,
+        straight into the step's q buffer) and one ``guided_minibatch`` with ``coefs`` = (policy, value, entropy,
+        distill) and ``tau``, over ``epochs`` passes (the config's num_epochs), with no host read inside the loop.
+        Returns the mean statistics: update's 6 keys and the 5 DISTILL_KEYS."""
+        cfg = self.config
+        bs = int(batch_size or cfg.batch_size)
+        if isinstance(last_values, np.ndarray):
+            last_values = torch.from_numpy(last_values)
+        buffer.compute_returns_and_advantages(last_values, cfg.gamma, cfg.gae_lambda)
+        w = K._weights(weights)
+        coefs = (*(float(c) for c in coefs), float(tau))
+        if len(coefs) != 5:
+            raise ValueError("update_guided: coefs = (policy, value, entropy, distill)")
+        acc = torch.zeros(12, dtype=torch.float32, device=self.device)
+        n = 0
+        for _ in range(int(cfg.num_epochs if epochs is None else epochs)):
+            for x, mask_bits, actions, old_lp, adv, ret, board, hand, combo in \
+                    buffer.get_guided_minibatches(bs, out=self.guided_inputs):
+                ent = self._guided_entry(board.numel())
+                q = ent[1][6] if ent is not None else self._distill_q.get(board.numel())
+                if q is None:
+                    q = self._distill_q[board.numel()] = torch.empty((board.numel(), 192), dtype=torch.int64,
+                                                                     device=board.device)
+                K.plan_values(board, hand, w, depth, combo=combo, out={"q": q})
+                acc += self.guided_minibatch(x, mask_bits, actions, old_lp, adv, ret, q, coefs)
+                n += 1
+        m = (acc / max(n, 1)).tolist()
+        self.check_optimizer_guard()
+        return dict(zip(PPO_KEYS + DISTILL_KEYS, m[:11]))
 
     # ----------------------------------------------------------- checkpoint
     def save(self, path: str) -> None:

@@ -877,6 +877,54 @@ extern "C" int bb_distill_loss_fused(const bb_distill_loss_args* a, void* stream
 }
 
 namespace {
+// stats: the forward's outputs are required; grad: the backward's.  Every rule by name, before any HIP call.
+int guided_check(const bb_guided_loss_args* a, bool stats, bool grad, const char* what) {
+  const std::string w = std::string(what) + ": ";
+  if (!a) return fail(nullptr, BB_ERR_ARG, w + "NULL argument struct");
+  if (a->B < 0) return fail(nullptr, BB_ERR_ARG, w + "B is negative");
+  const auto ok = [](float v) { return v >= 0.f && v <= 3.402823466e38f; };  // false for NaN
+  if (!ok(a->tau)) return fail(nullptr, BB_ERR_ARG, w + "tau must be finite and >= 0");
+  if (!ok(a->clip)) return fail(nullptr, BB_ERR_ARG, w + "clip must be finite and >= 0");
+  if (!ok(a->policy_coef) || !ok(a->value_coef) || !ok(a->entropy_coef) || !ok(a->distill_coef))
+    return fail(nullptr, BB_ERR_ARG, w + "coefficients must be finite and >= 0");
+  if (!a->logits || !a->values || !a->mask_bits || !a->actions || !a->old_logp || !a->adv || !a->ret)
+    return fail(nullptr, BB_ERR_ARG, w + "logits, values, mask_bits, actions, old_logp, adv and ret are required");
+  if (!a->q && a->distill_coef != 0.f) return fail(nullptr, BB_ERR_ARG, w + "q is required when distill_coef != 0");
+  if (!a->q && a->coefs_dev) return fail(nullptr, BB_ERR_ARG, w + "q is required with coefs_dev");
+  if (stats && (!a->ws || !a->cnt || !a->stats)) return fail(nullptr, BB_ERR_ARG, w + "ws, cnt and stats are required");
+  if (grad && (!a->grad_loss || !a->dlogits || !a->dvalues))
+    return fail(nullptr, BB_ERR_ARG, w + "grad_loss, dlogits and dvalues are required");
+  return BB_OK;
+}
+}  // namespace
+
+extern "C" int64_t bb_guided_loss_workspace_bytes(int32_t B) {
+  if (B < 0) return -1;
+  return guided_loss_workspace_bytes(B);
+}
+
+extern "C" int bb_guided_loss_forward(const bb_guided_loss_args* a, void* stream) {
+  int rc = guided_check(a, true, false, "bb_guided_loss_forward");
+  if (rc != BB_OK || a->B == 0) return rc;
+  hipError_t st = launch_guided_loss_forward(*a, (hipStream_t)stream);
+  return st == hipSuccess ? BB_OK : hip_fail(nullptr, st, "bb_guided_loss_forward");
+}
+
+extern "C" int bb_guided_loss_backward(const bb_guided_loss_args* a, void* stream) {
+  int rc = guided_check(a, false, true, "bb_guided_loss_backward");
+  if (rc != BB_OK || a->B == 0) return rc;
+  hipError_t st = launch_guided_loss_backward(*a, (hipStream_t)stream);
+  return st == hipSuccess ? BB_OK : hip_fail(nullptr, st, "bb_guided_loss_backward");
+}
+
+extern "C" int bb_guided_loss_fused(const bb_guided_loss_args* a, void* stream) {
+  int rc = guided_check(a, true, true, "bb_guided_loss_fused");
+  if (rc != BB_OK || a->B == 0) return rc;
+  hipError_t st = launch_guided_loss_fused(*a, (hipStream_t)stream);
+  return st == hipSuccess ? BB_OK : hip_fail(nullptr, st, "bb_guided_loss_fused");
+}
+
+namespace {
 int conv_check(int32_t N, int32_t cin, int32_t cout, const char* what) {
   if (N <= 0) return fail(nullptr, BB_ERR_ARG, std::string(what) + ": empty batch");
   if (!conv3x3_supported(cin, cout))

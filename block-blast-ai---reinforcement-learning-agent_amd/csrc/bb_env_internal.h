@@ -183,6 +183,12 @@ hipError_t launch_distill_loss_forward(const bb_distill_loss_args& a, hipStream_
 hipError_t launch_distill_loss_backward(const bb_distill_loss_args& a, hipStream_t s);
 hipError_t launch_distill_loss_fused(const bb_distill_loss_args& a, hipStream_t s);
 
+// bb_guided.hip
+int64_t guided_loss_workspace_bytes(int B);
+hipError_t launch_guided_loss_forward(const bb_guided_loss_args& a, hipStream_t s);
+hipError_t launch_guided_loss_backward(const bb_guided_loss_args& a, hipStream_t s);
+hipError_t launch_guided_loss_fused(const bb_guided_loss_args& a, hipStream_t s);
+
 constexpr int kOptMaxTensors = 48;  // == BB_OPT_MAX_TENSORS
 int64_t adam_clip_workspace_bytes(int count, const int64_t* n);
 hipError_t launch_adam_clip(int count, float* const* p, float* const* g, float* const* m, float* const* v,

@@ -1151,6 +1151,122 @@ class DistillLossFunction(torch.autograd.Function):
 
 
 # ---------------------------------------------------------------------------
+# Search-guided PPO: the PPO loss and the distillation cross-entropy on one softmax (csrc/bb_guided.hip)
+# ---------------------------------------------------------------------------
+GUIDED_STATS = ("policy_loss", "value_loss", "entropy", "total_loss", "approx_kl", "clip_fraction",
+                "cross_entropy", "kl", "target_entropy", "policy_entropy", "agreement", "rows")
+
+
+def _guided_inputs(logits, values, mask_bits, actions, old_logp, adv, ret, q):
+    """The eight row tensors as the kernel reads them (logits / values f32, or bf16 when both are; mask_bits and
+    q int64; q may be None), and whether bf16."""
+    _need_cuda(logits, values, mask_bits, actions, old_logp, adv, ret, q)
+    if logits.dim() != 2 or logits.shape[1] != 192:
+        raise L.BBNativeError(f"guided_loss: logits must be [B, 192], got {tuple(logits.shape)}")
+    b, dev = logits.shape[0], logits.device
+    bf16 = logits.dtype == torch.bfloat16 and values.dtype == torch.bfloat16
+    act = torch.bfloat16 if bf16 else torch.float32
+    for t, shape, name in ((mask_bits, (b, 3), "mask_bits"), (q, (b, 192), "q")):
+        if t is not None and (t.dtype != torch.int64 or tuple(t.shape) != shape or t.device != dev):
+            raise L.BBNativeError(f"guided_loss: {name} must be int64 {list(shape)} on {dev}")
+    if any(t.numel() != b for t in (values, actions, old_logp, adv, ret)):
+        raise L.BBNativeError(f"guided_loss: values, actions, old_logp, adv and ret must hold {b} rows")
+    ins = (logits.contiguous().to(act), values.contiguous().to(act), mask_bits.contiguous(),
+           actions.contiguous().long(), old_logp.contiguous().float(), adv.contiguous().float(),
+           ret.contiguous().float(), None if q is None else q.contiguous())
+    return ins, bf16
+
+
+def _guided_args(ins, bf16: bool, clip: float, coefs, coefs_dev, **outs) -> L.GuidedLossArgs:
+    """bb_guided_loss_args of the eight row tensors, clip, coefs = (policy, value, entropy, distill, tau), the
+    optional device copy of those five, and the call's own tensors by field name."""
+    logits, values, mask_bits, actions, old_logp, adv, ret, q = ins
+    return L.GuidedLossArgs(logits=_a(logits), values=_a(values), bf16=int(bf16), mask_bits=_a(mask_bits),
+                            actions=_a(actions), old_logp=_a(old_logp), adv=_a(adv), ret=_a(ret), q=_a(q),
+                            B=logits.shape[0], clip=float(clip), policy_coef=float(coefs[0]),
+                            value_coef=float(coefs[1]), entropy_coef=float(coefs[2]), distill_coef=float(coefs[3]),
+                            tau=float(coefs[4]), coefs_dev=_a(coefs_dev), **{k: _a(t) for k, t in outs.items()})
+
+
+def _guided_forward_outs(lib, b: int, dev) -> dict:
+    ws = torch.empty((lib.bb_guided_loss_workspace_bytes(b) + 7) // 8, dtype=torch.float64, device=dev)
+    return dict(ws=ws, cnt=_bgrad_counters(dev, 1), stats=torch.empty(12, dtype=torch.float32, device=dev),
+                loss=torch.empty((), dtype=torch.float32, device=dev))
+
+
+def _guided_coefs_dev(coefs_dev, dev):
+    if coefs_dev is not None and (coefs_dev.dtype != torch.float32 or coefs_dev.numel() != 5
+                                  or coefs_dev.device != dev or not coefs_dev.is_contiguous()):
+        raise L.BBNativeError(f"guided_loss: coefs_dev must be 5 contiguous float32 on {dev}")
+    return coefs_dev
+
+
+def guided_loss(logits, values, mask_bits, actions, old_logp, adv, ret, q, clip: float, coefs,
+                coefs_dev: Optional[torch.Tensor] = None):
+    """bb_guided_loss_forward: policy * PPO surrogate + value * value loss - entropy * entropy + distill *
+    cross-entropy to softmax(q / tau), on one masked softmax under ``mask_bits`` (int64 [B, 3]).  ``coefs`` =
+    (policy, value, entropy, distill, tau); ``coefs_dev`` (5 float32 on the device) overrides them, read by the
+    kernel; ``q`` (int64 [B, 192] as ``plan_values`` writes it) may be None when distill is 0 and there is no
+    ``coefs_dev``.  Returns (loss, stats[12] = GUIDED_STATS); no gradient (GuidedLossFunction has one)."""
+    ins, bf16 = _guided_inputs(logits, values, mask_bits, actions, old_logp, adv, ret, q)
+    lib, dev = L.load(), ins[0].device
+    fwd = _guided_forward_outs(lib, ins[0].shape[0], dev)
+    a = _guided_args(ins, bf16, clip, coefs, _guided_coefs_dev(coefs_dev, dev), **fwd)
+    L.check(lib.bb_guided_loss_forward(C.byref(a), _s(dev)), "bb_guided_loss_forward")
+    return fwd["loss"], fwd["stats"]
+
+
+class GuidedLossFunction(torch.autograd.Function):
+    """``guided_loss`` with its gradients for the logits and the values (bb_guided_loss_*).  Returns (total loss,
+    stats[12]); stats carry no gradient.  ``seed``: the tensor the caller will backpropagate the loss with, as for
+    PPOLossFunction: forward and backward then run as one launch (bb_guided_loss_fused) and the backward hands the
+    gradients over when autograd passes that same tensor; any other gradient runs bb_guided_loss_backward."""
+
+    @staticmethod
+    def forward(ctx, logits, values, mask_bits, actions, old_logp, adv, ret, q, clip: float, coefs,
+                coefs_dev: Optional[torch.Tensor] = None, seed: Optional[torch.Tensor] = None):
+        ins, bf16 = _guided_inputs(logits, values, mask_bits, actions, old_logp, adv, ret, q)
+        lib, dev = L.load(), ins[0].device
+        coefs = tuple(float(c) for c in coefs)
+        coefs_dev = _guided_coefs_dev(coefs_dev, dev)
+        fwd = _guided_forward_outs(lib, ins[0].shape[0], dev)
+        ctx.seed, ctx.grads = None, None
+        if seed is not None and seed.is_cuda and seed.dtype == torch.float32 and seed.numel() == 1:
+            dlogits, dvalues = torch.empty_like(ins[0]), torch.empty_like(ins[1])
+            a = _guided_args(ins, bf16, clip, coefs, coefs_dev, grad_loss=seed, dlogits=dlogits, dvalues=dvalues,
+                             **fwd)
+            L.check(lib.bb_guided_loss_fused(C.byref(a), _s(dev)), "bb_guided_loss_fused")
+            ctx.seed, ctx.grads = seed, (dlogits, dvalues)
+        else:
+            a = _guided_args(ins, bf16, clip, coefs, coefs_dev, **fwd)
+            L.check(lib.bb_guided_loss_forward(C.byref(a), _s(dev)), "bb_guided_loss_forward")
+        ctx.has_q = ins[7] is not None
+        ctx.save_for_backward(*[t for t in ins if t is not None], *([coefs_dev] if coefs_dev is not None else []))
+        ctx.call = (bf16, float(clip), coefs, coefs_dev is not None)
+        ctx.in_dtypes = (logits.dtype, values.dtype)
+        ctx.mark_non_differentiable(fwd["stats"])
+        ctx.set_materialize_grads(False)
+        return fwd["loss"], fwd["stats"]
+
+    @staticmethod
+    def backward(ctx, grad_loss, grad_stats):
+        if grad_loss is None:
+            return (None,) * 12
+        if ctx.grads is not None and grad_loss is ctx.seed:  # computed by the forward's launch
+            (dlogits, dvalues), ctx.grads = ctx.grads, None
+        else:
+            bf16, clip, coefs, has_dev = ctx.call
+            saved = list(ctx.saved_tensors)
+            coefs_dev = saved.pop() if has_dev else None
+            ins = tuple(saved) if ctx.has_q else (*saved, None)
+            dlogits, dvalues = torch.empty_like(ins[0]), torch.empty_like(ins[1])
+            a = _guided_args(ins, bf16, clip, coefs, coefs_dev, grad_loss=grad_loss.float().reshape(1).contiguous(),
+                             dlogits=dlogits, dvalues=dvalues)
+            L.check(L.load().bb_guided_loss_backward(C.byref(a), _s(ins[0].device)), "bb_guided_loss_backward")
+        return (dlogits.to(ctx.in_dtypes[0]), dvalues.to(ctx.in_dtypes[1]), *(None,) * 10)
+
+
+# ---------------------------------------------------------------------------
 # clip_grad_norm_ + Adam, and the Linear layers' autocast casts (csrc/bb_optim.hip)
 # ---------------------------------------------------------------------------
 OPT_MAX_TENSORS = 48  # BB_OPT_MAX_TENSORS

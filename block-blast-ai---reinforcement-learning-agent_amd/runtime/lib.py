@@ -191,6 +191,17 @@ class DistillLossArgs(C.Structure):
                 ("grad_loss", _P), ("dlogits", _P), ("ws", _P), ("cnt", _P), ("stats", _P), ("loss", _P)]
 
 
+class GuidedLossArgs(C.Structure):
+    """bb_guided_loss_args: q may be NULL iff distill_coef == 0 and coefs_dev is NULL; coefs_dev (device [5] =
+    policy, value, entropy, distill, tau) overrides the five scalars; grad_loss / dlogits / dvalues are the
+    backward's, ws / cnt / stats / loss the forward's."""
+    _fields_ = [("logits", _P), ("values", _P), ("bf16", _I32), ("mask_bits", _P), ("actions", _P), ("old_logp", _P),
+                ("adv", _P), ("ret", _P), ("q", _P), ("B", _I32), ("clip", _F), ("policy_coef", _F),
+                ("value_coef", _F), ("entropy_coef", _F), ("distill_coef", _F), ("tau", _F), ("coefs_dev", _P),
+                ("grad_loss", _P), ("dlogits", _P), ("dvalues", _P), ("ws", _P), ("cnt", _P), ("stats", _P),
+                ("loss", _P)]
+
+
 # name -> (restype, argtypes); exactly the entry points of include/bbvec.h
 SIGNATURES = {
     "bb_abi_version": (C.c_int, []),
@@ -254,6 +265,10 @@ SIGNATURES = {
     "bb_distill_loss_forward": (C.c_int, [C.POINTER(DistillLossArgs), _P]),
     "bb_distill_loss_backward": (C.c_int, [C.POINTER(DistillLossArgs), _P]),
     "bb_distill_loss_fused": (C.c_int, [C.POINTER(DistillLossArgs), _P]),
+    "bb_guided_loss_workspace_bytes": (C.c_int64, [_I32]),
+    "bb_guided_loss_forward": (C.c_int, [C.POINTER(GuidedLossArgs), _P]),
+    "bb_guided_loss_backward": (C.c_int, [C.POINTER(GuidedLossArgs), _P]),
+    "bb_guided_loss_fused": (C.c_int, [C.POINTER(GuidedLossArgs), _P]),
     "bb_adam_clip_workspace_bytes": (C.c_int64, [_I32, _P]),
     "bb_adam_clip_step": (C.c_int, [_I32, _P, _P, _P, _P, _P, _P, C.c_double, C.c_double, C.c_double, C.c_double, _F,
                                     _P, _P, _P]),

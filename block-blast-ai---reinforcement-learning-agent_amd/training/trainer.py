@@ -280,8 +280,23 @@ def train(config: Dict[str, Any], resume_path: Optional[str] = None, seed: int =
     # has tuned.
     distill_cfg = train_cfg.get("distill") or {}
     distill_updates = int(distill_cfg.get("updates", 0))
+    # training.distill.value_coef (default 0: the path above): when above 0 the distillation iterations run the
+    # guided loss (PPOAgent.update_guided) with policy 0, entropy 0, distill 1 and this value coefficient, so the
+    # critic is fitted on the rollout's returns while the policy is distilled and PPO does not start from an
+    # uninformed value head.
+    distill_value_coef = float(distill_cfg.get("value_coef", 0.0)) if distill_updates > 0 else 0.0
+    # training.guide: in the PPO iterations the loss gains distill_coef * cross-entropy to the search target
+    # (PPOAgent.update_guided); distill_coef goes linearly from `beta` to `beta_final` (default 0) over
+    # `decay_updates` iterations counted from the first PPO iteration and stays there (decay_updates 0: it stays
+    # at beta); an iteration whose coefficient is 0 is the plain PPO update.  depth / tau / weights default to the
+    # distill block's values, or to its defaults.  Absent, or with both betas 0: agent.update as ever, and the
+    # rollout stores no combo.
+    guide_cfg = train_cfg.get("guide") or {}
+    guide_beta, guide_final = float(guide_cfg.get("beta", 0.0)), float(guide_cfg.get("beta_final", 0.0))
+    guide_decay = int(guide_cfg.get("decay_updates", 0))
+    guided = guide_beta > 0 or (guide_final > 0 and guide_decay > 0)
     roll = DeviceRollout(local, rank * local, num_envs, seed, reward_cfg, rollout_steps, device,
-                         safe_mask=safe_mask, positions=distill_updates > 0)
+                         safe_mask=safe_mask, positions=distill_updates > 0 or guided)
     if main:
         print(f"Created {num_envs} parallel environments" + (f" ({world} shards of {local})" if world > 1 else ""))
         if safe_mask:
@@ -294,6 +309,24 @@ def train(config: Dict[str, Any], resume_path: Optional[str] = None, seed: int =
             print(f"Distilling the full-hand search into the policy for the first {distill_updates} updates "
                   f"(training.distill: depth {distill_args['depth']}, tau {distill_args['tau']:g}, "
                   f"{distill_args['epochs']} epoch(s))")
+            if distill_value_coef > 0:
+                print(f"  with the value head fitted on the returns (value_coef {distill_value_coef:g})")
+    if guided:
+        search_args = dict(weights=dict(guide_cfg.get("weights") or distill_cfg.get("weights") or DEFAULT_WEIGHTS),
+                           depth=int(guide_cfg.get("depth", distill_cfg.get("depth", 3))),
+                           tau=float(guide_cfg.get("tau", distill_cfg.get("tau", 50.0))))
+        if main:
+            sched = f"{guide_beta:g} -> {guide_final:g} over {guide_decay} updates" if guide_decay > 0 else f"{guide_beta:g}"
+            print(f"Guiding PPO with the full-hand search (training.guide: beta {sched}, "
+                  f"depth {search_args['depth']}, tau {search_args['tau']:g})")
+
+    def guide_coef(k: int) -> float:
+        """distill_coef of the k-th PPO iteration (k = 0: the first)."""
+        if not guided:
+            return 0.0
+        if guide_decay <= 0:
+            return guide_beta
+        return guide_beta + (guide_final - guide_beta) * min(k, guide_decay) / guide_decay
 
     agent_cfg = ppo_config_from(config)
     agent = PPOAgent(agent_cfg, device)
@@ -364,8 +397,20 @@ def train(config: Dict[str, Any], resume_path: Optional[str] = None, seed: int =
                 tracker.extend("episode_length", moves)
             safe_stats = roll.safe_stats(world) if safe_mask else None
             distilling = num_updates < distill_updates
-            if distilling:
+            beta = 0.0 if distilling else guide_coef(num_updates - distill_updates)
+            if distilling and distill_value_coef > 0:
+                update_metrics = agent.update_guided(
+                    roll.buffer, agent.values_device(roll.x), weights=distill_args["weights"],
+                    depth=distill_args["depth"], tau=distill_args["tau"], coefs=(0.0, distill_value_coef, 0.0, 1.0),
+                    batch_size=local_batch, epochs=distill_args["epochs"])
+            elif distilling:
                 update_metrics = agent.distill(roll.buffer, batch_size=local_batch, **distill_args)
+            elif beta > 0:
+                update_metrics = agent.update_guided(
+                    roll.buffer, agent.values_device(roll.x),
+                    coefs=(1.0, agent_cfg.value_coef, agent_cfg.entropy_coef, beta), batch_size=local_batch,
+                    **search_args)
+                update_metrics["guide_beta"] = beta
             else:
                 last_values = agent.values_device(roll.x)
                 update_metrics = agent.update(roll.buffer, last_values, batch_size=local_batch)
@@ -393,9 +438,9 @@ def train(config: Dict[str, Any], resume_path: Optional[str] = None, seed: int =
                 tb.log_metrics({"performance/avg_score": avg_score, "performance/max_score": metrics["max_score"],
                                 "performance/best_score": best_score, "performance/avg_length": metrics["avg_length"],
                                 "performance/fps": fps, **{f"training/{k}": update_metrics[k] for k in
-                                                           (DISTILL_KEYS if distilling else
-                                                            ("policy_loss", "value_loss", "entropy", "approx_kl",
-                                                             "clip_fraction"))}}, global_step)
+                                                           (*DISTILL_KEYS, "guide_beta", "policy_loss", "value_loss",
+                                                            "entropy", "approx_kl", "clip_fraction")
+                                                           if k in update_metrics}}, global_step)
                 if progress_callback is not None and main:
                     keep = progress_callback({"total_steps": global_step, "mean_score": avg_score,
                                               "best_score": best_score, "episodes": n_episodes, "fps": fps})

@@ -58,7 +58,9 @@ extern "C" {
                                  (additive, still 9) bb_safe_mask(_pos): the hand-safe mask alone, by an
                                  existence search, and the sampling mask (safe, else legal);
                                  (additive, still 9) bb_distill_loss_args with bb_distill_loss_forward / _backward /
-                                 _fused: policy distillation from the search values; bb_snapshot_combo */
+                                 _fused: policy distillation from the search values; bb_snapshot_combo;
+                                 (additive, still 9) bb_guided_loss_args with bb_guided_loss_forward / _backward /
+                                 _fused: the PPO loss and the distillation cross-entropy on one softmax */
 
 #define BB_OK 0
 #define BB_ERR_ARG (-1)
@@ -681,6 +683,79 @@ typedef struct bb_distill_loss_args {
 int bb_distill_loss_forward(const bb_distill_loss_args* a, void* stream);
 int bb_distill_loss_backward(const bb_distill_loss_args* a, void* stream);
 int bb_distill_loss_fused(const bb_distill_loss_args* a, void* stream);
+
+/* Search-guided PPO: the PPO minibatch loss and the distillation cross-entropy
+ * above on one masked softmax, fused, forward and backward:
+ *   total = policy_coef * policy_loss + value_coef * value_loss
+ *           - entropy_coef * entropy + distill_coef * cross_entropy
+ * With policy_coef = 0 it is distillation that also fits the critic on the
+ * rollout's returns; with policy_coef = 1 and a decaying distill_coef it is PPO
+ * regularised towards the search.  Per row i < B: logits [B][192] and values
+ * [B] (f32, or bf16 as bb_ppo_loss_args.bf16), mask_bits [B][3] (the words the
+ * policy sampled under; no f32 mask is read), action, old log-prob, advantage,
+ * return, and q [B][192] (exactly what bb_plan_values writes).  With M the
+ * actions whose mask bit is set:
+ *   PPO half      bb_ppo_loss_*'s row with the mask taken as M: the softmax, the
+ *                 p / sum p normalisation, the log-prob clamp at f32 eps, the
+ *                 masked entropy with its 1e-10 clamps, the ratio, the clipped
+ *                 surrogate, (value - ret)^2, approx_kl and clip_fraction
+ *   distillation  bb_distill_loss_*'s row: S, qmax and the int64 difference, the
+ *                 -2^31 cut-off, tau == 0 the one-hot of the lowest argmax; ce,
+ *                 ht, hp, agree and rows.  A row with empty S adds nothing to
+ *                 these five sums and gets no distillation gradient.
+ * The row maximum and the sum of exponentials are computed once for both.  A
+ * row with empty M adds 0 to every sum and all of its gradients, dvalues
+ * included, are 0.  Forward writes stats[12] = {policy_loss, value_loss,
+ * entropy, total_loss, approx_kl, clip_fraction, cross_entropy, kl,
+ * target_entropy, policy_entropy, agreement, rows}, every mean over B as in the
+ * two kernels, and, if non-NULL, loss[0] = total_loss.  With q == NULL the
+ * distillation half is skipped and the last six statistics are 0.  ws
+ * (bb_guided_loss_workspace_bytes(B) bytes), cnt and the fixed-order sum of
+ * fp64 block partials are those of bb_distill_loss_*: two launches are
+ * bit-identical.  Backward, with g = grad_loss[0]:
+ *   dlogits = g (policy_coef dpolicy - entropy_coef dentropy), by bb_ppo_loss's
+ *             formulas (autograd's rules for min / clamp / log), plus
+ *             g distill_coef / B (pi - t) on M for rows with non-empty S; 0
+ *             outside M
+ *   dvalues = g value_coef 2 (value - ret) / B
+ * f32, or bf16 rounded to nearest even.  bb_guided_loss_fused is both in one
+ * launch and equals them bit for bit.  coefs_dev, when non-NULL, is device
+ * memory [5] = {policy_coef, value_coef, entropy_coef, distill_coef, tau} read
+ * by the kernel instead of the five scalars, so a captured launch can be
+ * replayed under a schedule; its values are the caller's contract.  BB_ERR_ARG,
+ * the rule named in bb_last_error, before any HIP call: a NULL struct or
+ * required field, B < 0, a negative or non-finite tau, clip or coefficient,
+ * q == NULL with distill_coef != 0 or with coefs_dev.  Asynchronous on the
+ * stream, no allocation, graph-capturable from the first call.  B == 0 does
+ * nothing. */
+int64_t bb_guided_loss_workspace_bytes(int32_t B);
+
+typedef struct bb_guided_loss_args {
+  const void* logits;        /* [B][192]                                  required      */
+  const void* values;        /* [B]                                       required      */
+  int32_t bf16;
+  const uint64_t* mask_bits; /* [B][3]                                    required      */
+  const int64_t* actions;    /* [B]                                       required      */
+  const float* old_logp;     /* [B]                                       required      */
+  const float* adv;          /* [B]                                       required      */
+  const float* ret;          /* [B]                                       required      */
+  const int64_t* q;          /* [B][192]  may be NULL iff distill_coef == 0 and coefs_dev == NULL */
+  int32_t B;                 /* >= 0                                                    */
+  float clip, policy_coef, value_coef, entropy_coef, distill_coef; /* >= 0, finite     */
+  float tau;                 /* >= 0, finite; in the units of q                         */
+  const float* coefs_dev;    /* [5]       optional: overrides the five scalars after clip */
+  const float* grad_loss;    /* [1]       backward, fused: required; forward: unused    */
+  void* dlogits;             /* [B][192]  backward, fused: required; forward: unused    */
+  void* dvalues;             /* [B]       backward, fused: required; forward: unused    */
+  double* ws;                /*           forward, fused: required; backward: unused    */
+  uint32_t* cnt;             /* [1]       forward, fused: required; backward: unused    */
+  float* stats;              /* [12]      forward, fused: required; backward: unused    */
+  float* loss;               /* [1]       forward, fused: optional; backward: unused    */
+} bb_guided_loss_args;
+
+int bb_guided_loss_forward(const bb_guided_loss_args* a, void* stream);
+int bb_guided_loss_backward(const bb_guided_loss_args* a, void* stream);
+int bb_guided_loss_fused(const bb_guided_loss_args* a, void* stream);
 
 /* The CNN's 3x3 / padding-1 convolutions over 8x8 boards (network.py:75-117,
  * ResidualBlock network.py:14-30; nn.Conv2d.forward and its autograd
