@@ -45,6 +45,7 @@
 #include <algorithm>
 
 #include "bb_env_internal.h"
+#include "bb_handoff.h"
 
 namespace bb {
 
@@ -381,37 +382,8 @@ constexpr int kBgradCols = 8 * kBgradCL;
 constexpr int kBgradChunk = BB_BGRAD_CFG == 0 ? BB_BGRAD_CHUNK : BB_BGRAD_CFG == 3 ? 512 : 0;  // rows per chunk
 constexpr int kBgradMaxSplit = 64;
 
-// Last-arriver hand-off between workgroups, ordered by the HIP memory model rather than by hardware behaviour:
-// partial sums stored with agent-scope atomic stores (written through, sc1), a workgroup barrier (every wave's
-// stores issued before the count), then one lane counts the workgroup with an agent-scope release add
-// (buffer_wbl2 sc1 + s_waitcnt vmcnt(0) before it: the partials of every wave that passed the barrier are
-// published); the lane whose add returns the last count issues an agent-scope acquire fence (buffer_inv sc1)
-// before its workgroup -- after a barrier, or in the same wave -- loads the partials.  The other workgroups skip
-// the acquire (acq_rel on every add: 1.510 against 1.478 ms per bf16 step, profiles/r06/handoff/).  The re-arm
-// of the counter is an agent-scope atomic store.
-#ifndef BB_HANDOFF_ORDER
-#define BB_HANDOFF_ORDER __ATOMIC_RELEASE  // A/B only: __ATOMIC_RELAXED is the round-5 form (tools/variants.py hrx)
-#endif
-typedef __attribute__((address_space(1))) float gfloat;
-typedef __attribute__((address_space(1))) uint32_t guint32;
-__device__ __forceinline__ void wt_store(float* p, float v) {
-  __hip_atomic_store((gfloat*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ float wt_load(const float* p) {
-  return __hip_atomic_load((const gfloat*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// true in the lane whose add completes the count n (it has then acquired every other workgroup's release)
-__device__ __forceinline__ bool wt_arrive_last(uint32_t* c, uint32_t n) {
-  const bool last = __hip_atomic_fetch_add((guint32*)c, 1u, BB_HANDOFF_ORDER, __HIP_MEMORY_SCOPE_AGENT) == n - 1u;
-  if (last && BB_HANDOFF_ORDER != __ATOMIC_RELAXED) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  return last;
-}
-__device__ __forceinline__ void wt_rearm(uint32_t* c) {
-  __hip_atomic_store((guint32*)c, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// the waves' own stores complete before the barrier that precedes the arrive (the release covers them too;
-// kept so a wave never reaches the barrier with its partial stores still in flight)
-__device__ __forceinline__ void wt_drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+// The split reductions below hand their partial sums to the last workgroup to arrive: bb_handoff.h's wt_store, a
+// drain, a barrier, one lane's wt_arrive_last; that workgroup loads the partials, finalises and re-arms the counter.
 
 struct Philox4 {
   uint32_t v[4];

@@ -13,19 +13,10 @@
 
 #include "bb_device.h"
 #include "bb_env_internal.h"
+#include "bb_loss_rows.h"
 
 namespace bb {
 
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = __fadd_rn(v, __shfl_xor(v, o));
-  return v;
-}
 __device__ __forceinline__ double wave_sum_d(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = __dadd_rn(v, __shfl_xor(v, o));
@@ -39,8 +30,6 @@ __device__ __forceinline__ double wave_incl_scan_d(double v, int lane) {
   }
   return v;
 }
-
-constexpr float kEps = 1.1920928955078125e-07f;  // torch.finfo(float32).eps (clamp_probs)
 
 __global__ void __launch_bounds__(256) masked_sample_kernel(const float* __restrict__ logits,
                                                             const uint64_t* __restrict__ mbits, int n,
@@ -62,32 +51,13 @@ __global__ void __launch_bounds__(256) masked_sample_kernel(const float* __restr
       x[j] = logits[(int64_t)row * 192 + j * 64 + lane];
       v[j] = (mbits[(int64_t)row * 3 + j] >> lane) & 1ull;
     }
-    // logits + where(mask, 0, -inf) then F.softmax (network.py:173-180, 213)
-    float mx = -INFINITY;
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-      if (v[j]) mx = fmaxf(mx, x[j]);
-    mx = wave_max(mx);
-    float e[3];
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      e[j] = v[j] ? expf(__fsub_rn(x[j], mx)) : 0.f;
-      s = __fadd_rn(s, e[j]);
-    }
-    s = wave_sum(s);
-    float pr[3];
-    float s2 = 0.f;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      pr[j] = __fdiv_rn(e[j], s);
-      s2 = __fadd_rn(s2, pr[j]);
-    }
-    s2 = wave_sum(s2);
-    // Categorical(probs): P = probs / probs.sum(-1)
+    // logits + where(mask, 0, -inf) then F.softmax (network.py:173-180, 213); Categorical(probs): P = probs /
+    // probs.sum(-1) (bb_loss_rows.h)
+    const Cat c = categorical(masked_softmax(x, v));
+    const float(&pr)[3] = c.p;
     float P[3];
 #pragma unroll
-    for (int j = 0; j < 3; ++j) P[j] = __fdiv_rn(pr[j], s2);
+    for (int j = 0; j < 3; ++j) P[j] = __fdiv_rn(pr[j], c.sp);
 
     int64_t a;
     if (action_in) {
@@ -143,23 +113,9 @@ __global__ void __launch_bounds__(256) masked_sample_kernel(const float* __restr
         a = last < 0 ? 0 : last;
       }
     }
-    // dist.log_prob(a) = log(clamp(P_a, eps, 1 - eps))
-    const int aj = (int)(a >> 6), al = (int)(a & 63);
-    float pa = __shfl(aj == 0 ? P[0] : (aj == 1 ? P[1] : P[2]), al);
-    float lp = logf(fminf(fmaxf(pa, kEps), 1.f - kEps));
-    // _masked_entropy (network.py:232-262)
-    float ms = 0.f;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) ms = __fadd_rn(ms, v[j] ? pr[j] : 0.f);
-    ms = fmaxf(wave_sum(ms), 1e-10f);
-    float h = 0.f;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      const float q = __fdiv_rn(v[j] ? pr[j] : 0.f, ms);
-      const float lq = logf(fmaxf(q, 1e-10f));
-      h = __fadd_rn(h, v[j] ? __fmul_rn(q, lq) : 0.f);
-    }
-    h = -wave_sum(h);
+    // dist.log_prob(a) = log(clamp(P_a, eps, 1 - eps)) and _masked_entropy (network.py:232-262)
+    const float lp = cat_logp(c, a).logp;
+    const float h = masked_entropy(c, v).ent;
     if (lane == 0) {
       if (action_out) action_out[row] = a;
       if (logp_out) logp_out[row] = lp;

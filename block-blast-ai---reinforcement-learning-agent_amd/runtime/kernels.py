@@ -988,6 +988,52 @@ def conv3x3_prep_multi(weights, defer: bool = False):
 
 
 # ---------------------------------------------------------------------------
+# The three fused losses' shared plumbing (csrc/bb_loss.hip, bb_distill.hip, bb_guided.hip)
+# ---------------------------------------------------------------------------
+def _loss_forward_outs(name: str, nstats: int, b: int, dev, cnt=None) -> dict:
+    """The forward half's tensors of bb_<name>_loss_*: workspace, hand-off counter, stats[nstats], loss."""
+    nbytes = getattr(L.load(), f"bb_{name}_loss_workspace_bytes")(b)
+    return dict(ws=torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev),
+                cnt=_bgrad_counters(dev, 1) if cnt is None else cnt,
+                stats=torch.empty(nstats, dtype=torch.float32, device=dev),
+                loss=torch.empty((), dtype=torch.float32, device=dev))
+
+
+def _loss_call(name: str, form: str, args, dev) -> None:
+    call = f"bb_{name}_loss_{form}"
+    L.check(getattr(L.load(), call)(C.byref(args), _s(dev)), call)
+
+
+def _loss_forward(ctx, name: str, nstats: int, ins, mk_args, seed, grads_like):
+    """bb_<name>_loss_fused when ``seed`` is a usable loss gradient (one float32 on the device; the gradients,
+    shaped like ``grads_like``, are kept on ctx for the backward to hand over), else bb_<name>_loss_forward.
+    ``mk_args(**outs)``: the call's argument struct.  Returns (loss, stats)."""
+    dev = ins[0].device
+    fwd = _loss_forward_outs(name, nstats, ins[0].shape[0], dev)
+    ctx.seed, ctx.grads = None, None
+    if seed is not None and seed.is_cuda and seed.dtype == torch.float32 and seed.numel() == 1:
+        grads = {k: torch.empty_like(t) for k, t in grads_like.items()}
+        _loss_call(name, "fused", mk_args(grad_loss=seed, **grads, **fwd), dev)
+        ctx.seed, ctx.grads = seed, tuple(grads.values())
+    else:
+        _loss_call(name, "forward", mk_args(**fwd), dev)
+    ctx.mark_non_differentiable(fwd["stats"])
+    ctx.set_materialize_grads(False)  # no zero-filled gradient for the statistics
+    return fwd["loss"], fwd["stats"]
+
+
+def _loss_backward(ctx, name: str, grad_loss, mk_args, grads_like):
+    """The gradients the forward's launch computed when autograd passes its seed, else bb_<name>_loss_backward."""
+    if ctx.grads is not None and grad_loss is ctx.seed:
+        grads, ctx.grads = ctx.grads, None
+        return grads
+    grads = {k: torch.empty_like(t) for k, t in grads_like.items()}
+    g = grad_loss.float().reshape(1).contiguous()
+    _loss_call(name, "backward", mk_args(grad_loss=g, **grads), grads_like["dlogits"].device)
+    return tuple(grads.values())
+
+
+# ---------------------------------------------------------------------------
 # PPO minibatch loss, forward and backward (csrc/bb_loss.hip)
 # ---------------------------------------------------------------------------
 def _ppo_loss_args(ins, bf16: bool, coef, **outs) -> L.PpoLossArgs:
@@ -1020,46 +1066,18 @@ class PPOLossFunction(torch.autograd.Function):
         ins = (logits.contiguous().to(act), values.contiguous().to(act), masks.contiguous().float(),
                actions.contiguous().long(), old_log_probs.contiguous().float(), advantages.contiguous().float(),
                returns.contiguous().float())
-        b = ins[0].shape[0]
-        dev = ins[0].device
-        lib = L.load()
-        ws = torch.empty((lib.bb_ppo_loss_workspace_bytes(b) + 7) // 8, dtype=torch.float64, device=dev)
-        cnt = _bgrad_counters(dev, 1)
-        stats = torch.empty(6, dtype=torch.float32, device=dev)
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        coef = (float(clip), float(value_coef), float(entropy_coef))
-        ctx.seed, ctx.grads = None, None
-        fwd = dict(ws=ws, cnt=cnt, stats=stats, loss=loss)
-        if seed is not None and seed.is_cuda and seed.dtype == torch.float32 and seed.numel() == 1:
-            dlogits, dvalues = torch.empty_like(ins[0]), torch.empty_like(ins[1])
-            a = _ppo_loss_args(ins, bf16, coef, grad_loss=seed, dlogits=dlogits, dvalues=dvalues, **fwd)
-            L.check(lib.bb_ppo_loss_fused(C.byref(a), _s(dev)), "bb_ppo_loss_fused")
-            ctx.seed, ctx.grads = seed, (dlogits, dvalues)
-        else:
-            L.check(lib.bb_ppo_loss_forward(C.byref(_ppo_loss_args(ins, bf16, coef, **fwd)), _s(dev)),
-                    "bb_ppo_loss_forward")
+        ctx.call = (bf16, (float(clip), float(value_coef), float(entropy_coef)))
         ctx.save_for_backward(*ins)
-        ctx.coef = coef
-        ctx.bf16 = bf16
-        ctx.mark_non_differentiable(stats)
-        ctx.set_materialize_grads(False)  # no zero-filled gradient for the statistics
-        return loss, stats
+        return _loss_forward(ctx, "ppo", 6, ins, lambda **o: _ppo_loss_args(ins, *ctx.call, **o), seed,
+                             dict(dlogits=ins[0], dvalues=ins[1]))
 
     @staticmethod
     def backward(ctx, grad_loss, grad_stats):
         if grad_loss is None:
             return (None,) * 11
-        if ctx.grads is not None and grad_loss is ctx.seed:  # computed by the forward's launch
-            dlogits, dvalues = ctx.grads
-            ctx.grads = None
-            return dlogits, dvalues, None, None, None, None, None, None, None, None, None
         ins = ctx.saved_tensors
-        g = grad_loss.float().reshape(1).contiguous()
-        dlogits = torch.empty_like(ins[0])
-        dvalues = torch.empty_like(ins[1])
-        a = _ppo_loss_args(ins, ctx.bf16, ctx.coef, grad_loss=g, dlogits=dlogits, dvalues=dvalues)
-        L.check(L.load().bb_ppo_loss_backward(C.byref(a), _s(ins[0].device)), "bb_ppo_loss_backward")
-        return dlogits, dvalues, None, None, None, None, None, None, None, None, None
+        return (*_loss_backward(ctx, "ppo", grad_loss, lambda **o: _ppo_loss_args(ins, *ctx.call, **o),
+                                dict(dlogits=ins[0], dvalues=ins[1])), *(None,) * 9)
 
 
 # ---------------------------------------------------------------------------
@@ -1088,12 +1106,6 @@ def _distill_args(ins, bf16: bool, tau: float, **outs) -> L.DistillLossArgs:
                              tau=float(tau), **{k: _a(t) for k, t in outs.items()})
 
 
-def _distill_forward_outs(lib, b: int, dev, cnt=None) -> dict:
-    ws = torch.empty((lib.bb_distill_loss_workspace_bytes(b) + 7) // 8, dtype=torch.float64, device=dev)
-    return dict(ws=ws, cnt=_bgrad_counters(dev, 1) if cnt is None else cnt, stats=torch.empty(6, dtype=torch.float32, device=dev),
-                loss=torch.empty((), dtype=torch.float32, device=dev))
-
-
 def distill_loss(logits: torch.Tensor, mask_bits: torch.Tensor, q: torch.Tensor, tau: float,
                  cnt: Optional[torch.Tensor] = None):
     """bb_distill_loss_forward: the cross-entropy between softmax(q / tau) over the masked legal actions
@@ -1102,10 +1114,8 @@ def distill_loss(logits: torch.Tensor, mask_bits: torch.Tensor, q: torch.Tensor,
     DISTILL_STATS); no gradient (DistillLossFunction has one).  ``cnt``: the hand-off counter (one zeroed int32,
     re-armed by each launch) instead of the stream's, e.g. for a launch captured before any eager one."""
     ins, bf16 = _distill_inputs(logits, mask_bits, q)
-    lib, dev = L.load(), ins[0].device
-    fwd = _distill_forward_outs(lib, ins[0].shape[0], dev, cnt)
-    L.check(lib.bb_distill_loss_forward(C.byref(_distill_args(ins, bf16, tau, **fwd)), _s(dev)),
-            "bb_distill_loss_forward")
+    fwd = _loss_forward_outs("distill", 6, ins[0].shape[0], ins[0].device, cnt)
+    _loss_call("distill", "forward", _distill_args(ins, bf16, tau, **fwd), ins[0].device)
     return fwd["loss"], fwd["stats"]
 
 
@@ -1118,35 +1128,18 @@ class DistillLossFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, mask_bits, q, tau: float, seed: Optional[torch.Tensor] = None):
         ins, bf16 = _distill_inputs(logits, mask_bits, q)
-        lib, dev = L.load(), ins[0].device
-        fwd = _distill_forward_outs(lib, ins[0].shape[0], dev)
-        ctx.seed, ctx.grads = None, None
-        if seed is not None and seed.is_cuda and seed.dtype == torch.float32 and seed.numel() == 1:
-            dlogits = torch.empty_like(ins[0])
-            a = _distill_args(ins, bf16, tau, grad_loss=seed, dlogits=dlogits, **fwd)
-            L.check(lib.bb_distill_loss_fused(C.byref(a), _s(dev)), "bb_distill_loss_fused")
-            ctx.seed, ctx.grads = seed, dlogits
-        else:
-            L.check(lib.bb_distill_loss_forward(C.byref(_distill_args(ins, bf16, tau, **fwd)), _s(dev)),
-                    "bb_distill_loss_forward")
+        ctx.call, ctx.in_dtype = (bf16, float(tau)), logits.dtype
         ctx.save_for_backward(*ins)
-        ctx.tau, ctx.bf16, ctx.in_dtype = float(tau), bf16, logits.dtype
-        ctx.mark_non_differentiable(fwd["stats"])
-        ctx.set_materialize_grads(False)
-        return fwd["loss"], fwd["stats"]
+        return _loss_forward(ctx, "distill", 6, ins, lambda **o: _distill_args(ins, *ctx.call, **o), seed,
+                             dict(dlogits=ins[0]))
 
     @staticmethod
     def backward(ctx, grad_loss, grad_stats):
         if grad_loss is None:
             return (None,) * 5
-        if ctx.grads is not None and grad_loss is ctx.seed:  # computed by the forward's launch
-            dlogits, ctx.grads = ctx.grads, None
-        else:
-            ins = ctx.saved_tensors
-            dlogits = torch.empty_like(ins[0])
-            a = _distill_args(ins, ctx.bf16, ctx.tau, grad_loss=grad_loss.float().reshape(1).contiguous(),
-                              dlogits=dlogits)
-            L.check(L.load().bb_distill_loss_backward(C.byref(a), _s(ins[0].device)), "bb_distill_loss_backward")
+        ins = ctx.saved_tensors
+        (dlogits,) = _loss_backward(ctx, "distill", grad_loss, lambda **o: _distill_args(ins, *ctx.call, **o),
+                                    dict(dlogits=ins[0]))
         return dlogits.to(ctx.in_dtype), None, None, None, None
 
 
@@ -1188,12 +1181,6 @@ def _guided_args(ins, bf16: bool, clip: float, coefs, coefs_dev, **outs) -> L.Gu
                             tau=float(coefs[4]), coefs_dev=_a(coefs_dev), **{k: _a(t) for k, t in outs.items()})
 
 
-def _guided_forward_outs(lib, b: int, dev) -> dict:
-    ws = torch.empty((lib.bb_guided_loss_workspace_bytes(b) + 7) // 8, dtype=torch.float64, device=dev)
-    return dict(ws=ws, cnt=_bgrad_counters(dev, 1), stats=torch.empty(12, dtype=torch.float32, device=dev),
-                loss=torch.empty((), dtype=torch.float32, device=dev))
-
-
 def _guided_coefs_dev(coefs_dev, dev):
     if coefs_dev is not None and (coefs_dev.dtype != torch.float32 or coefs_dev.numel() != 5
                                   or coefs_dev.device != dev or not coefs_dev.is_contiguous()):
@@ -1209,10 +1196,10 @@ def guided_loss(logits, values, mask_bits, actions, old_logp, adv, ret, q, clip:
     kernel; ``q`` (int64 [B, 192] as ``plan_values`` writes it) may be None when distill is 0 and there is no
     ``coefs_dev``.  Returns (loss, stats[12] = GUIDED_STATS); no gradient (GuidedLossFunction has one)."""
     ins, bf16 = _guided_inputs(logits, values, mask_bits, actions, old_logp, adv, ret, q)
-    lib, dev = L.load(), ins[0].device
-    fwd = _guided_forward_outs(lib, ins[0].shape[0], dev)
+    dev = ins[0].device
+    fwd = _loss_forward_outs("guided", 12, ins[0].shape[0], dev)
     a = _guided_args(ins, bf16, clip, coefs, _guided_coefs_dev(coefs_dev, dev), **fwd)
-    L.check(lib.bb_guided_loss_forward(C.byref(a), _s(dev)), "bb_guided_loss_forward")
+    _loss_call("guided", "forward", a, dev)
     return fwd["loss"], fwd["stats"]
 
 
@@ -1226,43 +1213,25 @@ class GuidedLossFunction(torch.autograd.Function):
     def forward(ctx, logits, values, mask_bits, actions, old_logp, adv, ret, q, clip: float, coefs,
                 coefs_dev: Optional[torch.Tensor] = None, seed: Optional[torch.Tensor] = None):
         ins, bf16 = _guided_inputs(logits, values, mask_bits, actions, old_logp, adv, ret, q)
-        lib, dev = L.load(), ins[0].device
-        coefs = tuple(float(c) for c in coefs)
-        coefs_dev = _guided_coefs_dev(coefs_dev, dev)
-        fwd = _guided_forward_outs(lib, ins[0].shape[0], dev)
-        ctx.seed, ctx.grads = None, None
-        if seed is not None and seed.is_cuda and seed.dtype == torch.float32 and seed.numel() == 1:
-            dlogits, dvalues = torch.empty_like(ins[0]), torch.empty_like(ins[1])
-            a = _guided_args(ins, bf16, clip, coefs, coefs_dev, grad_loss=seed, dlogits=dlogits, dvalues=dvalues,
-                             **fwd)
-            L.check(lib.bb_guided_loss_fused(C.byref(a), _s(dev)), "bb_guided_loss_fused")
-            ctx.seed, ctx.grads = seed, (dlogits, dvalues)
-        else:
-            a = _guided_args(ins, bf16, clip, coefs, coefs_dev, **fwd)
-            L.check(lib.bb_guided_loss_forward(C.byref(a), _s(dev)), "bb_guided_loss_forward")
+        coefs_dev = _guided_coefs_dev(coefs_dev, ins[0].device)
         ctx.has_q = ins[7] is not None
         ctx.save_for_backward(*[t for t in ins if t is not None], *([coefs_dev] if coefs_dev is not None else []))
-        ctx.call = (bf16, float(clip), coefs, coefs_dev is not None)
+        ctx.call = (bf16, float(clip), tuple(float(c) for c in coefs), coefs_dev is not None)
         ctx.in_dtypes = (logits.dtype, values.dtype)
-        ctx.mark_non_differentiable(fwd["stats"])
-        ctx.set_materialize_grads(False)
-        return fwd["loss"], fwd["stats"]
+        return _loss_forward(ctx, "guided", 12, ins, lambda **o: _guided_args(ins, *ctx.call[:3], coefs_dev, **o),
+                             seed, dict(dlogits=ins[0], dvalues=ins[1]))
 
     @staticmethod
     def backward(ctx, grad_loss, grad_stats):
         if grad_loss is None:
             return (None,) * 12
-        if ctx.grads is not None and grad_loss is ctx.seed:  # computed by the forward's launch
-            (dlogits, dvalues), ctx.grads = ctx.grads, None
-        else:
-            bf16, clip, coefs, has_dev = ctx.call
-            saved = list(ctx.saved_tensors)
-            coefs_dev = saved.pop() if has_dev else None
-            ins = tuple(saved) if ctx.has_q else (*saved, None)
-            dlogits, dvalues = torch.empty_like(ins[0]), torch.empty_like(ins[1])
-            a = _guided_args(ins, bf16, clip, coefs, coefs_dev, grad_loss=grad_loss.float().reshape(1).contiguous(),
-                             dlogits=dlogits, dvalues=dvalues)
-            L.check(L.load().bb_guided_loss_backward(C.byref(a), _s(ins[0].device)), "bb_guided_loss_backward")
+        bf16, clip, coefs, has_dev = ctx.call
+        saved = list(ctx.saved_tensors)
+        coefs_dev = saved.pop() if has_dev else None
+        ins = tuple(saved) if ctx.has_q else (*saved, None)
+        dlogits, dvalues = _loss_backward(ctx, "guided", grad_loss,
+                                          lambda **o: _guided_args(ins, bf16, clip, coefs, coefs_dev, **o),
+                                          dict(dlogits=ins[0], dvalues=ins[1]))
         return (dlogits.to(ctx.in_dtypes[0]), dvalues.to(ctx.in_dtypes[1]), *(None,) * 10)
 
 
