@@ -219,22 +219,53 @@ __device__ __forceinline__ void philox_words(uint64_t seed, uint64_t idx, uint64
   philox4x32_10(out, (uint32_t)seed, (uint32_t)(seed >> 32));
 }
 
-// Index of the k-th (0-based) set bit of x (k < popcount(x)).
-__device__ __forceinline__ int select_bit(uint64_t x, uint32_t k) {
-  int pos = 0;
-  uint32_t c = __popc((uint32_t)x);
-  if (k >= c) { k -= c; x >>= 32; pos += 32; }
-  c = __popc((uint32_t)x & 0xFFFFu);
-  if (k >= c) { k -= c; x >>= 16; pos += 16; }
-  c = __popc((uint32_t)x & 0xFFu);
-  if (k >= c) { k -= c; x >>= 8; pos += 8; }
-  c = __popc((uint32_t)x & 0xFu);
-  if (k >= c) { k -= c; x >>= 4; pos += 4; }
-  c = __popc((uint32_t)x & 0x3u);
-  if (k >= c) { k -= c; x >>= 2; pos += 2; }
+// The low t bits of w (1 <= t <= 31): one bit-field extract on the device.
+__host__ __device__ __forceinline__ uint32_t low_bits(uint32_t w, uint32_t t) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_ubfe(w, 0u, t);
+#else
+  return w & ((1u << t) - 1u);
+#endif
+}
+
+// Index of the k-th (0-based) set bit of x (k < popcount(x)).  A binary search on prefix popcounts of the 32-bit
+// half that holds the bit: pos grows by s whenever the low pos + s bits of the half hold at most k set bits.
+// Neither the word nor k moves between the levels (a level is extract, count, compare, select), where the
+// six-level form that shifted the word and reduced k cost 48 VALU (64-bit shifts and two selects per level).
+// Out of contract it answers as that form did (tests/native/select_bit_check.cpp): every level goes up, so 63
+// for k >= popcount(x), x == 0 included -- the quota pass calls it in dummy lanes and drops the result.
+#ifndef BB_SELECT_PREFIX
+#define BB_SELECT_PREFIX 1  // 0: the six-level form (the A/B arm "sel0" of tools/variants.py)
+#endif
+__host__ __device__ __forceinline__ int select_bit(uint64_t x, uint32_t k) {
+#if !BB_SELECT_PREFIX
+  int p6 = 0;
+  uint32_t c = __builtin_popcount((uint32_t)x);
+  if (k >= c) { k -= c; x >>= 32; p6 += 32; }
+  c = __builtin_popcount((uint32_t)x & 0xFFFFu);
+  if (k >= c) { k -= c; x >>= 16; p6 += 16; }
+  c = __builtin_popcount((uint32_t)x & 0xFFu);
+  if (k >= c) { k -= c; x >>= 8; p6 += 8; }
+  c = __builtin_popcount((uint32_t)x & 0xFu);
+  if (k >= c) { k -= c; x >>= 4; p6 += 4; }
+  c = __builtin_popcount((uint32_t)x & 0x3u);
+  if (k >= c) { k -= c; x >>= 2; p6 += 2; }
   c = (uint32_t)x & 1u;
-  if (k >= c) { pos += 1; }
-  return pos;
+  if (k >= c) { p6 += 1; }
+  return p6;
+#else
+  const uint32_t lo = (uint32_t)x, c = (uint32_t)__builtin_popcount(lo);
+  const bool up = k >= c;
+  const uint32_t w = up ? (uint32_t)(x >> 32) : lo;
+  const uint32_t kh = up ? k - c : k;
+  uint32_t pos = 0u;
+#pragma unroll
+  for (uint32_t s = 16u; s; s >>= 1) {
+    const uint32_t t = pos | s;
+    pos = kh >= (uint32_t)__builtin_popcount(low_bits(w, t)) ? t : pos;
+  }
+  return (int)((up ? 32u : 0u) | pos);
+#endif
 }
 
 // Synthetic random policy: the k-th legal action, k = (u * popcount) >> 32,

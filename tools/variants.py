@@ -104,6 +104,11 @@ VARIANTS = {
     "sqe0": ["-DBB_QUICK_EARLY_ROWS=0"],
     "ssl0": ["-DBB_SLOW_SKIP_LEAVES=0"],
     "r13sel": ["-DBB_QUICK_EARLY_ROWS=0", "-DBB_SLOW_SKIP_LEAVES=0"],
+    # round 14: select_bit's six-level form, which is the round-13 build instruction for instruction.  The env
+    # waves' reward operands held in VGPRs (arms "main" against "rtv0", "sel0" against "parent" of
+    # profiles/r14/r14ab_*) did not clear the bar: tools/patches/r14_reward_tail_vgpr.diff
+    "sel0": ["-DBB_SELECT_PREFIX=0"],
+    "sel0diag": ["-DBB_SELECT_PREFIX=0", "-DBB_ASYNC_DIAG=1"],
     # fp32 board convolutions (csrc/bb_conv32.hip): input channels per weight stage, LDS ring slots
     "c32s64": ["-DBB_CONV32_SCI=64"],
     "c32r3": ["-DBB_CONV32_RING=3"],
