@@ -742,6 +742,9 @@ int bn_check(int32_t dtype, int32_t nhwc, int32_t N, int32_t C, int32_t HW) {
   if (nhwc != 0 && nhwc != 1) return fail(nullptr, BB_ERR_ARG, "bb_bn: layout must be 0 (NCHW) or 1 (NHWC)");
   if (N <= 0 || C <= 0 || HW <= 0) return fail(nullptr, BB_ERR_ARG, "bb_bn: empty tensor");
   const int esz = dtype == 1 ? 2 : 4;
+  // the NCHW reduction gives each 16-byte vector of a row its own thread of a 256-thread block (bb_nn.hip plan_for)
+  if (!nhwc && (int64_t)HW * esz > 256 * 16)
+    return fail(nullptr, BB_ERR_ARG, "bb_bn: NCHW HW rows must be at most 256 16-byte vectors (4096 bytes)");
   if (!nhwc && (HW * esz) % 16 != 0) return fail(nullptr, BB_ERR_ARG, "bb_bn: NCHW HW rows must be 16-byte multiples");
   if (nhwc && ((C * esz) % 16 != 0 || 256 % (C * esz / 16) != 0))
     return fail(nullptr, BB_ERR_ARG, "bb_bn: NHWC channel rows must be 16 B x a power of two <= 256");

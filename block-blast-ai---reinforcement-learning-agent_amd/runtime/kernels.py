@@ -382,13 +382,15 @@ def _bn_layout(x: torch.Tensor) -> int:
 
 def bn_fusable(x: torch.Tensor) -> bool:
     """f32/bf16 device tensor, NCHW with HW rows or NHWC with C rows of whole
-    16-byte vectors."""
+    16-byte vectors; an NCHW row of at most 256 of them (bb_bn_workspace_bytes'
+    rule, include/bbvec.h)."""
     if not (x.is_cuda and x.dim() == 4 and x.dtype in _BN_DTYPES and x.numel() > 0):
         return False
     if _bn_layout(x):
         row = x.shape[1] * x.element_size()  # bytes per NHWC row: 16 x a power of two <= 256
         return row % 16 == 0 and 256 % (row // 16) == 0
-    return (x.shape[2] * x.shape[3] * x.element_size()) % 16 == 0
+    row = x.shape[2] * x.shape[3] * x.element_size()
+    return row % 16 == 0 and row <= 256 * 16
 
 
 # BatchNorm batch statistics from the producing convolution's store pass (bb_conv3x3_forward_stats ->

@@ -521,7 +521,11 @@ int bb_gather_obs(const uint64_t* d_board, const uint32_t* d_hand,
  * mask from x.  It writes dx and, where non-NULL, dweight, dbias and
  * dpre_bias = sum of dx per channel.  Three launches each (two with `part`).
  * No atomics: results are deterministic.  All pointers are device pointers;
- * every optional field is "NULL / 0: absent". */
+ * every optional field is "NULL / 0: absent".
+ * Shape rule, checked by all three entry points: an NCHW row (HW elements) is
+ * at most 256 16-byte vectors, so HW <= 1024 for f32 and HW <= 2048 for bf16;
+ * bb_bn_workspace_bytes returns -1 and the launches BB_ERR_ARG for any shape,
+ * dtype or layout outside the rules above. */
 int64_t bb_bn_workspace_bytes(int32_t dtype, int32_t nhwc, int32_t N, int32_t C, int32_t HW);
 
 typedef struct bb_bn_fwd {

@@ -99,7 +99,21 @@ def test_masked_sample_philox_uniform_and_distribution(cuda):
     assert np.abs(counts - p).max() < 0.01
 
 
-@pytest.mark.parametrize("T,N", [(128, 64), (128, 4096), (7, 3), (128, 65536)])  # (128, 65536): config 3
+GUARD = 12345.0  # fills the rows around an output handed in as the inside of a larger buffer
+
+
+def _guarded(shape, cuda):
+    """An f32 buffer of ``shape`` plus one row before and after, filled with GUARD, and its inner view."""
+    buf = torch.full((shape[0] + 2, *shape[1:]), GUARD, dtype=torch.float32, device=cuda)
+    return buf, buf[1:-1]
+
+
+def _guards_intact(buf):
+    return bool((buf[0] == GUARD).all()) and bool((buf[-1] == GUARD).all())
+
+
+# (128, 65536): config 3; (1, 1), (1, 257), (3, 255): one step, one env, the last block one thread over / short
+@pytest.mark.parametrize("T,N", [(128, 64), (128, 4096), (7, 3), (128, 65536), (1, 1), (1, 257), (3, 255)])
 def test_gae_bit_exact(cuda, T, N):
     from runtime import kernels as K
 
@@ -113,6 +127,29 @@ def test_gae_bit_exact(cuda, T, N):
     adv, ret = K.gae(t(r), t(v), t(d), t(last), 0.99, 0.95)
     np.testing.assert_array_equal(adv.cpu().numpy(), adv_ref)
     np.testing.assert_array_equal(ret.cpu().numpy(), ret_ref)
+    # every episode ending at every step, none ending, and no discount; the outputs the inner rows of guarded buffers
+    for dones, gamma, lam in ((np.ones_like(d), 0.99, 0.95), (np.zeros_like(d), 0.99, 0.95), (d, 1.0, 1.0)):
+        adv_ref, ret_ref = OP.gae(r, v, dones, last, gamma, lam)
+        (abuf, adv), (rbuf, ret) = _guarded((T, N), cuda), _guarded((T, N), cuda)
+        K.gae(t(r), t(v), t(dones), t(last), gamma, lam, adv=adv, ret=ret)
+        np.testing.assert_array_equal(adv.cpu().numpy(), adv_ref)
+        np.testing.assert_array_equal(ret.cpu().numpy(), ret_ref)
+        assert _guards_intact(abuf) and _guards_intact(rbuf), "written outside adv / ret [T][N]"
+    # all ones: every step stands alone, adv = r - v
+    np.testing.assert_array_equal(OP.gae(r, v, np.ones_like(d), last, 0.99, 0.95)[0], r - v)
+
+
+def _packed_records(rng, n):
+    board = rng.integers(0, 2 ** 63, n, dtype=np.int64)
+    hand = (rng.integers(0, 37, (n, 3)) * np.array([1, 64, 4096])).sum(1) | (rng.integers(0, 8, n) << 18)
+    hand = hand.astype(np.int32)
+    mbits = rng.integers(-2 ** 63, 2 ** 63 - 1, (n, 3), dtype=np.int64)
+    return board, hand, mbits
+
+
+def _mask_rows(mbits, idx):
+    bits = ((mbits.view(np.uint64)[idx][:, :, None] >> np.arange(64, dtype=np.uint64)) & np.uint64(1))
+    return bits.reshape(-1, 192).astype(np.float32)
 
 
 def test_gather_obs_expansion(cuda):
@@ -121,10 +158,7 @@ def test_gather_obs_expansion(cuda):
 
     rng = np.random.default_rng(0)
     n = 3000
-    board = rng.integers(0, 2 ** 63, n, dtype=np.int64)
-    hand = (rng.integers(0, 37, (n, 3)) * np.array([1, 64, 4096])).sum(1) | (rng.integers(0, 8, n) << 18)
-    hand = hand.astype(np.int32)
-    mbits = rng.integers(-2 ** 63, 2 ** 63 - 1, (n, 3), dtype=np.int64)
+    board, hand, mbits = _packed_records(rng, n)
     idx = rng.permutation(n)[:1000]
     x, mf = K.gather_obs(torch.from_numpy(board).to(cuda), torch.from_numpy(hand).to(cuda),
                          torch.from_numpy(mbits).to(cuda), torch.from_numpy(idx).to(cuda))
@@ -134,6 +168,48 @@ def test_gather_obs_expansion(cuda):
     assert np.array_equal(x.cpu().numpy()[:, 1:], exp_pieces)
     bits = ((mbits.view(np.uint64)[idx][:, :, None] >> np.arange(64, dtype=np.uint64)) & np.uint64(1))
     assert np.array_equal(mf.cpu().numpy(), bits.reshape(-1, 192).astype(np.float32))
+    # one row; duplicate indices; either output alone; the outputs the inner rows of guarded buffers
+    dev = [torch.from_numpy(a).to(cuda) for a in (board, hand, mbits)]
+    for idx in (np.array([n - 1]), np.array([7, 7, 0, 7, n - 1, 0, 7]), rng.integers(0, n, 259)):
+        k = idx.size
+        want_x = np.concatenate([board_planes(board.view(np.uint64)[idx])[:, None],
+                                 piece_planes(hand.view(np.uint32)[idx])], axis=1)
+        want_m = _mask_rows(mbits, idx)
+        di = torch.from_numpy(idx).to(cuda)
+        for wx, wm in ((True, True), (True, False), (False, True)):
+            (xbuf, ox), (mbuf, om) = _guarded((k, 4, 8, 8), cuda), _guarded((k, 192), cuda)
+            x, mf = K.gather_obs(*dev, di, want_x=wx, want_mask=wm, out_x=ox, out_mask=om)
+            assert (x is not None) == wx and (mf is not None) == wm
+            if wx:
+                assert x.data_ptr() == ox.data_ptr() and np.array_equal(ox.cpu().numpy(), want_x)
+            else:
+                assert bool((xbuf == GUARD).all()), "x written though not wanted"
+            if wm:
+                assert mf.data_ptr() == om.data_ptr() and np.array_equal(om.cpu().numpy(), want_m)
+            else:
+                assert bool((mbuf == GUARD).all()), "mask written though not wanted"
+            assert _guards_intact(xbuf) and _guards_intact(mbuf), "written outside x [n][4][8][8] / mask [n][192]"
+
+
+def test_gather_obs_above_the_grid_cap(cuda):
+    """262,144 + 77 rows: more 16-byte chunks of x than the expand kernels' 65,536 blocks hold, so their grid-stride
+    loops run.  On the host: the first 64, the last 141 and 2,000 random rows; on the device: the guard rows."""
+    from runtime import kernels as K
+    from environment._host import board_planes, piece_planes
+
+    rng = np.random.default_rng(262144)
+    src, n = 5000, 262144 + 77
+    board, hand, mbits = _packed_records(rng, src)
+    idx = rng.integers(0, src, n)
+    (xbuf, ox), (mbuf, om) = _guarded((n, 4, 8, 8), cuda), _guarded((n, 192), cuda)
+    K.gather_obs(*[torch.from_numpy(a).to(cuda) for a in (board, hand, mbits, idx)], out_x=ox, out_mask=om)
+    assert _guards_intact(xbuf) and _guards_intact(mbuf), "written outside x [n][4][8][8] / mask [n][192]"
+    rows = np.unique(np.concatenate([np.arange(64), np.arange(n - 141, n), rng.integers(0, n, 2000)]))
+    dr = torch.from_numpy(rows).to(cuda)
+    x, mf = ox[dr].cpu().numpy(), om[dr].cpu().numpy()
+    assert np.array_equal(x[:, 0], board_planes(board.view(np.uint64)[idx[rows]]))
+    assert np.array_equal(x[:, 1:], piece_planes(hand.view(np.uint32)[idx[rows]]))
+    assert np.array_equal(mf, _mask_rows(mbits, idx[rows]))
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
