@@ -5,8 +5,9 @@ The reference has no baseline players; these give a checkpoint's evaluation some
 device the envs live on: ``GreedyAgent`` through the fused ``bb_greedy_actions`` kernel (the arg-max of an
 integer value over the afterstates of the 192 actions, csrc/bb_lookahead.hip), ``RandomAgent`` through the
 Philox random-legal policy ``bb_random_actions``.  ``HandPlanAgent`` searches every way to play out the hand
-(``bb_plan_actions``, the fused search kernel of the same file; ``evaluate.py --agent plan``).  ``device="cpu"``
-runs them on the host backend.
+(``bb_plan_actions``, the fused search kernel of the same file; ``evaluate.py --agent plan``).
+``PopulationPlanAgent`` is that search with weights of its own for every env (``bb_plan_actions_each``), which
+``evaluation/tune.py`` tunes the weights with.  ``device="cpu"`` runs them on the host backend.
 """
 from __future__ import annotations
 
@@ -132,6 +133,41 @@ class HandPlanAgent(GreedyAgent):
         if depth not in (1, 2, 3):
             raise ValueError(f"depth must be 1, 2 or 3, not {depth}")
         self.depth = depth
+
+
+class PopulationPlanAgent(BaseAgent):
+    """One ``HandPlanAgent`` per env, each with weights of its own, all searched in one launch per move
+    (``bb_plan_actions_each``).  ``rows``: int32 [N, 8], env i's weights in the order of ``L.GREEDY_FIELDS``
+    (``runtime.kernels.weight_rows`` makes them from dicts); they are moved to the agent's device.  ``depth`` 1..3
+    is the search depth; ``depth=0`` asks for the one-ply greedy kernel (``bb_greedy_actions_each``), which chooses
+    what depth 1 chooses.  Only ``act_env`` is offered: the agent is tied to a ``DeviceEnvBatch`` of N envs
+    (``evaluation/tune.py`` plays a population of candidate weights with it)."""
+
+    def __init__(self, rows: torch.Tensor, depth: int = 3, device=None):
+        from runtime.device_env import resolve_device
+
+        super().__init__(resolve_device(device))
+        if int(depth) not in (0, 1, 2, 3):
+            raise ValueError(f"depth must be 0 (the one-ply greedy kernel), 1, 2 or 3, not {depth}")
+        self.depth = int(depth)
+        self.rows = rows.to(self.device).contiguous()
+
+    def act_env(self, env_batch, out: torch.Tensor) -> torch.Tensor:
+        if self.depth == 0:
+            return env_batch.greedy_actions_each(out, self.rows)
+        return env_batch.plan_actions_each(out, self.rows, self.depth)
+
+    def select_action(self, observation: Dict[str, Any], deterministic: bool = True) -> Tuple[int, Dict[str, Any]]:
+        raise NotImplementedError("PopulationPlanAgent plays a DeviceEnvBatch (act_env); for one game use HandPlanAgent")
+
+    def update(self, *args, **kwargs) -> Dict[str, float]:
+        return {}
+
+    def save(self, path: str) -> None:
+        raise NotImplementedError("a population has no single weights file; save the HandPlanAgent of one row")
+
+    def load(self, path: str) -> None:
+        raise NotImplementedError("a population has no single weights file; load a HandPlanAgent")
 
 
 class RandomAgent(BaseAgent):

@@ -644,6 +644,36 @@ int bb_plan_actions(bb_env* env, const bb_greedy_weights* w, int32_t depth, cons
   });
 }
 
+// One row of weights per position (greedy_each_kernel, plan_each_kernel): d_w is device memory
+int bb_greedy_actions_each_pos(const bb_positions* pos, int32_t n, const bb_greedy_weights* d_w, int32_t* d_action,
+                               int64_t* d_value, void* stream) {
+  return look_pos_call("bb_greedy_actions_each_pos", bb_look_rules::greedy_actions_each_pos(pos, n, d_w, d_action), [&] {
+    return launch_greedy_each(pos->board, pos->hand, pos->combo, n, d_w, d_action, d_value, (hipStream_t)stream);
+  });
+}
+
+int bb_greedy_actions_each(bb_env* env, const bb_greedy_weights* d_w, int32_t* d_action, int64_t* d_value,
+                           void* stream) {
+  return look_env_call(env, "bb_greedy_actions_each", bb_look_rules::greedy_actions_each(d_w, d_action), [&] {
+    return launch_greedy_each(env->d.board, env->d.hand, env->d.combo, env->n, d_w, d_action, d_value,
+                              (hipStream_t)stream);
+  });
+}
+
+int bb_plan_actions_each_pos(const bb_positions* pos, int32_t n, const bb_greedy_weights* d_w, int32_t depth,
+                             const bb_plan_out* out, void* stream) {
+  return look_pos_call("bb_plan_actions_each_pos", bb_look_rules::plan_actions_each_pos(pos, n, d_w, depth, out), [&] {
+    return launch_plan_each(pos->board, pos->hand, pos->combo, n, d_w, depth, *out, (hipStream_t)stream);
+  });
+}
+
+int bb_plan_actions_each(bb_env* env, const bb_greedy_weights* d_w, int32_t depth, const bb_plan_out* out,
+                         void* stream) {
+  return look_env_call(env, "bb_plan_actions_each", bb_look_rules::plan_actions_each(d_w, depth, out), [&] {
+    return launch_plan_each(env->d.board, env->d.hand, env->d.combo, env->n, d_w, depth, *out, (hipStream_t)stream);
+  });
+}
+
 // Per-action full-hand values (plan_values_kernel)
 int bb_plan_values_pos(const bb_positions* pos, int32_t n, const bb_greedy_weights* w, int32_t depth,
                        const bb_plan_values_out* out, void* stream) {

@@ -100,6 +100,11 @@ hipError_t launch_afterstates(const uint64_t* board, const uint32_t* hand, const
                               int n, const bb_reward_cfg& cfg, const bb_afterstate_out& out, hipStream_t s);
 hipError_t launch_greedy(const uint64_t* board, const uint32_t* hand, const int32_t* combo, int n,
                          const bb_greedy_weights& w, int32_t* action, int64_t* value, hipStream_t s);
+// launch_greedy / launch_plan with w = rows[i] for position i (bb_lookahead.hip): rows is device memory [n]
+hipError_t launch_greedy_each(const uint64_t* board, const uint32_t* hand, const int32_t* combo, int n,
+                              const bb_greedy_weights* rows, int32_t* action, int64_t* value, hipStream_t s);
+hipError_t launch_plan_each(const uint64_t* board, const uint32_t* hand, const int32_t* combo, int n,
+                            const bb_greedy_weights* rows, int depth, const bb_plan_out& out, hipStream_t s);
 // full-hand lookahead (bb_lookahead.hip): depth 1..3, out.action required
 hipError_t launch_plan(const uint64_t* board, const uint32_t* hand, const int32_t* combo, int n,
                        const bb_greedy_weights& w, int depth, const bb_plan_out& out, hipStream_t s);

@@ -366,10 +366,12 @@ void afterstates_host(const uint64_t* board, const uint32_t* hand, const int32_t
   }
 }
 
+// `each`: w is the first of n rows and position i takes w[i] (the _each forms); else every position takes w[0]
 void greedy_host(const uint64_t* board, const uint32_t* hand, const int32_t* combo, int32_t n,
-                 const bb_greedy_weights& w, int32_t* action, int64_t* value) {
+                 const bb_greedy_weights* rows, bool each, int32_t* action, int64_t* value) {
 #pragma omp parallel for schedule(static)
   for (int32_t i = 0; i < n; ++i) {
+    const bb_greedy_weights& w = rows[each ? i : 0];
     int64_t best = INT64_MIN;
     int32_t best_a = 0;
     for (int act = 0; act < 192; ++act) {  // ascending: a later action must be strictly better
@@ -421,9 +423,10 @@ void plan_dfs(uint64_t B, uint32_t hand, int combo, int depth, int ply, int64_t 
 }
 
 void plan_host(const uint64_t* board, const uint32_t* hand, const int32_t* combo, int32_t n,
-               const bb_greedy_weights& w, int depth, const bb_plan_out& out) {
+               const bb_greedy_weights* rows, bool each, int depth, const bb_plan_out& out) {  // rows: as greedy_host
 #pragma omp parallel for schedule(dynamic, 1)  // the trees differ by orders of magnitude
   for (int32_t i = 0; i < n; ++i) {
+    const bb_greedy_weights& w = rows[each ? i : 0];
     PlanBest best{INT64_MIN, {-1, -1, -1}, 0, false};
     int32_t seq[3];
     plan_dfs(board[i], hand[i], combo ? combo[i] : 0, depth, 0, 0, seq, w, best);
@@ -771,7 +774,7 @@ int bb_greedy_actions_pos(const bb_positions* pos, int32_t n, const bb_greedy_we
                           int64_t* d_value, void* stream) {
   (void)stream;
   if (int rc = refused(nullptr, "bb_greedy_actions_pos", R::greedy_actions_pos(pos, n, w, d_action))) return rc;
-  greedy_host(pos->board, pos->hand, pos->combo, n, *w, d_action, d_value);
+  greedy_host(pos->board, pos->hand, pos->combo, n, w, false, d_action, d_value);
   return BB_OK;
 }
 
@@ -779,7 +782,7 @@ int bb_greedy_actions(bb_env* env, const bb_greedy_weights* w, int32_t* d_action
   (void)stream;
   if (!env) return BB_ERR_ARG;
   if (int rc = refused(env, "bb_greedy_actions", R::greedy_actions(w, d_action))) return rc;
-  greedy_host(env->board.data(), env->hand.data(), env->combo.data(), env->n, *w, d_action, d_value);
+  greedy_host(env->board.data(), env->hand.data(), env->combo.data(), env->n, w, false, d_action, d_value);
   return BB_OK;
 }
 
@@ -787,7 +790,7 @@ int bb_plan_actions_pos(const bb_positions* pos, int32_t n, const bb_greedy_weig
                         const bb_plan_out* out, void* stream) {
   (void)stream;
   if (int rc = refused(nullptr, "bb_plan_actions_pos", R::plan_actions_pos(pos, n, w, depth, out))) return rc;
-  plan_host(pos->board, pos->hand, pos->combo, n, *w, depth, *out);
+  plan_host(pos->board, pos->hand, pos->combo, n, w, false, depth, *out);
   return BB_OK;
 }
 
@@ -795,7 +798,45 @@ int bb_plan_actions(bb_env* env, const bb_greedy_weights* w, int32_t depth, cons
   (void)stream;
   if (!env) return BB_ERR_ARG;
   if (int rc = refused(env, "bb_plan_actions", R::plan_actions(w, depth, out))) return rc;
-  plan_host(env->board.data(), env->hand.data(), env->combo.data(), env->n, *w, depth, *out);
+  plan_host(env->board.data(), env->hand.data(), env->combo.data(), env->n, w, false, depth, *out);
+  return BB_OK;
+}
+
+// One row of weights per position: d_w is host memory here, [n] ([num_envs]) rows
+
+int bb_greedy_actions_each_pos(const bb_positions* pos, int32_t n, const bb_greedy_weights* d_w, int32_t* d_action,
+                               int64_t* d_value, void* stream) {
+  (void)stream;
+  if (int rc = refused(nullptr, "bb_greedy_actions_each_pos", R::greedy_actions_each_pos(pos, n, d_w, d_action)))
+    return rc;
+  greedy_host(pos->board, pos->hand, pos->combo, n, d_w, true, d_action, d_value);
+  return BB_OK;
+}
+
+int bb_greedy_actions_each(bb_env* env, const bb_greedy_weights* d_w, int32_t* d_action, int64_t* d_value,
+                           void* stream) {
+  (void)stream;
+  if (!env) return BB_ERR_ARG;
+  if (int rc = refused(env, "bb_greedy_actions_each", R::greedy_actions_each(d_w, d_action))) return rc;
+  greedy_host(env->board.data(), env->hand.data(), env->combo.data(), env->n, d_w, true, d_action, d_value);
+  return BB_OK;
+}
+
+int bb_plan_actions_each_pos(const bb_positions* pos, int32_t n, const bb_greedy_weights* d_w, int32_t depth,
+                             const bb_plan_out* out, void* stream) {
+  (void)stream;
+  if (int rc = refused(nullptr, "bb_plan_actions_each_pos", R::plan_actions_each_pos(pos, n, d_w, depth, out)))
+    return rc;
+  plan_host(pos->board, pos->hand, pos->combo, n, d_w, true, depth, *out);
+  return BB_OK;
+}
+
+int bb_plan_actions_each(bb_env* env, const bb_greedy_weights* d_w, int32_t depth, const bb_plan_out* out,
+                         void* stream) {
+  (void)stream;
+  if (!env) return BB_ERR_ARG;
+  if (int rc = refused(env, "bb_plan_actions_each", R::plan_actions_each(d_w, depth, out))) return rc;
+  plan_host(env->board.data(), env->hand.data(), env->combo.data(), env->n, d_w, true, depth, *out);
   return BB_OK;
 }
 

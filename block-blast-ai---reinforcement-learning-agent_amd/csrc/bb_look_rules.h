@@ -1,12 +1,12 @@
-// bb_look_rules.h -- the argument rules of the ten lookahead entry points of include/bbvec.h, one copy for
+// bb_look_rules.h -- the argument rules of the fourteen lookahead entry points of include/bbvec.h, one copy for
 // both backends (csrc/bb_capi.cpp and csrc/bb_host.cpp).  Plain C++, nothing from HIP.
 //
 // Each function returns the rule an argument set breaks, as the text that follows "<entry point>: " in
 // bb_last_error, or nullptr when the call is accepted.  A refusal is BB_ERR_ARG and comes before any HIP call.
 // The handle forms check the handle themselves, first: a NULL env is a bare BB_ERR_ARG with no text.
 //
-// Asymmetries that are part of the ABI as it stands: bb_afterstates_pos, bb_greedy_actions_pos and
-// bb_plan_actions_pos refuse n == 0 and answer every broken rule with one text; bb_plan_values_pos accepts n == 0
+// Asymmetries that are part of the ABI as it stands: bb_afterstates_pos, bb_greedy_actions(_each)_pos and
+// bb_plan_actions(_each)_pos refuse n == 0 and answer every broken rule with one text; bb_plan_values_pos accepts n == 0
 // (and does nothing) and names the rule that broke, and so does bb_safe_mask_pos.
 #pragma once
 #include <stdint.h>
@@ -43,6 +43,27 @@ inline const char* plan_actions_pos(const bb_positions* pos, int32_t n, const bb
                                     const bb_plan_out* out) {
   return no_positions(pos) || n <= 0 || !w || !out || !out->action || bad_depth(depth)
              ? "positions (board, hand), n > 0, weights, depth in 1..3 and out->action are required"
+             : nullptr;
+}
+
+// the per-position forms (bb_*_each): the uniform form's rule with "weight rows" for "weights"
+inline const char* greedy_actions_each(const bb_greedy_weights* d_w, const int32_t* d_action) {
+  return !d_w || !d_action ? "weight rows and d_action are required" : nullptr;
+}
+inline const char* greedy_actions_each_pos(const bb_positions* pos, int32_t n, const bb_greedy_weights* d_w,
+                                           const int32_t* d_action) {
+  return no_positions(pos) || n <= 0 || !d_w || !d_action
+             ? "positions (board, hand), n > 0, weight rows and d_action are required"
+             : nullptr;
+}
+inline const char* plan_actions_each(const bb_greedy_weights* d_w, int32_t depth, const bb_plan_out* out) {
+  return !d_w || !out || !out->action || bad_depth(depth) ? "weight rows, depth in 1..3 and out->action are required"
+                                                          : nullptr;
+}
+inline const char* plan_actions_each_pos(const bb_positions* pos, int32_t n, const bb_greedy_weights* d_w,
+                                         int32_t depth, const bb_plan_out* out) {
+  return no_positions(pos) || n <= 0 || !d_w || !out || !out->action || bad_depth(depth)
+             ? "positions (board, hand), n > 0, weight rows, depth in 1..3 and out->action are required"
              : nullptr;
 }
 

@@ -1,4 +1,4 @@
-// bb_lookahead.hip -- one-ply lookahead (gfx950): bb_afterstates / bb_greedy_actions of include/bbvec.h.
+// bb_lookahead.hip -- one-ply lookahead (gfx950): bb_afterstates / bb_greedy_actions(_each) of include/bbvec.h.
 //
 // The deterministic half of a step for all 192 actions of a position: what engine.py:326-346
 // (can_place_piece) accepts, what engine.py:390-454 (make_move) does before it draws a new hand, and the
@@ -122,6 +122,63 @@ greedy_kernel(LookTable t, LookPos pos, int n, bb_greedy_weights w, int32_t* __r
     // an illegal lane carries (INT64_MIN, 0): every legal value is above INT64_MIN (|weight| < 2^31, every
     // feature < 2^15), so it never wins over a legal lane, and with no legal lane the result is action 0
     int64_t v = a.legal ? move_terms(w, a) + state_terms(w, a) : INT64_MIN;
+    int act = a.legal ? p * 64 + cell : 0;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+      const int64_t v2 = __shfl_xor(v, d, 64);
+      const int act2 = __shfl_xor(act, d, 64);
+      take_better(v, act, v2, act2);
+    }
+    if (cell == 0) {
+      s_v[p] = v;
+      s_a[p] = act;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      take_better(v, act, s_v[1], s_a[1]);
+      take_better(v, act, s_v[2], s_a[2]);
+      action[i] = act;
+      if (value) value[i] = v;
+    }
+    __syncthreads();  // the records are rewritten by the workgroup's next position
+  }
+}
+
+// ---------------------------------------------------------------------------
+// One row of weights per position (bbvec.h bb_greedy_actions_each / bb_plan_actions_each): greedy_kernel and
+// plan_kernel with w = rows[i].  They are kernels of their own, not a template over the two above, so that the
+// uniform kernels' code objects stay instruction for instruction what DESIGN.md measured (a shared body changed
+// their scalar code).  The row is read inside the position loop -- a workgroup that strides past the grid cap meets
+// another row at every position -- at the wave-uniform index i and, like the position, told to be uniform: eight
+// scalar loads, the row in scalar registers.
+// ---------------------------------------------------------------------------
+static_assert(sizeof(bb_greedy_weights) == 8 * sizeof(int32_t), "a weight row is eight int32");
+__device__ __forceinline__ bb_greedy_weights load_weights(const bb_greedy_weights* __restrict__ rows, int64_t i) {
+  const int32_t* r = reinterpret_cast<const int32_t*>(rows + i);
+  bb_greedy_weights w;
+  w.lines = (int32_t)uniform32((uint32_t)r[0]);
+  w.score = (int32_t)uniform32((uint32_t)r[1]);
+  w.holes = (int32_t)uniform32((uint32_t)r[2]);
+  w.filled = (int32_t)uniform32((uint32_t)r[3]);
+  w.centre = (int32_t)uniform32((uint32_t)r[4]);
+  w.mobility = (int32_t)uniform32((uint32_t)r[5]);
+  w.dead = (int32_t)uniform32((uint32_t)r[6]);
+  w.refill = (int32_t)uniform32((uint32_t)r[7]);
+  return w;
+}
+
+__global__ void __launch_bounds__(kLookBlock)
+greedy_each_kernel(LookTable t, LookPos pos, int n, const bb_greedy_weights* __restrict__ rows,
+                   int32_t* __restrict__ action, int64_t* __restrict__ value) {
+  __shared__ int64_t s_v[kHand];
+  __shared__ int s_a[kHand];
+  const int p = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int cell = (int)(threadIdx.x & 63u);
+  for (int64_t i = blockIdx.x; i < (int64_t)n; i += gridDim.x) {
+    const Position P = load_position(pos, i);
+    const bb_greedy_weights w = load_weights(rows, i);
+    const After a = eval_action(t, P.B, P.hand, P.combo, p, cell);
+    int64_t v = a.legal ? move_terms(w, a) + state_terms(w, a) : INT64_MIN;  // as greedy_kernel
     int act = a.legal ? p * 64 + cell : 0;
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) {
@@ -343,6 +400,65 @@ plan_kernel(LookTable t, LookPos pos, int n, bb_greedy_weights w, int depth, bb_
   }
 }
 
+// plan_kernel with w = rows[i] (see greedy_each_kernel): the same search body, the same LDS, barriers and join
+__global__ void __launch_bounds__(kPlanBlock)
+plan_each_kernel(LookTable t, LookPos pos, int n, const bb_greedy_weights* __restrict__ rows, int depth,
+                 bb_plan_out out) {
+  __shared__ PlanRecord s_rec[kPlanRecords];
+  __shared__ int s_cnt[kHand];
+  __shared__ int64_t s_v[kPlanWaves];
+  __shared__ uint32_t s_key[kPlanWaves];
+  __shared__ int s_leaves[kPlanWaves];
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int cell = (int)(threadIdx.x & 63u);
+  for (int64_t i = blockIdx.x; i < (int64_t)n; i += gridDim.x) {
+    const Position P = load_position(pos, i);
+    const bb_greedy_weights w = load_weights(rows, i);
+    int64_t best = INT64_MIN;
+    uint32_t best_key = kPlanNoKey;
+    int leaves = 0;
+    bool unused = false;
+
+    const Ply1 ply1 = plan_ply1(t, P, depth, wave, cell);
+    if (ply1.closed) {
+      best = move_terms(w, ply1.a) + state_terms(w, ply1.a);
+      best_key = ((uint32_t)(wave * 64 + cell) << 16) | 0xFFFFu;
+      leaves = 1;
+    }
+    const int total = plan_compact(s_rec, s_cnt, w, ply1, wave, cell);
+
+    for (int r = wave; r < total; r += kPlanWaves)
+      plan_record_turn<false>(t, s_rec[r], P.hand, w, depth, cell, best, best_key, leaves, unused);
+
+    plan_wave_join(best, best_key, leaves);
+    if (cell == 0) {
+      s_v[wave] = best;
+      s_key[wave] = best_key;
+      s_leaves[wave] = leaves;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+      for (int k = 1; k < kPlanWaves; ++k) {
+        take_plan(best, best_key, s_v[k], s_key[k]);
+        leaves += s_leaves[k];
+      }
+      const bool found = best_key != kPlanNoKey;
+      const int p1 = (int)(best_key >> 16), p2 = (int)((best_key >> 8) & 0xFFu), p3 = (int)(best_key & 0xFFu);
+      out.action[i] = found ? p1 : 0;
+      if (out.value) out.value[i] = best;
+      if (out.plan) {
+        out.plan[i * 3 + 0] = found ? p1 : -1;
+        out.plan[i * 3 + 1] = found && p2 != 0xFF ? p2 : -1;
+        out.plan[i * 3 + 2] = found && p3 != 0xFF ? p3 : -1;
+      }
+      if (out.leaves) out.leaves[i] = leaves;
+    }
+    // no barrier here, as in plan_kernel: thread 0 reads only s_v / s_key / s_leaves, which the next position
+    // writes after two more barriers; its row is in this wave's own registers
+  }
+}
+
 // ---------------------------------------------------------------------------
 // Per-action full-hand values (bbvec.h bb_plan_values): plan_kernel's search with the maximum kept per first move.
 //
@@ -525,10 +641,25 @@ hipError_t launch_greedy(const uint64_t* board, const uint32_t* hand, const int3
   return hipGetLastError();
 }
 
+hipError_t launch_greedy_each(const uint64_t* board, const uint32_t* hand, const int32_t* combo, int n,
+                              const bb_greedy_weights* rows, int32_t* action, int64_t* value, hipStream_t s) {
+  const LookPos pos{board, hand, combo, nullptr};
+  hipLaunchKernelGGL(greedy_each_kernel, look_grid(n), dim3(kLookBlock), 0, s, look_table(), pos, n, rows, action,
+                     value);
+  return hipGetLastError();
+}
+
 hipError_t launch_plan(const uint64_t* board, const uint32_t* hand, const int32_t* combo, int n,
                        const bb_greedy_weights& w, int depth, const bb_plan_out& out, hipStream_t s) {
   const LookPos pos{board, hand, combo, nullptr};
   hipLaunchKernelGGL(plan_kernel, plan_grid(n), dim3(kPlanBlock), 0, s, look_table(), pos, n, w, depth, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_plan_each(const uint64_t* board, const uint32_t* hand, const int32_t* combo, int n,
+                            const bb_greedy_weights* rows, int depth, const bb_plan_out& out, hipStream_t s) {
+  const LookPos pos{board, hand, combo, nullptr};
+  hipLaunchKernelGGL(plan_each_kernel, plan_grid(n), dim3(kPlanBlock), 0, s, look_table(), pos, n, rows, depth, out);
   return hipGetLastError();
 }
 

@@ -75,20 +75,26 @@ def _evaluate_sequential(agent, num_episodes: int, deterministic: bool, render: 
 
 def evaluate_agent(agent, num_episodes: int = 100, deterministic: bool = True, render: bool = False,
                    seed: int = 42, max_moves: int = 100_000, record_actions: bool = False,
-                   safe_mask: bool = False) -> Dict[str, Any]:
+                   safe_mask: bool = False, seeds=None) -> Dict[str, Any]:
     """evaluate.py:23-90 (same keys in the returned dict).  record_actions: also return every episode's
     action sequence under "actions" (for replaying the games elsewhere, e.g. through the oracle).  A game still
     running after max_moves moves is cut off there and reports its score, lines and max combo so far.
     safe_mask: an ``act_device`` agent samples under the legal mask AND the hand-safe mask (the legal mask alone
-    where no move is safe); an ``act_env`` agent chooses its own mask (``RandomAgent(safe=True)``)."""
+    where no move is safe); an ``act_env`` agent chooses its own mask (``RandomAgent(safe=True)``).
+    seeds: one seed per episode (a list of num_episodes ints) in place of ``seed + e``, e.g. the same piece stream
+    for several episodes (``evaluation/tune.py``); not with render."""
     agent.eval()
+    if seeds is None:
+        seeds = [seed + e for e in range(num_episodes)]
+    elif render or len(seeds) != num_episodes:
+        raise ValueError("evaluate_agent: seeds needs one seed per episode and excludes render")
     if render:
         return _evaluate_sequential(agent, num_episodes, deterministic, render, seed, record_actions)
     from runtime.device_env import DeviceEnvBatch
 
     dev = agent.device
     n = num_episodes
-    env = DeviceEnvBatch(n, [seed + e for e in range(n)], autoreset=False, device=dev)
+    env = DeviceEnvBatch(n, [int(sd) for sd in seeds], autoreset=False, device=dev)
     env.reset()
     x = torch.zeros((n, 4, 8, 8), dtype=torch.float32, device=dev)
     mb = torch.zeros((n, 3), dtype=torch.int64, device=dev)

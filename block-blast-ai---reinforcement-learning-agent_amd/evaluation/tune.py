@@ -1,0 +1,235 @@
+"""Tuning the eight integer weights of the search agents (``agents/greedy.py``) by playing.
+
+The reference has no search agent and so nothing to tune.  ``GreedyAgent`` / ``HandPlanAgent`` choose their moves by an
+integer value of eight weights (bb_greedy_weights); which weights score best is found here by the cross-entropy
+method (CEM) over whole games: a population of candidate weight vectors plays the same piece streams, the best
+quarter refits a diagonal Gaussian, and so on.  What makes this cheap is ``bb_plan_actions_each``: one search launch
+per move serves the whole population, every env with the weights of its candidate (``PopulationPlanAgent``).
+
+``evaluate_population``  final scores int64 [P, G] of P candidates on G shared piece streams, one env batch
+``cem``                  the objective-agnostic core (float64 on the host, integer candidates)
+``tune``                 CEM with the mean score as fitness; writes the agents' weights JSON and a JSONL log
+``compare``              score per move of several weight sets on shared held-out games
+
+Every default below (population 64, 8 games, 300 moves, 30 generations, elite fraction 0.25, sigma0 300, scale 1000,
+sigma floor 10, 32 held-out games, ``dead`` fixed) is a starting point chosen by reasoning: none of them has been
+tuned.  Playing strength is reported, never asserted.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import math
+import os
+import time
+from typing import Callable, Dict, List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from agents.greedy import DEFAULT_WEIGHTS, PopulationPlanAgent
+from runtime import kernels as K
+from runtime import lib as L
+
+from .evaluate import evaluate_agent
+
+HOLDOUT_SEED_OFFSET = 10 ** 6  # the held-out games of ``tune`` are seeded seed + 10**6 + g
+
+
+def _play_population(weight_dicts: Sequence[Dict[str, int]], games: int, moves: int, seed: int, depth: int, device):
+    """(scores, lengths), int64 [P, G] each: env c * G + g plays candidate c on the piece stream seeded seed + g."""
+    p, g = len(weight_dicts), int(games)
+    rows = K.weight_rows(list(weight_dicts)).repeat_interleave(g, dim=0)
+    agent = PopulationPlanAgent(rows, depth=depth, device=device)
+    res = evaluate_agent(agent, num_episodes=p * g, seeds=[seed + e % g for e in range(p * g)], max_moves=int(moves))
+    return (torch.tensor(res["scores"], dtype=torch.int64).view(p, g),
+            torch.tensor(res["lengths"], dtype=torch.int64).view(p, g))
+
+
+def evaluate_population(weight_dicts: Sequence[Dict[str, int]], games: int, moves: int, seed: int, depth: int = 3,
+                        device=None) -> torch.Tensor:
+    """The final score of every (candidate, game): int64 [P, G] on the CPU.  One ``DeviceEnvBatch`` of P * G envs
+    without auto-reset; candidate c, game g is seeded ``seed + g`` -- common random numbers: every candidate sees the
+    same G piece streams, so candidates differ by their play alone.  The accounting is ``evaluate_agent``'s: the
+    score latched at termination, the score so far for a game cut off after ``moves`` moves.  ``depth`` 1..3 searches
+    with ``bb_plan_actions_each``, 0 uses the one-ply greedy kernel.  Row c equals the ``scores`` of
+    ``evaluate_agent(HandPlanAgent(weight_dicts[c], depth), num_episodes=G, seed=seed, max_moves=moves)`` when the
+    dict names all eight weights (a HandPlanAgent fills missing ones from DEFAULT_WEIGHTS, a row with zeros)."""
+    return _play_population(weight_dicts, games, moves, seed, depth, device)[0]
+
+
+def normalise(theta: np.ndarray, free: Sequence[int], scale: float) -> np.ndarray:
+    """theta with its free coordinates scaled so that the largest of them is ``scale`` in magnitude (left alone
+    when they are all zero).  The arg-max of the agents' value does not change under a positive scaling of all
+    weights; fixing the scale keeps a search over integers from drifting towards large or unresolvably small ones.
+    Fixed coordinates are not touched."""
+    out = np.array(theta, dtype=np.float64)
+    free = list(free)
+    top = np.max(np.abs(out[..., free]), axis=-1, keepdims=True)
+    out[..., free] = out[..., free] * np.where(top > 0, scale / np.where(top > 0, top, 1.0), 1.0)
+    return out
+
+
+def cem(fitness: Callable[[np.ndarray, int], np.ndarray], mean0, sigma0, population: int, elite_frac: float,
+        generations: int, rng: np.random.Generator, free: Sequence[int], scale: float = 1000,
+        sigma_floor: float = 10) -> List[dict]:
+    """The cross-entropy method over integer vectors, maximising ``fitness``; float64 on the host.
+
+    mean0: the start vector [D]; the coordinates in ``free`` are searched, the others stay at mean0's values in every
+    candidate.  sigma0: a scalar or [len(free)].  The mean's free part is brought to ``scale`` first (``normalise``).
+    Generation k: candidate 0 is the current mean itself, candidates 1..population-1 are mean + sigma * N(0, 1) on
+    the free coordinates (one ``rng.standard_normal((population - 1, len(free)))`` draw per generation); every
+    candidate is normalised to ``scale`` and rounded to integers (``np.rint``), and ``fitness(candidates int64 [P, D],
+    k)`` returns [P] floats.  The elites are the top ceil(population * elite_frac) by fitness, ties to the lower index
+    (a stable sort); the new mean and sigma are the mean and the population standard deviation (ddof 0) of the
+    elites' integer free coordinates, sigma floored at ``sigma_floor``.  Returns one record per generation:
+    candidates, fitness, elite (indices, best first), mean and sigma (full [D] / [len(free)], after the update),
+    best_fitness, mean_fitness.  The same rng state gives the same history."""
+    free = list(free)
+    mean = normalise(np.asarray(mean0, dtype=np.float64), free, scale)
+    sigma = np.broadcast_to(np.asarray(sigma0, dtype=np.float64), (len(free),)).copy()
+    n_elite = max(1, math.ceil(population * elite_frac))
+    history = []
+    for k in range(generations):
+        cand = np.tile(mean, (population, 1))
+        cand[1:, free] = mean[free] + sigma * rng.standard_normal((population - 1, len(free)))
+        cand = np.rint(normalise(cand, free, scale)).astype(np.int64)
+        fit = np.asarray(fitness(cand, k), dtype=np.float64)
+        elite = np.argsort(-fit, kind="stable")[:n_elite]
+        mean = mean.copy()
+        mean[free] = cand[elite][:, free].astype(np.float64).mean(axis=0)
+        sigma = np.maximum(cand[elite][:, free].astype(np.float64).std(axis=0), sigma_floor)
+        history.append({"generation": k, "candidates": cand, "fitness": fit, "elite": elite, "mean": mean.copy(),
+                        "sigma": sigma.copy(), "best_fitness": float(fit.max()), "mean_fitness": float(fit.mean())})
+    return history
+
+
+def _dict_of(theta) -> Dict[str, int]:
+    return {k: int(v) for k, v in zip(L.GREEDY_FIELDS, theta)}
+
+
+def _agent_depth(agent: str, depth: int) -> int:
+    if agent not in ("plan", "greedy"):
+        raise ValueError(f"agent must be 'plan' or 'greedy', not {agent!r}")
+    if agent == "plan" and int(depth) not in (1, 2, 3):
+        raise ValueError(f"depth must be 1, 2 or 3, not {depth}")
+    return int(depth) if agent == "plan" else 0  # 0: PopulationPlanAgent's one-ply greedy kernel
+
+
+def compare(weight_dicts: Sequence[Dict[str, int]], games: int, moves: int, seed: int, depth: int = 3,
+            device=None) -> List[dict]:
+    """Several weight sets on the same ``games`` piece streams (seeds seed + g), one population call: per set the mean
+    score, the mean score per move (each game's score over its own moves) and its standard error over the games, and
+    the number of games that ended before the ``moves`` cut."""
+    scores, lengths = _play_population(weight_dicts, games, moves, seed, depth, device)
+    per_move = scores.double() / lengths.clamp(min=1).double()
+    return [{"weights": dict(w), "mean_score": float(scores[c].double().mean()),
+             "mean_length": float(lengths[c].double().mean()),
+             "ended_before_cut": int((lengths[c] < int(moves)).sum()),
+             "score_per_move": float(per_move[c].mean()),
+             "score_per_move_se": float(per_move[c].std(unbiased=True) / math.sqrt(games)) if games > 1 else 0.0}
+            for c, w in enumerate(weight_dicts)]
+
+
+def tune(agent: str = "plan", depth: int = 3, population: int = 64, games: int = 8, moves: int = 300,
+         generations: int = 30, elite_frac: float = 0.25, seed: int = 1, init: Optional[Dict[str, int]] = None,
+         fixed: Sequence[str] = ("dead",), device=None, output: Optional[str] = None, log: Optional[str] = None,
+         sigma0: float = 300.0, scale: float = 1000, sigma_floor: float = 10, holdout_games: int = 32) -> dict:
+    """CEM over the weights of ``HandPlanAgent(depth)`` (agent "plan") or ``GreedyAgent`` (agent "greedy").
+
+    Fitness is a candidate's mean final score over ``games`` games of at most ``moves`` moves
+    (``evaluate_population``).  Generation k plays the seeds ``seed + k * games + g``: fresh for each generation,
+    shared by all its candidates.  ``init`` (default DEFAULT_WEIGHTS) is the start mean; the weights named in
+    ``fixed`` keep init's values.  After the last generation one population call with P = 2 plays ``init`` against
+    the final weights (the last mean, normalised and rounded) on ``holdout_games`` held-out games seeded from
+    ``seed + 10**6``.  ``output``: the final weights in the agents' JSON format ({"agent", "depth", "weights"};
+    ``HandPlanAgent.load`` / ``evaluate.py --weights`` read it).  ``log``: a JSONL file, one "generation" record per
+    generation (seeds, best and mean fitness, the best candidate, the mean vector and sigma after the update,
+    candidate 0 = the mean as it was played and its fitness) and one "final" record (the weights, the held-out comparison,
+    the settings, the build id).  Deterministic for a given ``seed``: the sampling is numpy's ``default_rng(seed)``,
+    the games are seeded, the search is exact.  Every default is untuned (see the module docstring).  Returns the
+    final record."""
+    eval_depth = _agent_depth(agent, depth)
+    init = dict(DEFAULT_WEIGHTS) if init is None else {**{k: 0 for k in L.GREEDY_FIELDS}, **init}
+    L.greedy_weights(init)  # rejects unknown names
+    unknown = set(fixed) - set(L.GREEDY_FIELDS)
+    if unknown:
+        raise ValueError(f"unknown fixed weights {sorted(unknown)}; the fields are {L.GREEDY_FIELDS}")
+    free = [i for i, k in enumerate(L.GREEDY_FIELDS) if k not in fixed]
+    mean0 = np.array([init[k] for k in L.GREEDY_FIELDS], dtype=np.float64)
+    t0 = time.perf_counter()
+
+    def fitness(cand: np.ndarray, k: int) -> np.ndarray:
+        scores = evaluate_population([_dict_of(c) for c in cand], games, moves, seed + k * games, eval_depth, device)
+        return scores.double().mean(dim=1).numpy()
+
+    history = cem(fitness, mean0, sigma0, population, elite_frac, generations, np.random.default_rng(seed), free,
+                  scale=scale, sigma_floor=sigma_floor)
+    final_theta = np.rint(normalise(history[-1]["mean"] if history else mean0, free, scale)).astype(np.int64)
+    weights = _dict_of(final_theta)
+    held = compare([init, weights], holdout_games, moves, seed + HOLDOUT_SEED_OFFSET, eval_depth, device)
+    host = device is not None and torch.device(device).type == "cpu"
+    final = {"record": "final", "agent": agent, "depth": int(depth) if agent == "plan" else None, "weights": weights,
+             "init": init, "fixed": list(fixed),
+             "holdout": {"seed0": seed + HOLDOUT_SEED_OFFSET, "games": holdout_games, "moves": moves,
+                         "init": held[0], "tuned": held[1]},
+             "settings": {"population": population, "games": games, "moves": moves, "generations": generations,
+                          "elite_frac": elite_frac, "seed": seed, "sigma0": sigma0, "scale": scale,
+                          "sigma_floor": sigma_floor},
+             "build_id": L.build_id(host=host), "backend": "host" if host else "hip",
+             "wall_s": round(time.perf_counter() - t0, 3)}
+    if output:
+        doc = {"agent": agent, "weights": weights}
+        if agent == "plan":
+            doc = {"agent": agent, "depth": int(depth), "weights": weights}
+        with open(output, "w") as f:
+            json.dump(doc, f, indent=2)
+    if log:
+        os.makedirs(os.path.dirname(os.path.abspath(log)), exist_ok=True)
+        with open(log, "w") as f:
+            for h in history:
+                best = int(h["elite"][0])
+                f.write(json.dumps({
+                    "record": "generation", "generation": h["generation"],
+                    "seeds": [seed + h["generation"] * games + g for g in range(games)],
+                    "best_fitness": h["best_fitness"], "mean_fitness": h["mean_fitness"],
+                    "mean_played": _dict_of(h["candidates"][0]), "mean_played_fitness": float(h["fitness"][0]),
+                    "best": _dict_of(h["candidates"][best]),
+                    "mean": [float(x) for x in h["mean"]], "sigma": [float(x) for x in h["sigma"]]}) + "\n")
+            f.write(json.dumps(final) + "\n")
+    return final
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser(description="Tune the search agents' weights by the cross-entropy method")
+    ap.add_argument("--agent", choices=("plan", "greedy"), default="plan")
+    ap.add_argument("--depth", type=int, choices=(1, 2, 3), default=3, help="--agent plan: moves searched ahead")
+    ap.add_argument("--population", type=int, default=64)
+    ap.add_argument("--games", type=int, default=8, help="games per candidate and generation (shared piece streams)")
+    ap.add_argument("--moves", type=int, default=300, help="cut every game off after this many moves")
+    ap.add_argument("--generations", type=int, default=30)
+    ap.add_argument("--elite-frac", type=float, default=0.25)
+    ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--holdout-games", type=int, default=32)
+    ap.add_argument("--device", type=str, default=None, help="cpu = the host backend")
+    ap.add_argument("--output", type=str, default=None, help="the tuned weights, in the agents' JSON format")
+    ap.add_argument("--log", type=str, default=None, help="JSONL: one record per generation and a final one")
+    ap.add_argument("--compare", type=str, default=None,
+                    help="no tuning: play this weights JSON against DEFAULT_WEIGHTS on --games games seeded from --seed")
+    args = ap.parse_args()
+    if args.compare:
+        with open(args.compare) as f:
+            other = json.load(f)["weights"]
+        res = compare([dict(DEFAULT_WEIGHTS), other], args.games, args.moves, args.seed, _agent_depth(args.agent, args.depth),
+                      args.device)
+        print(json.dumps({"record": "compare", "seed0": args.seed, "games": args.games, "moves": args.moves,
+                          "agent": args.agent, "depth": args.depth, "init": res[0], "other": res[1]}))
+        return
+    final = tune(agent=args.agent, depth=args.depth, population=args.population, games=args.games, moves=args.moves,
+                 generations=args.generations, elite_frac=args.elite_frac, seed=args.seed,
+                 device=args.device, output=args.output, log=args.log, holdout_games=args.holdout_games)
+    print(json.dumps(final))
+
+
+if __name__ == "__main__":
+    main()

@@ -289,6 +289,35 @@ class DeviceEnvBatch:
                 "bb_plan_actions", self.handle, self.lib)
         return out
 
+    def greedy_actions_each(self, out: torch.Tensor, rows: torch.Tensor,
+                            value: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """bb_greedy_actions_each on the live state: ``greedy_actions`` with env i's weights taken from rows[i]
+        (int32 [N, 8] on this device, ``runtime.kernels.weight_rows``), read when the launch runs."""
+        from . import kernels as K
+
+        n = self.num_envs
+        for t, dt in ((out, torch.int32), (value, torch.int64)):
+            assert t is None or (t.dtype == dt and t.device == self.device and t.is_contiguous() and t.numel() == n)
+        K._rows("greedy_actions_each", rows, n, self.device)
+        L.check(self.lib.bb_greedy_actions_each(self.handle, _ptr(rows), _ptr(out), _ptr(value),
+                                                _stream(self.device)),
+                "bb_greedy_actions_each", self.handle, self.lib)
+        return out
+
+    def plan_actions_each(self, out: torch.Tensor, rows: torch.Tensor, depth: int = 3,
+                          value: Optional[torch.Tensor] = None, plan: Optional[torch.Tensor] = None,
+                          leaves: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """bb_plan_actions_each on the live state: ``plan_actions`` with env i's weights taken from rows[i] (int32
+        [N, 8] on this device, ``runtime.kernels.weight_rows``), read when the launch runs: one launch searches for
+        a whole population of weight vectors."""
+        from . import kernels as K
+
+        o = K._plan_out({"action": out, "value": value, "plan": plan, "leaves": leaves}, self.num_envs, self.device)
+        K._rows("plan_actions_each", rows, self.num_envs, self.device)
+        L.check(self.lib.bb_plan_actions_each(self.handle, _ptr(rows), int(depth), C.byref(o), _stream(self.device)),
+                "bb_plan_actions_each", self.handle, self.lib)
+        return out
+
     def plan_values(self, weights, depth: int = 3, out: Optional[dict] = None) -> dict:
         """bb_plan_values on the live state: the search of ``plan_actions`` kept per first move.  ``out``: a dict
         with any of "q" i64 / "rest" i32 / "leaves" i32 [N, 192] and "safe" i64 [N, 3] tensors to write (missing

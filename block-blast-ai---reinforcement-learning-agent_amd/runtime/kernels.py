@@ -280,6 +280,76 @@ def plan_actions(board: torch.Tensor, hand: torch.Tensor, weights, depth: int = 
     return res
 
 
+def weight_rows(weights, n: Optional[int] = None, device=None) -> torch.Tensor:
+    """Rows of bb_greedy_weights for the ``*_each`` calls: a contiguous int32 [n, 8] tensor on ``device`` (default
+    the CPU), the columns in the struct's field order (``L.GREEDY_FIELDS``).  ``weights``: a dict of the fields
+    (missing = 0), repeated n times (once without n), or a list of such dicts, one per row (n, when given, must be
+    its length).  Unknown names are rejected as ``L.greedy_weights`` rejects them."""
+    dicts = [weights] * (1 if n is None else int(n)) if isinstance(weights, dict) else list(weights)
+    if n is not None and len(dicts) != int(n):
+        raise ValueError(f"weight_rows: {len(dicts)} weight sets for n = {n}")
+    if not dicts:
+        raise ValueError("weight_rows: at least one row is required")
+    structs = {id(d): L.greedy_weights(d) for d in dicts}  # one check per distinct dict
+    rows = [[getattr(structs[id(d)], k) for k in L.GREEDY_FIELDS] for d in dicts]
+    return torch.tensor(rows, dtype=torch.int32).to(device if device is not None else "cpu").contiguous()
+
+
+def _rows(call: str, rows, n: int, dev) -> torch.Tensor:
+    """The rows tensor of an ``*_each`` call, checked: one row of eight int32 per position, where the positions are."""
+    if not (isinstance(rows, torch.Tensor) and rows.dtype == torch.int32 and rows.device == dev
+            and rows.is_contiguous() and tuple(rows.shape) == (n, len(L.GREEDY_FIELDS))):
+        raise L.BBNativeError(f"{call}: rows must be a contiguous {torch.int32} [{n}, {len(L.GREEDY_FIELDS)}] "
+                              f"tensor on {dev} (see weight_rows)")
+    return rows
+
+
+def greedy_actions_each(board: torch.Tensor, hand: torch.Tensor, rows: torch.Tensor,
+                        combo: Optional[torch.Tensor] = None, action: Optional[torch.Tensor] = None,
+                        value: Optional[torch.Tensor] = None,
+                        want_value: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """bb_greedy_actions_each_pos: ``greedy_actions`` with the weights of position i taken from rows[i] (int32
+    [n, 8], ``weight_rows``), in one launch.  Position i's result is that of ``greedy_actions`` on it alone under
+    rows[i].  The rows are read when the launch runs.  Returns (action int32 [n], value int64 [n] or None)."""
+    pos, n, dev = _positions(board, hand, combo, None)
+    _rows("greedy_actions_each", rows, n, dev)
+    action = torch.empty(n, dtype=torch.int32, device=dev) if action is None else action
+    if value is None and want_value:
+        value = torch.empty(n, dtype=torch.int64, device=dev)
+    for t, dt in ((action, torch.int32), (value, torch.int64)):
+        if t is not None and not (t.dtype == dt and t.device == dev and t.is_contiguous() and t.numel() == n):
+            raise L.BBNativeError(
+                f"greedy_actions_each: outputs must be contiguous {dt} tensors of {n} elements on {dev}")
+    lib, stream = _look_lib(dev)
+    L.check(lib.bb_greedy_actions_each_pos(C.byref(pos), n, _p(rows), _p(action), _p(value), stream),
+            "bb_greedy_actions_each_pos", lib=lib)
+    return action, value
+
+
+def plan_actions_each(board: torch.Tensor, hand: torch.Tensor, rows: torch.Tensor, depth: int = 3,
+                      combo: Optional[torch.Tensor] = None, action: Optional[torch.Tensor] = None,
+                      value: Optional[torch.Tensor] = None, plan: Optional[torch.Tensor] = None,
+                      leaves: Optional[torch.Tensor] = None, want_value: bool = True, want_plan: bool = False,
+                      want_leaves: bool = False) -> dict:
+    """bb_plan_actions_each_pos: ``plan_actions`` with the weights of position i taken from rows[i] (int32 [n, 8],
+    ``weight_rows``), in one launch -- a population of weight vectors searched at once.  Position i's outputs are
+    those of ``plan_actions`` on it alone under rows[i]; the returned dict is ``plan_actions``'.  The rows are read
+    when the launch runs, so a captured launch replays with what they hold then."""
+    pos, n, dev = _positions(board, hand, combo, None)
+    _rows("plan_actions_each", rows, n, dev)
+    res = {"action": torch.empty(n, dtype=torch.int32, device=dev) if action is None else action}
+    for k, given, want in (("value", value, want_value), ("plan", plan, want_plan), ("leaves", leaves, want_leaves)):
+        if given is not None:
+            res[k] = given
+        elif want:
+            res[k] = torch.empty((n, 3) if k == "plan" else n, dtype=PLAN_OUTPUTS[k][0], device=dev)
+    o = _plan_out(res, n, dev)
+    lib, stream = _look_lib(dev)
+    L.check(lib.bb_plan_actions_each_pos(C.byref(pos), n, _p(rows), int(depth), C.byref(o), stream),
+            "bb_plan_actions_each_pos", lib=lib)
+    return res
+
+
 PLAN_VALUE_OUTPUTS = {"q": (torch.int64, 192), "rest": (torch.int32, 192), "leaves": (torch.int32, 192),
                       "safe": (torch.int64, 3)}
 

@@ -230,6 +230,10 @@ SIGNATURES = {
     "bb_greedy_actions": (C.c_int, [_P, C.POINTER(GreedyWeights), _P, _P, _P]),
     "bb_plan_actions_pos": (C.c_int, [C.POINTER(Positions), _I32, C.POINTER(GreedyWeights), _I32, C.POINTER(PlanOut), _P]),
     "bb_plan_actions": (C.c_int, [_P, C.POINTER(GreedyWeights), _I32, C.POINTER(PlanOut), _P]),
+    "bb_greedy_actions_each_pos": (C.c_int, [C.POINTER(Positions), _I32, _P, _P, _P, _P]),
+    "bb_greedy_actions_each": (C.c_int, [_P, _P, _P, _P, _P]),
+    "bb_plan_actions_each_pos": (C.c_int, [C.POINTER(Positions), _I32, _P, _I32, C.POINTER(PlanOut), _P]),
+    "bb_plan_actions_each": (C.c_int, [_P, _P, _I32, C.POINTER(PlanOut), _P]),
     "bb_plan_values_pos": (C.c_int, [C.POINTER(Positions), _I32, C.POINTER(GreedyWeights), _I32,
                                      C.POINTER(PlanValuesOut), _P]),
     "bb_plan_values": (C.c_int, [_P, C.POINTER(GreedyWeights), _I32, C.POINTER(PlanValuesOut), _P]),
@@ -297,6 +301,8 @@ HOST_SYMBOLS = ("bb_abi_version", "bb_build_id", "bb_create", "bb_destroy", "bb_
                 "bb_snapshot_combo", "bb_get_state", "bb_set_state", "bb_random_actions", "bb_afterstates_pos",
                 "bb_afterstates",
                 "bb_greedy_actions_pos", "bb_greedy_actions", "bb_plan_actions_pos", "bb_plan_actions",
+                "bb_greedy_actions_each_pos", "bb_greedy_actions_each", "bb_plan_actions_each_pos",
+                "bb_plan_actions_each",
                 "bb_plan_values_pos", "bb_plan_values", "bb_safe_mask_pos", "bb_safe_mask")
 
 _lib = None

@@ -60,7 +60,9 @@ extern "C" {
                                  (additive, still 9) bb_distill_loss_args with bb_distill_loss_forward / _backward /
                                  _fused: policy distillation from the search values; bb_snapshot_combo;
                                  (additive, still 9) bb_guided_loss_args with bb_guided_loss_forward / _backward /
-                                 _fused: the PPO loss and the distillation cross-entropy on one softmax */
+                                 _fused: the PPO loss and the distillation cross-entropy on one softmax;
+                                 (additive, still 9) bb_greedy_actions_each(_pos) and bb_plan_actions_each(_pos): one
+                                 row of weights per position, read from the memory of the position columns */
 
 #define BB_OK 0
 #define BB_ERR_ARG (-1)
@@ -346,6 +348,16 @@ int bb_afterstates(bb_env* env, const bb_afterstate_out* out, void* stream);
 int bb_greedy_actions_pos(const bb_positions* pos, int32_t n, const bb_greedy_weights* w, int32_t* d_action,
                           int64_t* d_value, void* stream);
 int bb_greedy_actions(bb_env* env, const bb_greedy_weights* w, int32_t* d_action, int64_t* d_value, void* stream);
+/* bb_greedy_actions with one row of weights per position: d_action[i] / d_value[i] are exactly what
+ * bb_greedy_actions_pos returns for position i alone with w = d_w[i].  d_w is [n] rows ([num_envs] for the handle
+ * form) of eight int32 in the struct's field order; any int32 is a valid weight.  The rows live in the same
+ * memory as the position columns: device memory for libbbvec.so, host memory for libbbvec_host.so.  The calls
+ * above take w as a host struct; these take d_w as a pointer into that memory, read when the launch runs, so
+ * a captured launch replays with whatever the rows hold then.  One launch; refusals, asynchrony, no allocation and
+ * graph capture as above (a NULL d_w is refused, and n <= 0 in the _pos form). */
+int bb_greedy_actions_each_pos(const bb_positions* pos, int32_t n, const bb_greedy_weights* d_w, int32_t* d_action,
+                               int64_t* d_value, void* stream);
+int bb_greedy_actions_each(bb_env* env, const bb_greedy_weights* d_w, int32_t* d_action, int64_t* d_value, void* stream);
 
 /* ---- full-hand lookahead ----------------------------------------------------
  * The exhaustive search over the deterministic part of a decision: the up to
@@ -387,6 +399,16 @@ typedef struct bb_plan_out {
 int bb_plan_actions_pos(const bb_positions* pos, int32_t n, const bb_greedy_weights* w, int32_t depth,
                         const bb_plan_out* out, void* stream);
 int bb_plan_actions(bb_env* env, const bb_greedy_weights* w, int32_t depth, const bb_plan_out* out, void* stream);
+/* bb_plan_actions with one row of weights per position: position i's action, value, plan and leaves are exactly
+ * what bb_plan_actions_pos returns for position i alone with w = d_w[i] (the tie rule, action 0 / INT64_MIN
+ * without a legal action, NULL optional outputs, depth 1..3).  d_w is [n] rows ([num_envs] for the handle form)
+ * of eight int32 in the struct's field order, in the same memory as the position columns: device memory for
+ * libbbvec.so, host memory for libbbvec_host.so -- unlike w above, which is a host struct.  The rows are read when
+ * the launch runs.  One launch for a whole population of weight vectors; refusals as bb_plan_actions(_pos), with
+ * a NULL d_w refused; asynchronous, no allocation, graph-capturable from the first call. */
+int bb_plan_actions_each_pos(const bb_positions* pos, int32_t n, const bb_greedy_weights* d_w, int32_t depth,
+                             const bb_plan_out* out, void* stream);
+int bb_plan_actions_each(bb_env* env, const bb_greedy_weights* d_w, int32_t depth, const bb_plan_out* out, void* stream);
 
 /* ---- per-action full-hand values and the hand-safe mask -----------------------
  * What bb_plan_actions folds into one maximum, kept per first move.  The search

@@ -46,8 +46,8 @@ def code_object_metadata():
     res = {}
     for block in text.split("  - .agpr_count:")[1:]:
         name = re.search(r"\.name:\s+(\S+)", block).group(1)
-        short = next(k for k in ("greedy_kernel", "afterstates_kernel", "plan_kernel", "plan_values_kernel",
-                                "safe_mask_kernel")
+        short = next(k for k in ("greedy_kernel", "greedy_each_kernel", "afterstates_kernel", "plan_kernel",
+                                "plan_each_kernel", "plan_values_kernel", "safe_mask_kernel")
                      if k in name)
         vgpr = int(re.search(r"\.vgpr_count:\s+(\d+)", block).group(1))
         res[short] = {
