@@ -939,7 +939,7 @@ int64_t linear_n1_workspace_bytes(int rows, int K) {
   return (int64_t)((K + kBgradCols - 1) / kBgradCols) * bgrad_split(rows) * kN1Slots * (int64_t)sizeof(float);
 }
 
-int linear_n1_counters(int K) { return K > 0 ? (K + kBgradCols - 1) / kBgradCols : -1; }
+int linear_n1_counters(int K) { return K > 0 && K % 8 == 0 ? (K + kBgradCols - 1) / kBgradCols : -1; }
 
 hipError_t launch_linear_n1_forward(const void* x, const void* w, const void* b, int rows, int K, int ldx, void* y,
                                     hipStream_t s) {

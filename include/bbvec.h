@@ -942,7 +942,8 @@ int bb_conv_in_forward_prep(const float* d_x, int32_t x_nhwc, const float* d_w, 
  * 8, 16-byte aligned.  Forward: y[r] = bf16(sum_k x[r][k] w[k] + b), f32 sums.  Backward: dx[r][k] = bf16(gy[r] w[k]), dW[k] = sum_r gy[r] x[r][k],
  * db = sum_r gy[r] (d_db NULL: skipped), f32 sums in a fixed order rounded to bf16; row chunks publish
  * partials to d_ws (bb_linear_n1_workspace_bytes(rows, K) bytes) with bb_linear_n1_counters(K) zeroed
- * counters in d_cnt (as bb_linear_bgrad).  One launch each. */
+ * counters in d_cnt (as bb_linear_bgrad).  One launch each.  Both size queries return -1 for a K that is not a
+ * positive multiple of 8. */
 int64_t bb_linear_n1_workspace_bytes(int32_t rows, int32_t K);
 int32_t bb_linear_n1_counters(int32_t K);
 int bb_linear_n1_forward(const void* d_x, const void* d_w, const void* d_b, int32_t rows, int32_t K, int32_t ldx,
