@@ -705,6 +705,19 @@ int bb_safe_mask(bb_env* env, int32_t mode, uint64_t* d_mask, void* stream) {
   });
 }
 
+// The refill census (census_kernel, csrc/bb_census.hip)
+int bb_refill_census_pos(const uint64_t* d_board, int32_t n, const bb_census_out* out, void* stream) {
+  const char* rule = bb_look_rules::refill_census_pos(d_board, n, out);
+  if (!rule && n == 0) return BB_OK;  // accepted, and nothing to do
+  return look_pos_call("bb_refill_census_pos", rule,
+                       [&] { return launch_refill_census(d_board, n, *out, (hipStream_t)stream); });
+}
+
+int bb_refill_census(bb_env* env, const bb_census_out* out, void* stream) {
+  return look_env_call(env, "bb_refill_census", bb_look_rules::refill_census(out),
+                       [&] { return launch_refill_census(env->d.board, env->n, *out, (hipStream_t)stream); });
+}
+
 int bb_masked_sample(const float* d_logits, const uint64_t* d_mask_bits, int32_t n, const float* d_uniform,
                      uint64_t seed, uint64_t step, uint64_t env_offset, int32_t deterministic,
                      const int64_t* d_action_in, int64_t* d_action, float* d_logp, float* d_entropy,

@@ -114,6 +114,8 @@ hipError_t launch_plan_values(const uint64_t* board, const uint32_t* hand, const
 // the hand-safe mask alone (bb_lookahead.hip): n > 0, mode BB_SAFE_WORDS / BB_SAFE_OR_LEGAL, mask [n][3]
 hipError_t launch_safe_mask(const uint64_t* board, const uint32_t* hand, int n, int mode, uint64_t* mask,
                             hipStream_t s);
+// the refill census (bb_census.hip): n > 0, board [n], out.count [n] / out.solvable [n][37][37], not both NULL
+hipError_t launch_refill_census(const uint64_t* board, int n, const bb_census_out& out, hipStream_t s);
 hipError_t launch_masked_sample(const float* logits, const uint64_t* mbits, int n, const float* uniform,
                                 uint64_t seed, uint64_t step, const uint64_t* d_step, uint64_t offset,
                                 int deterministic, const int64_t* action_in, int64_t* action, float* logp,

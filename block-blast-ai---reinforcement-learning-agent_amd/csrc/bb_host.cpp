@@ -502,6 +502,55 @@ void safe_mask_host(const uint64_t* board, const uint32_t* hand, int32_t n, int 
   }
 }
 
+// bbvec.h bb_refill_census (the host twin of census_kernel): which hands {a, b, c} engine.py:174-224 accepts on B.
+// An existence search of its own on clear_full / anchors_of: for every first piece a and anchor x the afterstate B1,
+// the anchors of all 37 pieces on B1 once, and the pairs {b, c} whose bit S[a][b] bit c is still clear; a's anchors
+// end early once every pair is in.  S[a] is symmetric in (b, c); the hand's three choices of a first piece are
+// joined at the end.
+bool pair_fits(uint64_t X, int b, int c, const uint64_t A[kPieces]) {
+  for (uint64_t m = A[b]; m; m &= m - 1)
+    if (anchors_of(c, clear_full(X | (T().p[b].shape << __builtin_ctzll(m))))) return true;
+  if (b != c)
+    for (uint64_t m = A[c]; m; m &= m - 1)
+      if (anchors_of(b, clear_full(X | (T().p[c].shape << __builtin_ctzll(m))))) return true;
+  return false;
+}
+
+void refill_census_host(const uint64_t* board, int32_t n, const bb_census_out& out) {
+  constexpr uint64_t kAll = (1ull << kPieces) - 1;
+#pragma omp parallel for schedule(dynamic, 1)  // clogged and open boards differ by orders of magnitude
+  for (int32_t i = 0; i < n; ++i) {
+    const uint64_t B = board[i];
+    uint64_t S[kPieces][kPieces] = {};
+    for (int a = 0; a < kPieces; ++a) {
+      int open = kPieces * (kPieces + 1) / 2;  // pairs b <= c not yet in S[a]
+      for (uint64_t ma = anchors_of(a, B); ma && open; ma &= ma - 1) {
+        const uint64_t B1 = clear_full(B | (T().p[a].shape << __builtin_ctzll(ma)));
+        uint64_t A[kPieces];
+        for (int p = 0; p < kPieces; ++p) A[p] = anchors_of(p, B1);
+        for (int b = 0; b < kPieces; ++b) {
+          if (S[a][b] == kAll) continue;
+          for (int c = b; c < kPieces; ++c) {
+            if (((S[a][b] >> c) & 1ull) || !(A[b] | A[c]) || !pair_fits(B1, b, c, A)) continue;
+            S[a][b] |= 1ull << c;
+            S[a][c] |= 1ull << b;
+            --open;
+          }
+        }
+      }
+    }
+    int32_t count = 0;
+    for (int a = 0; a < kPieces; ++a)
+      for (int b = 0; b < kPieces; ++b) {
+        uint64_t w = S[a][b] | S[b][a];
+        for (int c = 0; c < kPieces; ++c) w |= ((S[c][a] >> b) & 1ull) << c;
+        if (out.solvable) out.solvable[((size_t)i * kPieces + a) * kPieces + b] = w;
+        count += __builtin_popcountll(w);
+      }
+    if (out.count) out.count[i] = count;
+  }
+}
+
 }  // namespace
 
 #ifndef BB_BUILD_ID
@@ -868,6 +917,21 @@ int bb_safe_mask(bb_env* env, int32_t mode, uint64_t* d_mask, void* stream) {
   if (!env) return BB_ERR_ARG;
   if (int rc = refused(env, "bb_safe_mask", R::safe_mask(mode, d_mask))) return rc;
   safe_mask_host(env->board.data(), env->hand.data(), env->n, mode, d_mask);
+  return BB_OK;
+}
+
+int bb_refill_census_pos(const uint64_t* d_board, int32_t n, const bb_census_out* out, void* stream) {
+  (void)stream;
+  if (int rc = refused(nullptr, "bb_refill_census_pos", R::refill_census_pos(d_board, n, out))) return rc;
+  refill_census_host(d_board, n, *out);
+  return BB_OK;
+}
+
+int bb_refill_census(bb_env* env, const bb_census_out* out, void* stream) {
+  (void)stream;
+  if (!env) return BB_ERR_ARG;
+  if (int rc = refused(env, "bb_refill_census", R::refill_census(out))) return rc;
+  refill_census_host(env->board.data(), env->n, *out);
   return BB_OK;
 }
 

@@ -1,4 +1,4 @@
-// bb_look_rules.h -- the argument rules of the fourteen lookahead entry points of include/bbvec.h, one copy for
+// bb_look_rules.h -- the argument rules of the sixteen lookahead entry points of include/bbvec.h, one copy for
 // both backends (csrc/bb_capi.cpp and csrc/bb_host.cpp).  Plain C++, nothing from HIP.
 //
 // Each function returns the rule an argument set breaks, as the text that follows "<entry point>: " in
@@ -7,7 +7,7 @@
 //
 // Asymmetries that are part of the ABI as it stands: bb_afterstates_pos, bb_greedy_actions(_each)_pos and
 // bb_plan_actions(_each)_pos refuse n == 0 and answer every broken rule with one text; bb_plan_values_pos accepts n == 0
-// (and does nothing) and names the rule that broke, and so does bb_safe_mask_pos.
+// (and does nothing) and names the rule that broke, and so do bb_safe_mask_pos and bb_refill_census_pos.
 #pragma once
 #include <stdint.h>
 
@@ -90,6 +90,18 @@ inline const char* safe_mask_pos(const bb_positions* pos, int32_t n, int32_t mod
   if (no_positions(pos)) return "positions (board, hand) are NULL";
   if (n < 0) return "n is negative";
   return safe_mask(mode, d_mask);
+}
+
+// the refill census reads a board column alone (no bb_positions) and, like bb_plan_values_pos, accepts n == 0
+inline const char* refill_census(const bb_census_out* out) {
+  if (!out) return "out is NULL";
+  if (!out->count && !out->solvable) return "both outputs are NULL";
+  return nullptr;
+}
+inline const char* refill_census_pos(const uint64_t* board, int32_t n, const bb_census_out* out) {
+  if (!board) return "board is NULL";
+  if (n < 0) return "n is negative";
+  return refill_census(out);
 }
 
 }  // namespace bb_look_rules

@@ -93,6 +93,16 @@ def afterstates_dict(out: dict) -> dict:
     return res
 
 
+def census_dict(out: dict) -> dict:
+    """Device output of bb_refill_census (count [N]) -> numpy arrays of shape (N,): count i32, solvable_fraction f64
+    (count / 37^3) and hazard f64, the probability that the next deal cannot be played."""
+    from runtime.kernels import NUM_HANDS, refill_hazard
+
+    count = out["count"].cpu()
+    return {"count": count.numpy(), "solvable_fraction": count.numpy().astype(np.float64) / NUM_HANDS,
+            "hazard": refill_hazard(count).numpy()}
+
+
 def plan_values_dict(out: dict) -> dict:
     """Device outputs of bb_plan_values -> numpy arrays of shape (N, 192): q i64 (INT64_MIN: illegal), a2 / a3 i32
     (the rest of the best sequence, -1 for a ply not played or an illegal action), leaves i32, safe bool."""

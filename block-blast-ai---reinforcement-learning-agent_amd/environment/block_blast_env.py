@@ -115,6 +115,15 @@ class BlockBlastEnv(Env):
         mobility.  The state and the piece stream are not touched."""
         return {k: v[0] for k, v in _host.afterstates_dict(self._dev.afterstates()).items()}
 
+    def refill_census(self) -> Dict[str, float]:
+        """How the next deal would go on the board as it stands (bb_refill_census; the exact outcome space of the
+        reference's dealer): count (of the 37^3 ordered hands that can be placed in some order), solvable_fraction,
+        hazard (the probability that 100 draws end on a hand that cannot be played).  The state and the piece
+        stream are not touched."""
+        out = _host.census_dict(self._dev.refill_census())
+        return {"count": int(out["count"][0]), "solvable_fraction": float(out["solvable_fraction"][0]),
+                "hazard": float(out["hazard"][0])}
+
     def plan_values(self, weights: Optional[Dict[str, int]] = None, depth: int = 3) -> Dict[str, np.ndarray]:
         """Per action, what playing out the hand after it is worth (bb_plan_values; the reference has no
         counterpart): arrays of shape (192,) -- q (int64, INT64_MIN for an illegal action), a2 / a3 (the rest of

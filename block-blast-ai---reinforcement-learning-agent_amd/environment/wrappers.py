@@ -127,6 +127,13 @@ class VectorizedBlockBlastEnv:
         (fp64), score_gained, legal, dead, refill, lines, holes, centre, mobility."""
         return _host.afterstates_dict(self.dev.afterstates())
 
+    def refill_census(self) -> Dict[str, np.ndarray]:
+        """How the next deal would go on every env's board as it stands (bb_refill_census, one launch; the exact
+        outcome space of the reference's dealer): arrays of shape (num_envs,) -- count (of the 37^3 ordered hands
+        that can be placed in some order), solvable_fraction, hazard (the probability that 100 draws end on a hand
+        that cannot be played)."""
+        return _host.census_dict(self.dev.refill_census())
+
     def plan_values(self, weights: Optional[Dict[str, int]] = None, depth: int = 3) -> Dict[str, np.ndarray]:
         """Per action of every env, what playing out the hand after it is worth (bb_plan_values, one launch; the
         reference has no counterpart): arrays of shape (num_envs, 192) -- q (int64, INT64_MIN for an illegal

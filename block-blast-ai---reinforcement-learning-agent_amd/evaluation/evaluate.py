@@ -19,6 +19,11 @@ fused one-ply kernel); every other agent goes through ``act_device`` as before.
 the hand can still be placed in some order (``bb_plan_values``' safe words, from ``bb_safe_mask``: one more launch per move).  For
 ``--agent ppo`` they are AND-ed into the mask the policy samples under, for ``--agent random`` the agent draws from
 them; a position without a safe move keeps its legal mask.
+
+``--census`` (off by default) prices every refill: after each move that leaves an unfinished game with a whole new
+hand, ``bb_refill_census`` counts on the board as it stands how many of the 37^3 hands the dealer could have
+accepted, and the result gains, per episode and as means, the expected number of lost deals, the survival
+probability, the lowest and the mean solvable fraction and the number of refills (``census_summary``).
 """
 from __future__ import annotations
 
@@ -40,6 +45,32 @@ def _summary(scores, lengths, lines, combos) -> Dict[str, Any]:
         "mean_lines_cleared": np.mean(lines), "mean_max_combo": np.mean(combos),
         "scores": list(scores), "lengths": list(lengths),
     }
+
+
+CENSUS_KEYS = ("expected_losses", "survival", "min_solvable_fraction", "mean_solvable_fraction", "refills")
+
+
+def census_summary(counts: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """The per-episode census figures from the counts of every refill: counts int64 [R, n] on the CPU, row r the
+    census count of each game's board at its r-th refill step and -1 where that game had no refill then (finished).
+    With hazard = ``refill_hazard(count)`` and fraction = count / 37^3 over a game's refills: expected_losses = sum
+    of hazard, survival = product of (1 - hazard), min_solvable_fraction, mean_solvable_fraction (both 1.0 for a
+    game without a refill), float64 [n] each, and refills int64 [n].  Computed on the host from the integer counts,
+    so both backends give the same floats."""
+    from runtime.kernels import NUM_HANDS, refill_hazard
+
+    counts = counts.to(torch.int64).cpu()
+    n = counts.shape[1]
+    m = counts >= 0
+    c = counts.clamp(min=0)
+    one, zero = torch.ones((), dtype=torch.float64), torch.zeros((), dtype=torch.float64)
+    hz = torch.where(m, refill_hazard(c), zero)
+    frac = torch.where(m, c.double() / NUM_HANDS, one)
+    refills = m.sum(dim=0)
+    lowest = frac.min(dim=0).values if counts.shape[0] else torch.ones(n, dtype=torch.float64)
+    mean = torch.where(refills > 0, torch.where(m, frac, zero).sum(dim=0) / refills.clamp(min=1).double(), one)
+    return {"expected_losses": hz.sum(dim=0), "survival": (1.0 - hz).prod(dim=0), "min_solvable_fraction": lowest,
+            "mean_solvable_fraction": mean, "refills": refills}
 
 
 def _evaluate_sequential(agent, num_episodes: int, deterministic: bool, render: bool, seed: int,
@@ -75,19 +106,26 @@ def _evaluate_sequential(agent, num_episodes: int, deterministic: bool, render: 
 
 def evaluate_agent(agent, num_episodes: int = 100, deterministic: bool = True, render: bool = False,
                    seed: int = 42, max_moves: int = 100_000, record_actions: bool = False,
-                   safe_mask: bool = False, seeds=None) -> Dict[str, Any]:
+                   safe_mask: bool = False, seeds=None, census: bool = False) -> Dict[str, Any]:
     """evaluate.py:23-90 (same keys in the returned dict).  record_actions: also return every episode's
     action sequence under "actions" (for replaying the games elsewhere, e.g. through the oracle).  A game still
     running after max_moves moves is cut off there and reports its score, lines and max combo so far.
     safe_mask: an ``act_device`` agent samples under the legal mask AND the hand-safe mask (the legal mask alone
     where no move is safe); an ``act_env`` agent chooses its own mask (``RandomAgent(safe=True)``).
     seeds: one seed per episode (a list of num_episodes ints) in place of ``seed + e``, e.g. the same piece stream
-    for several episodes (``evaluation/tune.py``); not with render."""
+    for several episodes (``evaluation/tune.py``); not with render.
+    census: after every step that leaves an unfinished game with a whole hand -- a refill has just happened -- take
+    the refill census of the live boards (one ``bb_refill_census`` launch over all episodes; the games start together
+    and never reset, so their refills fall on the same steps).  It describes the deal before it was made: the hand
+    that was dealt is not read.  The result gains the CENSUS_KEYS as per-episode lists and their means as
+    "mean_<key>" (``census_summary``); not with render.  Without it the result is what it was."""
     agent.eval()
     if seeds is None:
         seeds = [seed + e for e in range(num_episodes)]
     elif render or len(seeds) != num_episodes:
         raise ValueError("evaluate_agent: seeds needs one seed per episode and excludes render")
+    if census and render:
+        raise ValueError("evaluate_agent: census excludes render")
     if render:
         return _evaluate_sequential(agent, num_episodes, deterministic, render, seed, record_actions)
     from runtime.device_env import DeviceEnvBatch
@@ -106,6 +144,10 @@ def evaluate_agent(agent, num_episodes: int = 100, deterministic: bool = True, r
     info64 = env.info.view(torch.int64).view(n, 7)
     info32 = env.info.view(torch.int32).view(n, 14)
     log = []
+    if census:
+        hand = torch.zeros(n, dtype=torch.int32, device=dev)
+        count = torch.zeros(n, dtype=torch.int32, device=dev)
+        census_rows = []
     act_env = getattr(agent, "act_env", None)
     for step in range(max_moves):
         if act_env is not None:
@@ -127,6 +169,11 @@ def evaluate_agent(agent, num_episodes: int = 100, deterministic: bool = True, r
         rec[:, 1] = torch.where(term, info32[:, 7].long(), rec[:, 1])
         rec[:, 2] = torch.where(term, info32[:, 8].long(), rec[:, 2])
         alive &= ~term
+        if census and step % 3 == 2:  # every game is on the third move of a hand, or over
+            env.snapshot(hand=hand)
+            env.refill_census(count=count)
+            whole = ((hand >> 18) & 7) == 0  # nothing of the hand used: it is a new one
+            census_rows.append(torch.where(alive & whole, count.long(), torch.full_like(count, -1, dtype=torch.int64)))
         if step % 16 == 15 and not bool(alive.any()):
             break
     if bool(alive.any()):  # games cut off by max_moves: their statistics so far (a finished game latched its own)
@@ -140,7 +187,22 @@ def evaluate_agent(agent, num_episodes: int = 100, deterministic: bool = True, r
     if record_actions:
         acts = torch.stack(log).cpu().numpy() if log else np.zeros((0, n), np.int32)
         res["actions"] = [acts[:int(lengths[e]), e].tolist() for e in range(n)]
+    if census:
+        rows = torch.stack(census_rows).cpu() if census_rows else torch.zeros((0, n), dtype=torch.int64)
+        for k, v in census_summary(rows).items():
+            res[k] = v.tolist()
+            res[f"mean_{k}"] = float(v.double().mean())
     return res
+
+
+def print_census(results: Dict[str, Any]) -> None:
+    """The census lines of the summary (``--census``)."""
+    print("\nRefill census:")
+    print(f"  Mean refills: {results['mean_refills']:.1f}")
+    print(f"  Expected lost deals per game: {results['mean_expected_losses']:.3e}")
+    print(f"  Mean survival probability: {results['mean_survival']:.6f}")
+    print(f"  Solvable fraction: mean {results['mean_mean_solvable_fraction']:.4f}, "
+          f"lowest {min(results['min_solvable_fraction']):.4f}")
 
 
 def print_results(results: Dict[str, Any]) -> None:
@@ -186,6 +248,9 @@ def main() -> None:
     ap.add_argument("--safe-mask", action="store_true",
                     help="--agent ppo / random: choose among hand-safe actions only (the legal moves after which "
                          "the rest of the hand still fits), among the legal ones where none is safe")
+    ap.add_argument("--census", action="store_true",
+                    help="price every refill: the exact probability that the deal fails on the board as it stands "
+                         "(expected lost deals, survival, solvable fractions per game)")
     args = ap.parse_args()
     if args.agent == "ppo":
         if args.checkpoint is None:
@@ -213,8 +278,11 @@ def main() -> None:
             agent.depth = args.depth
         print(f"Baseline agent: {args.agent}" + (" (hand-safe actions)" if getattr(agent, "safe", False) else ""))
     res = evaluate_agent(agent, num_episodes=args.episodes, deterministic=args.deterministic, render=args.render,
-                         seed=args.seed, max_moves=args.max_moves, safe_mask=args.safe_mask)
+                         seed=args.seed, max_moves=args.max_moves, safe_mask=args.safe_mask,
+                         **({"census": True} if args.census else {}))
     print_results(res)
+    if args.census:
+        print_census(res)
     if args.output:
         with open(args.output, "w") as f:
             json.dump({k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in res.items()}, f, indent=2,

@@ -6,14 +6,17 @@ method (CEM) over whole games: a population of candidate weight vectors plays th
 quarter refits a diagonal Gaussian, and so on.  What makes this cheap is ``bb_plan_actions_each``: one search launch
 per move serves the whole population, every env with the weights of its candidate (``PopulationPlanAgent``).
 
-``evaluate_population``  final scores int64 [P, G] of P candidates on G shared piece streams, one env batch
+``evaluate_population``  final scores int64 [P, G] of P candidates on G shared piece streams, one env batch; with
+                         ``census=True`` also what the refill census says of every game (``bb_refill_census``)
 ``cem``                  the objective-agnostic core (float64 on the host, integer candidates)
-``tune``                 CEM with the mean score as fitness; writes the agents' weights JSON and a JSONL log
+``tune``                 CEM with the mean score as fitness, or (``fitness="survival"``) the score discounted by the
+                         probability of surviving ``horizon`` moves; writes the agents' weights JSON and a JSONL log
 ``compare``              score per move of several weight sets on shared held-out games
 
 Every default below (population 64, 8 games, 300 moves, 30 generations, elite fraction 0.25, sigma0 300, scale 1000,
-sigma floor 10, 32 held-out games, ``dead`` fixed) is a starting point chosen by reasoning: none of them has been
-tuned.  Playing strength is reported, never asserted.
+sigma floor 10, 32 held-out games, ``dead`` fixed, and for ``fitness="survival"`` the form score * survival **
+(horizon / length) and horizon = moves) is a starting point chosen by reasoning: none of them has been tuned.
+Playing strength is reported, never asserted.
 """
 from __future__ import annotations
 
@@ -36,26 +39,49 @@ from .evaluate import evaluate_agent
 HOLDOUT_SEED_OFFSET = 10 ** 6  # the held-out games of ``tune`` are seeded seed + 10**6 + g
 
 
-def _play_population(weight_dicts: Sequence[Dict[str, int]], games: int, moves: int, seed: int, depth: int, device):
-    """(scores, lengths), int64 [P, G] each: env c * G + g plays candidate c on the piece stream seeded seed + g."""
+EXTRAS = ("expected_losses", "survival", "min_solvable_fraction", "refills")  # evaluate_population(census=True)
+
+
+def _play_population(weight_dicts: Sequence[Dict[str, int]], games: int, moves: int, seed: int, depth: int, device,
+                     census: bool = False):
+    """(scores, lengths, extras), int64 [P, G] each: env c * G + g plays candidate c on the piece stream seeded
+    seed + g.  extras: None, or with census the EXTRAS of ``evaluate_agent(census=True)`` as [P, G] tensors."""
     p, g = len(weight_dicts), int(games)
     rows = K.weight_rows(list(weight_dicts)).repeat_interleave(g, dim=0)
     agent = PopulationPlanAgent(rows, depth=depth, device=device)
-    res = evaluate_agent(agent, num_episodes=p * g, seeds=[seed + e % g for e in range(p * g)], max_moves=int(moves))
+    res = evaluate_agent(agent, num_episodes=p * g, seeds=[seed + e % g for e in range(p * g)], max_moves=int(moves),
+                         **({"census": True} if census else {}))
+    extras = None
+    if census:
+        extras = {k: torch.tensor(res[k], dtype=torch.int64 if k == "refills" else torch.float64).view(p, g)
+                  for k in EXTRAS}
     return (torch.tensor(res["scores"], dtype=torch.int64).view(p, g),
-            torch.tensor(res["lengths"], dtype=torch.int64).view(p, g))
+            torch.tensor(res["lengths"], dtype=torch.int64).view(p, g), extras)
 
 
 def evaluate_population(weight_dicts: Sequence[Dict[str, int]], games: int, moves: int, seed: int, depth: int = 3,
-                        device=None) -> torch.Tensor:
+                        device=None, census: bool = False):
     """The final score of every (candidate, game): int64 [P, G] on the CPU.  One ``DeviceEnvBatch`` of P * G envs
     without auto-reset; candidate c, game g is seeded ``seed + g`` -- common random numbers: every candidate sees the
     same G piece streams, so candidates differ by their play alone.  The accounting is ``evaluate_agent``'s: the
     score latched at termination, the score so far for a game cut off after ``moves`` moves.  ``depth`` 1..3 searches
     with ``bb_plan_actions_each``, 0 uses the one-ply greedy kernel.  Row c equals the ``scores`` of
     ``evaluate_agent(HandPlanAgent(weight_dicts[c], depth), num_episodes=G, seed=seed, max_moves=moves)`` when the
-    dict names all eight weights (a HandPlanAgent fills missing ones from DEFAULT_WEIGHTS, a row with zeros)."""
-    return _play_population(weight_dicts, games, moves, seed, depth, device)[0]
+    dict names all eight weights (a HandPlanAgent fills missing ones from DEFAULT_WEIGHTS, a row with zeros).
+    census=True: returns (scores, extras), extras holding float64 [P, G] tensors "expected_losses", "survival",
+    "min_solvable_fraction" and an int64 "refills" (``evaluation.evaluate.census_summary``).  The envs of a population
+    run without auto-reset and start together, so every live game refills on the same moves: one
+    ``bb_refill_census`` launch per three moves over all P * G boards, finished games masked."""
+    scores, _, extras = _play_population(weight_dicts, games, moves, seed, depth, device, census)
+    return (scores, extras) if census else scores
+
+
+def survival_fitness(scores: torch.Tensor, lengths: torch.Tensor, survival: torch.Tensor, horizon: int) -> torch.Tensor:
+    """``tune(fitness="survival")``'s objective per candidate, float64 [P]: the mean over games of
+    score_g * survival_g ** (horizon / max(length_g, 1)) -- the score discounted by the probability, at the hazard
+    rate the game showed over its own length, of getting through ``horizon`` moves without a lost deal."""
+    expo = float(horizon) / lengths.clamp(min=1).double()
+    return (scores.double() * survival.double() ** expo).mean(dim=1)
 
 
 def normalise(theta: np.ndarray, free: Sequence[int], scale: float) -> np.ndarray:
@@ -116,25 +142,38 @@ def _agent_depth(agent: str, depth: int) -> int:
     return int(depth) if agent == "plan" else 0  # 0: PopulationPlanAgent's one-ply greedy kernel
 
 
+def _extras_means(extras: Dict[str, torch.Tensor], c: int) -> Dict[str, float]:
+    """Candidate c's EXTRAS as columns: expected_losses summed over its games (to stand beside a count of ended
+    games), the others averaged, min_solvable_fraction as the lowest of its games."""
+    return {"expected_losses": float(extras["expected_losses"][c].sum()),
+            "survival": float(extras["survival"][c].mean()),
+            "min_solvable_fraction": float(extras["min_solvable_fraction"][c].min()),
+            "refills": float(extras["refills"][c].double().mean())}
+
+
 def compare(weight_dicts: Sequence[Dict[str, int]], games: int, moves: int, seed: int, depth: int = 3,
-            device=None) -> List[dict]:
+            device=None, census: bool = False) -> List[dict]:
     """Several weight sets on the same ``games`` piece streams (seeds seed + g), one population call: per set the mean
     score, the mean score per move (each game's score over its own moves) and its standard error over the games, and
-    the number of games that ended before the ``moves`` cut."""
-    scores, lengths = _play_population(weight_dicts, games, moves, seed, depth, device)
+    the number of games that ended before the ``moves`` cut.  census=True adds four columns: expected_losses (the
+    hazards of all the set's refills summed over its games -- the number of games the census expects the dealer to
+    have lost, beside ended_before_cut), survival (mean), min_solvable_fraction (lowest) and refills (mean)."""
+    scores, lengths, extras = _play_population(weight_dicts, games, moves, seed, depth, device, census)
     per_move = scores.double() / lengths.clamp(min=1).double()
     return [{"weights": dict(w), "mean_score": float(scores[c].double().mean()),
              "mean_length": float(lengths[c].double().mean()),
              "ended_before_cut": int((lengths[c] < int(moves)).sum()),
              "score_per_move": float(per_move[c].mean()),
-             "score_per_move_se": float(per_move[c].std(unbiased=True) / math.sqrt(games)) if games > 1 else 0.0}
+             "score_per_move_se": float(per_move[c].std(unbiased=True) / math.sqrt(games)) if games > 1 else 0.0,
+             **(_extras_means(extras, c) if census else {})}
             for c, w in enumerate(weight_dicts)]
 
 
 def tune(agent: str = "plan", depth: int = 3, population: int = 64, games: int = 8, moves: int = 300,
          generations: int = 30, elite_frac: float = 0.25, seed: int = 1, init: Optional[Dict[str, int]] = None,
          fixed: Sequence[str] = ("dead",), device=None, output: Optional[str] = None, log: Optional[str] = None,
-         sigma0: float = 300.0, scale: float = 1000, sigma_floor: float = 10, holdout_games: int = 32) -> dict:
+         sigma0: float = 300.0, scale: float = 1000, sigma_floor: float = 10, holdout_games: int = 32,
+         fitness: str = "score", horizon: Optional[int] = None) -> dict:
     """CEM over the weights of ``HandPlanAgent(depth)`` (agent "plan") or ``GreedyAgent`` (agent "greedy").
 
     Fitness is a candidate's mean final score over ``games`` games of at most ``moves`` moves
@@ -148,7 +187,19 @@ def tune(agent: str = "plan", depth: int = 3, population: int = 64, games: int =
     candidate 0 = the mean as it was played and its fitness) and one "final" record (the weights, the held-out comparison,
     the settings, the build id).  Deterministic for a given ``seed``: the sampling is numpy's ``default_rng(seed)``,
     the games are seeded, the search is exact.  Every default is untuned (see the module docstring).  Returns the
-    final record."""
+    final record.
+
+    ``fitness="survival"`` maximises ``survival_fitness`` instead: the mean over games of score_g * survival_g **
+    (horizon / max(length_g, 1)), survival_g from the refill census of the game's boards
+    (``evaluate_population(census=True)``); ``horizon`` defaults to ``moves``.  Its generation records gain
+    "mean_played_extras" and "best_extras" (the per-candidate means of the extras), the held-out comparison the
+    census columns, and the final record "fitness" and "horizon".  With ``fitness="score"`` the records are what they
+    were.  The form of the objective and the horizon are untuned."""
+    if fitness not in ("score", "survival"):
+        raise ValueError(f"fitness must be 'score' or 'survival', not {fitness!r}")
+    priced = fitness == "survival"
+    horizon = int(moves) if horizon is None else int(horizon)
+    extras_log: Dict[int, dict] = {}
     eval_depth = _agent_depth(agent, depth)
     init = dict(DEFAULT_WEIGHTS) if init is None else {**{k: 0 for k in L.GREEDY_FIELDS}, **init}
     L.greedy_weights(init)  # rejects unknown names
@@ -159,15 +210,21 @@ def tune(agent: str = "plan", depth: int = 3, population: int = 64, games: int =
     mean0 = np.array([init[k] for k in L.GREEDY_FIELDS], dtype=np.float64)
     t0 = time.perf_counter()
 
-    def fitness(cand: np.ndarray, k: int) -> np.ndarray:
-        scores = evaluate_population([_dict_of(c) for c in cand], games, moves, seed + k * games, eval_depth, device)
-        return scores.double().mean(dim=1).numpy()
+    def objective(cand: np.ndarray, k: int) -> np.ndarray:
+        sets = [_dict_of(c) for c in cand]
+        if not priced:
+            scores = evaluate_population(sets, games, moves, seed + k * games, eval_depth, device)
+            return scores.double().mean(dim=1).numpy()
+        scores, lengths, extras = _play_population(sets, games, moves, seed + k * games, eval_depth, device, True)
+        extras_log[k] = {key: extras[key].double().mean(dim=1).tolist() for key in EXTRAS}
+        return survival_fitness(scores, lengths, extras["survival"], horizon).numpy()
 
-    history = cem(fitness, mean0, sigma0, population, elite_frac, generations, np.random.default_rng(seed), free,
+    history = cem(objective, mean0, sigma0, population, elite_frac, generations, np.random.default_rng(seed), free,
                   scale=scale, sigma_floor=sigma_floor)
     final_theta = np.rint(normalise(history[-1]["mean"] if history else mean0, free, scale)).astype(np.int64)
     weights = _dict_of(final_theta)
-    held = compare([init, weights], holdout_games, moves, seed + HOLDOUT_SEED_OFFSET, eval_depth, device)
+    held = compare([init, weights], holdout_games, moves, seed + HOLDOUT_SEED_OFFSET, eval_depth, device,
+                   **({"census": True} if priced else {}))
     host = device is not None and torch.device(device).type == "cpu"
     final = {"record": "final", "agent": agent, "depth": int(depth) if agent == "plan" else None, "weights": weights,
              "init": init, "fixed": list(fixed),
@@ -178,6 +235,8 @@ def tune(agent: str = "plan", depth: int = 3, population: int = 64, games: int =
                           "sigma_floor": sigma_floor},
              "build_id": L.build_id(host=host), "backend": "host" if host else "hip",
              "wall_s": round(time.perf_counter() - t0, 3)}
+    if priced:
+        final["fitness"], final["horizon"] = fitness, horizon
     if output:
         doc = {"agent": agent, "weights": weights}
         if agent == "plan":
@@ -189,13 +248,18 @@ def tune(agent: str = "plan", depth: int = 3, population: int = 64, games: int =
         with open(log, "w") as f:
             for h in history:
                 best = int(h["elite"][0])
+                more = {}
+                if priced:
+                    ex = extras_log[h["generation"]]
+                    more = {"mean_played_extras": {key: ex[key][0] for key in EXTRAS},
+                            "best_extras": {key: ex[key][best] for key in EXTRAS}}
                 f.write(json.dumps({
                     "record": "generation", "generation": h["generation"],
                     "seeds": [seed + h["generation"] * games + g for g in range(games)],
                     "best_fitness": h["best_fitness"], "mean_fitness": h["mean_fitness"],
                     "mean_played": _dict_of(h["candidates"][0]), "mean_played_fitness": float(h["fitness"][0]),
                     "best": _dict_of(h["candidates"][best]),
-                    "mean": [float(x) for x in h["mean"]], "sigma": [float(x) for x in h["sigma"]]}) + "\n")
+                    "mean": [float(x) for x in h["mean"]], "sigma": [float(x) for x in h["sigma"]], **more}) + "\n")
             f.write(json.dumps(final) + "\n")
     return final
 
@@ -214,20 +278,33 @@ def main() -> None:
     ap.add_argument("--device", type=str, default=None, help="cpu = the host backend")
     ap.add_argument("--output", type=str, default=None, help="the tuned weights, in the agents' JSON format")
     ap.add_argument("--log", type=str, default=None, help="JSONL: one record per generation and a final one")
-    ap.add_argument("--compare", type=str, default=None,
-                    help="no tuning: play this weights JSON against DEFAULT_WEIGHTS on --games games seeded from --seed")
+    ap.add_argument("--compare", type=str, default=None, nargs="+",
+                    help="no tuning: play these weights JSON files against DEFAULT_WEIGHTS on --games games seeded "
+                         "from --seed")
+    ap.add_argument("--census", action="store_true",
+                    help="--compare: add the refill census columns (expected_losses, survival, "
+                         "min_solvable_fraction, refills)")
+    ap.add_argument("--fitness", choices=("score", "survival"), default="score",
+                    help="survival: the score discounted by the census' probability of surviving --horizon moves")
+    ap.add_argument("--horizon", type=int, default=None, help="--fitness survival: moves to survive (default --moves)")
     args = ap.parse_args()
     if args.compare:
-        with open(args.compare) as f:
-            other = json.load(f)["weights"]
-        res = compare([dict(DEFAULT_WEIGHTS), other], args.games, args.moves, args.seed, _agent_depth(args.agent, args.depth),
-                      args.device)
-        print(json.dumps({"record": "compare", "seed0": args.seed, "games": args.games, "moves": args.moves,
-                          "agent": args.agent, "depth": args.depth, "init": res[0], "other": res[1]}))
+        others = []
+        for path in args.compare:
+            with open(path) as f:
+                others.append(json.load(f)["weights"])
+        res = compare([dict(DEFAULT_WEIGHTS), *others], args.games, args.moves, args.seed,
+                      _agent_depth(args.agent, args.depth), args.device, **({"census": True} if args.census else {}))
+        rec = {"record": "compare", "seed0": args.seed, "games": args.games, "moves": args.moves,
+               "agent": args.agent, "depth": args.depth, "init": res[0], "other": res[1]}
+        if len(res) > 2:
+            rec["more"] = [{"file": os.path.basename(p), **r} for p, r in zip(args.compare[1:], res[2:])]
+        print(json.dumps(rec))
         return
     final = tune(agent=args.agent, depth=args.depth, population=args.population, games=args.games, moves=args.moves,
                  generations=args.generations, elite_frac=args.elite_frac, seed=args.seed,
-                 device=args.device, output=args.output, log=args.log, holdout_games=args.holdout_games)
+                 device=args.device, output=args.output, log=args.log, holdout_games=args.holdout_games,
+                 **({"fitness": args.fitness, "horizon": args.horizon} if args.fitness != "score" else {}))
     print(json.dumps(final))
 
 

@@ -356,6 +356,20 @@ class DeviceEnvBatch:
                 self.handle, self.lib)
         return out
 
+    def refill_census(self, count: Optional[torch.Tensor] = None, solvable: Optional[torch.Tensor] = None) -> dict:
+        """bb_refill_census on the live boards: count (int32 [N]) receives the number of the 37^3 ordered hands that
+        can still be placed on each env's board in some order, solvable (int64 [N, 37, 37]) the hands themselves (bit
+        c of word [a, b]).  Both None: a fresh count.  Returns the dict of what was written.  Reads the board column
+        and changes nothing, the piece stream included (see ``runtime.kernels.refill_census``)."""
+        from . import kernels as K
+
+        out = {k: t for k, t in (("count", count), ("solvable", solvable)) if t is not None}
+        out = out or K.census_outputs(self.num_envs, self.device)
+        o = K._census_out(out, self.num_envs, self.device)
+        L.check(self.lib.bb_refill_census(self.handle, C.byref(o), _stream(self.device)), "bb_refill_census",
+                self.handle, self.lib)
+        return out
+
     # ------------------------------------------------------------ host copies
     def state(self) -> dict:
         n = self.num_envs

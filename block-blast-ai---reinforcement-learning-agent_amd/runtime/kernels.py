@@ -1,5 +1,5 @@
 """torch-facing wrappers of the rollout-side HIP kernels (csrc/bb_ppo.hip,
-csrc/bb_env.hip expand, csrc/bb_lookahead.hip).  Inputs/outputs are device
+csrc/bb_env.hip expand, csrc/bb_lookahead.hip, csrc/bb_census.hip).  Inputs/outputs are device
 tensors; launches go on torch's current stream; nothing here falls back to
 CPU (the lookahead wrappers run on the host backend only for tensors the
 caller put on the CPU)."""
@@ -410,6 +410,60 @@ def safe_mask(board: torch.Tensor, hand: torch.Tensor, mode: int = SAFE_WORDS,
     lib, stream = _look_lib(dev)
     L.check(lib.bb_safe_mask_pos(C.byref(pos), n, int(mode), _p(out), stream), "bb_safe_mask_pos", lib=lib)
     return out
+
+
+# ---------------------------------------------------------------------------
+# The refill census (csrc/bb_census.hip; csrc/bb_host.cpp for CPU tensors)
+# ---------------------------------------------------------------------------
+NUM_HANDS = L.BB_NUM_HANDS  # 37^3 ordered hands
+CENSUS_OUTPUTS = {"count": (torch.int32, 1), "solvable": (torch.int64, L.BB_NUM_PIECES * L.BB_NUM_PIECES)}
+
+
+def census_outputs(n: int, dev, want=("count",)) -> dict:
+    """Fresh output tensors for ``refill_census``: count int32 [n], solvable int64 [n, 37, 37] (the bit patterns of
+    the u64 words)."""
+    unknown = set(want) - set(CENSUS_OUTPUTS)
+    if unknown:
+        raise L.BBNativeError(f"refill_census: unknown outputs {sorted(unknown)}; they are {tuple(CENSUS_OUTPUTS)}")
+    shapes = {"count": (n,), "solvable": (n, L.BB_NUM_PIECES, L.BB_NUM_PIECES)}
+    return {k: torch.empty(shapes[k], dtype=CENSUS_OUTPUTS[k][0], device=dev) for k in want}
+
+
+def _census_out(out: dict, n: int, dev) -> L.CensusOut:
+    """bb_census_out from a dict with "count" and / or "solvable" (missing or None = NULL)."""
+    table = {k: (k, dt, width) for k, (dt, width) in CENSUS_OUTPUTS.items()}
+    return _look_out(L.CensusOut, "refill_census", table, out, n, dev, shape="tensor of {numel} elements",
+                     at_least_one=True, known_only=True)
+
+
+def refill_census(board: torch.Tensor, want=("count",), out: Optional[dict] = None) -> dict:
+    """bb_refill_census_pos: for every board, which of the 37^3 hands the dealer would accept (bbvec.h "the refill
+    census"), in one launch.  board int64 [n] (bit r*8+c); n may be 0.  Returns a dict of the outputs named in
+    ``want`` (or the tensors of ``out``, written in place): "count" int32 [n] the number of ordered hands that can
+    be placed in some order, "solvable" int64 [n, 37, 37] with bit c of word [a, b] set for a solvable hand
+    {a, b, c}.  ``refill_hazard`` turns a count into the probability that the next deal cannot be played."""
+    if not (isinstance(board, torch.Tensor) and board.dtype == torch.int64 and board.dim() == 1
+            and board.is_contiguous()):
+        raise L.BBNativeError("refill_census: board must be a contiguous torch.int64 tensor of shape [n]")
+    n, dev = board.numel(), board.device
+    out = census_outputs(n, dev, want) if out is None else out
+    o = _census_out(out, n, dev)
+    if n == 0:  # an empty tensor has no storage to point at; the entry point would do nothing either
+        return out
+    lib, stream = _look_lib(dev)
+    L.check(lib.bb_refill_census_pos(_p(board), n, C.byref(o), stream), "bb_refill_census_pos", lib=lib)
+    return out
+
+
+def refill_hazard(count, attempts: int = 100) -> torch.Tensor:
+    """The probability that a dealer of ``attempts`` uniform draws (engine.py:155-172) ends on a hand that cannot
+    be played: (1 - count / 37^3) ** attempts as float64, computed as exp(attempts * log1p(-count / 37^3)); exactly
+    1 at count 0 and exactly 0 at count 37^3.  Above half of the hands the logarithm is taken of (37^3 - count) /
+    37^3 instead, whose numerator is an exact integer: 1 - p loses its digits there, the same function does not."""
+    c = torch.as_tensor(count).to(torch.int64)
+    log_q = torch.where(2 * c > NUM_HANDS, torch.log((NUM_HANDS - c).to(torch.float64) / NUM_HANDS),
+                        torch.log1p(-(c.to(torch.float64) / NUM_HANDS)))
+    return torch.exp(attempts * log_q)
 
 
 def unpack_rest(rest):

@@ -22,6 +22,7 @@ HOST_LIB_PATH = os.path.join(PKG_DIR, "libbbvec_host.so")
 BB_OK = 0
 BB_ACTIONS = 192
 BB_NUM_PIECES = 37
+BB_NUM_HANDS = 50653  # 37^3 ordered hands
 
 
 class BBNativeError(RuntimeError):
@@ -147,6 +148,11 @@ class PlanValuesOut(C.Structure):
     _fields_ = [("q", C.c_void_p), ("rest", C.c_void_p), ("leaves", C.c_void_p), ("safe", C.c_void_p)]
 
 
+class CensusOut(C.Structure):
+    """bb_census_out: device arrays count i32 [n], solvable u64 [n][37][37]; either may be NULL, not both."""
+    _fields_ = [("count", C.c_void_p), ("solvable", C.c_void_p)]
+
+
 _P = C.c_void_p
 _I32 = C.c_int32
 _U64 = C.c_uint64
@@ -239,6 +245,8 @@ SIGNATURES = {
     "bb_plan_values": (C.c_int, [_P, C.POINTER(GreedyWeights), _I32, C.POINTER(PlanValuesOut), _P]),
     "bb_safe_mask_pos": (C.c_int, [C.POINTER(Positions), _I32, _I32, _P, _P]),
     "bb_safe_mask": (C.c_int, [_P, _I32, _P, _P]),
+    "bb_refill_census_pos": (C.c_int, [_P, _I32, C.POINTER(CensusOut), _P]),
+    "bb_refill_census": (C.c_int, [_P, C.POINTER(CensusOut), _P]),
     "bb_masked_sample": (C.c_int, [_P, _P, _I32, _P, _U64, _U64, _U64, _I32, _P, _P, _P, _P, _P]),
     "bb_masked_sample_dstep": (C.c_int, [_P, _P, _I32, _U64, _P, _U64, _U64, _I32, _P, _P, _P, _P]),
     "bb_gae": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _F, _F, _P, _P, _P]),
@@ -303,7 +311,8 @@ HOST_SYMBOLS = ("bb_abi_version", "bb_build_id", "bb_create", "bb_destroy", "bb_
                 "bb_greedy_actions_pos", "bb_greedy_actions", "bb_plan_actions_pos", "bb_plan_actions",
                 "bb_greedy_actions_each_pos", "bb_greedy_actions_each", "bb_plan_actions_each_pos",
                 "bb_plan_actions_each",
-                "bb_plan_values_pos", "bb_plan_values", "bb_safe_mask_pos", "bb_safe_mask")
+                "bb_plan_values_pos", "bb_plan_values", "bb_safe_mask_pos", "bb_safe_mask",
+                "bb_refill_census_pos", "bb_refill_census")
 
 _lib = None
 _host = None

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """CLI: python tune.py --agent plan --depth 3 --population 64 --games 8 --moves 300 --generations 30 --seed 1 \\
                        --output weights.json --log tune.jsonl   (cross-entropy method over the search weights)
-        python tune.py --compare weights.json --games 100 --moves 3000 --seed 42   (against the defaults)"""
+        python tune.py --compare weights.json --games 100 --moves 3000 --seed 42   (against the defaults)
+        --fitness survival [--horizon N] prices survival by the refill census; --compare ... --census adds its columns"""
 import sys
 from pathlib import Path
 

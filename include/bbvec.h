@@ -62,7 +62,9 @@ extern "C" {
                                  (additive, still 9) bb_guided_loss_args with bb_guided_loss_forward / _backward /
                                  _fused: the PPO loss and the distillation cross-entropy on one softmax;
                                  (additive, still 9) bb_greedy_actions_each(_pos) and bb_plan_actions_each(_pos): one
-                                 row of weights per position, read from the memory of the position columns */
+                                 row of weights per position, read from the memory of the position columns;
+                                 (additive, still 9) bb_census_out with bb_refill_census(_pos): the exact count of
+                                 the 37^3 hands a board can still be dealt (engine.py:155-224) */
 
 #define BB_OK 0
 #define BB_ERR_ARG (-1)
@@ -482,6 +484,38 @@ int bb_plan_values(bb_env* env, const bb_greedy_weights* w, int32_t depth, const
 #define BB_SAFE_OR_LEGAL 1
 int bb_safe_mask_pos(const bb_positions* pos, int32_t n, int32_t mode, uint64_t* d_mask /* [n][3] */, void* stream);
 int bb_safe_mask(bb_env* env, int32_t mode, uint64_t* d_mask /* [N][3] */, void* stream);
+
+/* ---- the refill census -----------------------------------------------------------
+ * Replaces the dealer's acceptance test of engine.py:155-224 (_generate_valid_pieces
+ * with _can_place_all_pieces) as a random experiment by its exact outcome space: for
+ * a board B, which of the 37^3 ordered hands (a, b, c) the dealer would accept.
+ * Integers only.  A hand {a, b, c} is solvable on B iff for some order (x, y, z) of it
+ * there are anchors such that x fits B, y fits B1 = clear_full(B | x) and z fits
+ * clear_full(B1 | y): _can_place_all_pieces, and the same predicate as "bb_safe_mask
+ * mode 0 gives a non-zero word for the whole hand (a, b, c)".  It does not depend on
+ * the order, so
+ *   solvable[i][a][b]  bit c = hand {a, b, c} is solvable on board i; symmetric under
+ *                      every permutation of (a, b, c); bits 37..63 are zero
+ *   count[i]           = sum over a, b of popcount(solvable[i][a][b]), 0..BB_NUM_HANDS
+ * With p = count / BB_NUM_HANDS the dealer (up to 100 uniform draws, the 100th kept
+ * whatever it is) hands out a hand that cannot be played with probability (1 - p)^100.
+ * A crafted board with full lines is taken as it is, as in bb_afterstates.  Only the
+ * board is read: no hand, combo or reward config.  n == 0 does nothing.  BB_ERR_ARG
+ * (the rule named in bb_last_error, before any HIP call) for a NULL board, n < 0, a
+ * NULL out and an out with both pointers NULL.  The handle form reads the live board
+ * column and changes nothing, the RNG included, and refuses a handle in
+ * BB_ERR_DEVICE / BB_ERR_STATE.  Asynchronous on `stream`, no allocation, no sync
+ * (graph-capturable from the first call); indexing is 64-bit. */
+#define BB_NUM_HANDS 50653            /* 37^3 ordered hands */
+typedef struct bb_census_out {
+  int32_t*  count;     /* [n]          ordered hands (a,b,c) that engine.py:174-224 accepts on the board, 0..50653 */
+  uint64_t* solvable;  /* [n][37][37]  bit c of word [a][b] = hand {a,b,c} can be placed in some order; symmetric
+                          under every permutation of (a,b,c); bits 37..63 are zero */
+} bb_census_out;       /* device pointers (host pointers for libbbvec_host.so); either may be NULL, not both */
+/* replaces engine.py:155-224 for the positions given as a board column */
+int bb_refill_census_pos(const uint64_t* d_board, int32_t n, const bb_census_out* out, void* stream);
+/* replaces engine.py:155-224 for the handle's live boards ([N] / [N][37][37] outputs) */
+int bb_refill_census(bb_env* env, const bb_census_out* out, void* stream);
 
 /* Fused masked-categorical tail of BlockBlastNetwork.get_action_and_value
  * (network.py:173-180, 210-262; Categorical clamp semantics of torch 2.10):
