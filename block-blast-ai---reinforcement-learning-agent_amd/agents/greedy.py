@@ -6,6 +6,8 @@ device the envs live on: ``GreedyAgent`` through the fused ``bb_greedy_actions``
 integer value over the afterstates of the 192 actions, csrc/bb_lookahead.hip), ``RandomAgent`` through the
 Philox random-legal policy ``bb_random_actions``.  ``HandPlanAgent`` searches every way to play out the hand
 (``bb_plan_actions``, the fused search kernel of the same file; ``evaluate.py --agent plan``).
+``TwoHandPlanAgent`` looks past the refill that search stops at: below its best first moves it deals next hands by the
+dealer's law and searches them (``bb_play_plan_pos``, ``bb_refill_values``; ``evaluate.py --agent plan2``).
 ``PopulationPlanAgent`` is that search with weights of its own for every env (``bb_plan_actions_each``), which
 ``evaluation/tune.py`` tunes the weights with.  ``device="cpu"`` runs them on the host backend.
 """
@@ -133,6 +135,107 @@ class HandPlanAgent(GreedyAgent):
         if depth not in (1, 2, 3):
             raise ValueError(f"depth must be 1, 2 or 3, not {depth}")
         self.depth = depth
+
+
+class TwoHandPlanAgent(HandPlanAgent):
+    """``HandPlanAgent`` with a sampled look past the refill: a one-chance-node expectimax over the next hand.  Per
+    decision, all in integers:
+
+    1. ``plan_values`` at ``depth`` gives q[192] and the rest of the best sequence below every first move;
+    2. the candidates are the ``candidates`` legal actions with the largest q (stable descending sort: ties to the
+       lower action; fewer legal actions, fewer candidates; none: action 0);
+    3. ``play_plan`` on (a, rest[a]) gives each candidate's leaf board, combo, lines, score and status;
+    4. a leaf that is a refill is dealt ``deals`` next hands by ``refill_values`` -- stream id = the root position's
+       index in the batch, the same for all its candidates, so they meet the same draws (common random numbers); seed
+       = ``deal_seed(seed, move counter)`` -- and Q2[a] = deals * (w.lines * lines + w.score * score) + sum of the
+       dealt hands' values;
+    5. a leaf that is not a refill (the sequence ended dead, or ``depth`` cut it short) keeps Q2[a] = deals * q[a];
+    6. the action is the arg-max of Q2, ties to the lower action.
+
+    With ``candidates=1`` it plays what ``HandPlanAgent`` plays.  The defaults (8 candidates, 16 deals) are untuned."""
+
+    def __init__(self, weights: Optional[Dict[str, int]] = None, depth: int = 3, candidates: int = 8, deals: int = 16,
+                 seed: int = 0, device=None):
+        super().__init__(weights, depth, device)
+        if not 1 <= int(candidates) <= 192:
+            raise ValueError(f"candidates must be 1..192, not {candidates}")
+        if not 1 <= int(deals) <= L.BB_REFILL_MAX_DEALS:
+            raise ValueError(f"deals must be 1..{L.BB_REFILL_MAX_DEALS}, not {deals}")
+        self.candidates, self.deals, self.seed = int(candidates), int(deals), int(seed)
+        self.moves = 0  # decisions made so far: mixed into the deals' seed
+
+    @staticmethod
+    def deal_seed(seed: int, move: int) -> int:
+        """The Philox key of the deals of decision ``move`` (0-based): seed + (move + 1) * 0x9E3779B97F4A7C15 mod 2^64."""
+        return (int(seed) + (int(move) + 1) * 0x9E3779B97F4A7C15) & (2 ** 64 - 1)
+
+    def _decide(self, board, hand, combo, q, rest) -> torch.Tensor:
+        """Steps 2-6 for n positions: board i64 / hand i32 / combo i32 [n], q i64 / rest i32 [n, 192] -> int64 [n]."""
+        from runtime import kernels as K
+
+        n, k, m = board.numel(), self.candidates, self.deals
+        lowest = torch.iinfo(torch.int64).min
+        cand = torch.sort(q, dim=1, descending=True, stable=True).indices[:, :k]  # [n, k]
+        qc = q.gather(1, cand)
+        valid = qc != lowest
+        a2, a3 = K.unpack_rest(rest.gather(1, cand))
+        plan = torch.stack([cand.to(torch.int32), a2.to(torch.int32), a3.to(torch.int32)], dim=2)
+        plan = torch.where(valid.unsqueeze(2), plan, torch.full_like(plan, -1)).view(n * k, 3).contiguous()
+        leaf = K.play_plan(board.repeat_interleave(k), hand.repeat_interleave(k), plan, combo.repeat_interleave(k),
+                           want=("board", "combo", "lines", "score", "status"))
+        refill = ((leaf["status"] & K.PLAY_REFILL) != 0) & valid.view(-1)
+        q2 = torch.where(valid, m * qc, torch.full_like(qc, lowest)).view(-1)
+        idx = torch.nonzero(refill).view(-1)
+        if idx.numel():
+            root = torch.arange(n, dtype=torch.int64, device=board.device).repeat_interleave(k)
+            v = K.refill_values(leaf["board"][idx].contiguous(), self.weights, m, self.deal_seed(self.seed, self.moves),
+                                combo=leaf["combo"][idx].contiguous(), stream=root[idx].contiguous(),
+                                depth=self.depth)["value"]
+            moved = self.weights["lines"] * leaf["lines"][idx].long() + self.weights["score"] * leaf["score"][idx]
+            q2[idx] = m * moved + v.sum(dim=1)
+        q2 = q2.view(n, k)
+        best = q2.max(dim=1, keepdim=True).values
+        action = torch.where(q2 == best, cand, torch.full_like(cand, 192)).min(dim=1).values
+        self.moves += 1
+        return torch.where(valid.any(dim=1), action, torch.zeros_like(action))
+
+    def act_env(self, env_batch, out: torch.Tensor) -> torch.Tensor:
+        """The action of every env of a ``DeviceEnvBatch`` into out (int32 [N]); one decision of the move counter."""
+        n, dev = env_batch.num_envs, env_batch.device
+        pv = env_batch.plan_values(self.weights, self.depth,
+                                   out={"q": torch.empty((n, 192), dtype=torch.int64, device=dev),
+                                        "rest": torch.empty((n, 192), dtype=torch.int32, device=dev)})
+        board = torch.empty(n, dtype=torch.int64, device=dev)
+        hand = torch.empty(n, dtype=torch.int32, device=dev)
+        combo = torch.empty(n, dtype=torch.int32, device=dev)
+        env_batch.snapshot(board=board, hand=hand)
+        env_batch.snapshot_combo(combo)
+        out.copy_(self._decide(board, hand, combo, pv["q"], pv["rest"]))
+        return out
+
+    def select_action(self, observation: Dict[str, Any], deterministic: bool = True) -> Tuple[int, Dict[str, Any]]:
+        """From a Gym observation (no combo count in it: see ``GreedyAgent.select_action``)."""
+        from runtime import kernels as K
+
+        bits, hand = _position_of(observation)
+        board = torch.tensor([bits - (1 << 64) if bits >= 1 << 63 else bits], dtype=torch.int64, device=self.device)
+        hand_t = torch.tensor([hand], dtype=torch.int32, device=self.device)
+        pv = K.plan_values(board, hand_t, self.weights, self.depth, want=("q", "rest"))
+        action = self._decide(board, hand_t, torch.zeros(1, dtype=torch.int32, device=self.device), pv["q"], pv["rest"])
+        return int(action.cpu().item()), {}
+
+    def save(self, path: str) -> None:
+        with open(path, "w") as f:
+            json.dump({"agent": "plan2", "depth": self.depth, "candidates": self.candidates, "deals": self.deals,
+                       "seed": self.seed, "weights": self.weights}, f, indent=2)
+
+    def load(self, path: str) -> None:
+        super().load(path)
+        with open(path) as f:
+            data = json.load(f)
+        self.candidates = int(data.get("candidates", self.candidates))
+        self.deals = int(data.get("deals", self.deals))
+        self.seed = int(data.get("seed", self.seed))
 
 
 class PopulationPlanAgent(BaseAgent):

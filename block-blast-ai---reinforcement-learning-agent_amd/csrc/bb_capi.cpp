@@ -718,6 +718,35 @@ int bb_refill_census(bb_env* env, const bb_census_out* out, void* stream) {
                        [&] { return launch_refill_census(env->d.board, env->n, *out, (hipStream_t)stream); });
 }
 
+// Dealt next-hand values (refill_values_kernel, csrc/bb_lookahead.hip)
+int bb_refill_values_pos(const uint64_t* d_board, const int32_t* d_combo, const uint64_t* d_stream, int32_t n,
+                         const bb_greedy_weights* w, int32_t depth, int32_t deals, uint64_t seed,
+                         const bb_refill_values_out* out, void* stream) {
+  const char* rule = bb_look_rules::refill_values_pos(d_board, n, w, depth, deals, out);
+  if (!rule && n == 0) return BB_OK;  // accepted, and nothing to do
+  return look_pos_call("bb_refill_values_pos", rule, [&] {
+    return launch_refill_values(d_board, d_combo, d_stream, n, *w, depth, deals, seed, *out, (hipStream_t)stream);
+  });
+}
+
+int bb_refill_values(bb_env* env, const uint64_t* d_stream, const bb_greedy_weights* w, int32_t depth, int32_t deals,
+                     uint64_t seed, const bb_refill_values_out* out, void* stream) {
+  return look_env_call(env, "bb_refill_values", bb_look_rules::refill_values(w, depth, deals, out), [&] {
+    return launch_refill_values(env->d.board, env->d.combo, d_stream, env->n, *w, depth, deals, seed, *out,
+                                (hipStream_t)stream);
+  });
+}
+
+// A plan played to its leaf (play_plan_kernel, csrc/bb_lookahead.hip)
+int bb_play_plan_pos(const bb_positions* pos, int32_t n, const int32_t* d_plan, const bb_play_plan_out* out,
+                     void* stream) {
+  const char* rule = bb_look_rules::play_plan_pos(pos, n, d_plan, out);
+  if (!rule && n == 0) return BB_OK;  // accepted, and nothing to do
+  return look_pos_call("bb_play_plan_pos", rule, [&] {
+    return launch_play_plan(pos->board, pos->hand, pos->combo, n, d_plan, *out, (hipStream_t)stream);
+  });
+}
+
 int bb_masked_sample(const float* d_logits, const uint64_t* d_mask_bits, int32_t n, const float* d_uniform,
                      uint64_t seed, uint64_t step, uint64_t env_offset, int32_t deterministic,
                      const int64_t* d_action_in, int64_t* d_action, float* d_logp, float* d_entropy,

@@ -116,6 +116,14 @@ hipError_t launch_safe_mask(const uint64_t* board, const uint32_t* hand, int n, 
                             hipStream_t s);
 // the refill census (bb_census.hip): n > 0, board [n], out.count [n] / out.solvable [n][37][37], not both NULL
 hipError_t launch_refill_census(const uint64_t* board, int n, const bb_census_out& out, hipStream_t s);
+// dealt next-hand values (bb_lookahead.hip): n > 0, deals 1..1024, depth 1..3; board [n], combo [n] or NULL,
+// stream_id [n] or NULL; out.hand / value / attempts [n][deals], not all NULL
+hipError_t launch_refill_values(const uint64_t* board, const int32_t* combo, const uint64_t* stream_id, int n,
+                                const bb_greedy_weights& w, int depth, int deals, uint64_t seed,
+                                const bb_refill_values_out& out, hipStream_t s);
+// a plan played to its leaf (bb_lookahead.hip): n > 0, plan [n][3], the outputs [n], not all NULL
+hipError_t launch_play_plan(const uint64_t* board, const uint32_t* hand, const int32_t* combo, int n,
+                            const int32_t* plan, const bb_play_plan_out& out, hipStream_t s);
 hipError_t launch_masked_sample(const float* logits, const uint64_t* mbits, int n, const float* uniform,
                                 uint64_t seed, uint64_t step, const uint64_t* d_step, uint64_t offset,
                                 int deterministic, const int64_t* action_in, int64_t* action, float* logp,

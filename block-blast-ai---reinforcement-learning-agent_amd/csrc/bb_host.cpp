@@ -551,6 +551,95 @@ void refill_census_host(const uint64_t* board, int32_t n, const bb_census_out& o
   }
 }
 
+// Philox4x32-10 words 0..2 at counter (idx, step) under key seed: philox_w0's generator with the words kept
+void philox_w012(uint64_t seed, uint64_t idx, uint64_t step, uint32_t out[3]) {
+  uint32_t c0 = (uint32_t)idx, c1 = (uint32_t)(idx >> 32), c2 = (uint32_t)step, c3 = (uint32_t)(step >> 32);
+  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+  for (int r = 0; r < 10; ++r) {
+    if (r) {
+      k0 += 0x9E3779B9u;
+      k1 += 0xBB67AE85u;
+    }
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+    c1 = (uint32_t)p1;
+    c3 = (uint32_t)p0;
+    c0 = n0;
+    c2 = n2;
+  }
+  out[0] = c0;
+  out[1] = c1;
+  out[2] = c2;
+}
+
+// bbvec.h bb_refill_values (the host twin of refill_values_kernel): the dealer of engine.py:155-172 on Philox words
+// with this file's own solvable(), then plan_dfs on the dealt hand.  One (board, deal) pair per iteration.
+void refill_values_host(const uint64_t* board, const int32_t* combo, const uint64_t* stream_id, int32_t n,
+                        const bb_greedy_weights& w, int depth, int32_t deals, uint64_t seed,
+                        const bb_refill_values_out& out) {
+  const int64_t pairs = (int64_t)n * deals;
+#pragma omp parallel for schedule(dynamic, 1)  // the trees and the dealer loops differ by orders of magnitude
+  for (int64_t k = 0; k < pairs; ++k) {
+    const int64_t i = k / deals, j = k % deals;
+    const uint64_t B = board[i], idx = stream_id ? stream_id[i] : (uint64_t)i;
+    uint32_t id[3] = {0, 0, 0};
+    int32_t attempts = -100;
+    for (int t = 0; t < 100; ++t) {
+      uint32_t wd[3];
+      philox_w012(seed, idx, ((uint64_t)j << 7) | (uint64_t)t, wd);
+      for (int q = 0; q < 3; ++q) id[q] = (uint32_t)(((uint64_t)wd[q] * 37ull) >> 32);
+      if (solvable(B, id)) {
+        attempts = t + 1;
+        break;  // after 100 refusals the last draw stays (engine.py:171-172)
+      }
+    }
+    const uint32_t hand = hand_pack(id[0], id[1], id[2], 0u, false, false);
+    if (out.hand) out.hand[k] = hand;
+    if (out.attempts) out.attempts[k] = attempts;
+    if (out.value) {
+      PlanBest best{INT64_MIN, {-1, -1, -1}, 0, false};
+      int32_t seq[3];
+      plan_dfs(B, hand, combo ? combo[i] : 0, depth, 0, 0, seq, w, best);
+      out.value[k] = best.leaves ? best.value : (int64_t)w.dead;
+    }
+  }
+}
+
+// bbvec.h bb_play_plan_pos (the host twin of play_plan_kernel)
+void play_plan_host(const uint64_t* board, const uint32_t* hand, const int32_t* combo, int32_t n, const int32_t* plan,
+                    const bb_play_plan_out& out) {
+#pragma omp parallel for schedule(static)
+  for (int32_t i = 0; i < n; ++i) {
+    uint64_t B = board[i];
+    uint32_t h = hand[i];
+    int cb = combo ? combo[i] : 0;
+    int32_t lines = 0;
+    int64_t score = 0;
+    uint32_t status = 0;
+    for (int k = 0; k < 3; ++k) {
+      const int32_t act = plan[3 * (size_t)i + k];
+      if (act < 0) break;  // a ply not played
+      const After a = act < 192 ? eval_action(B, h, cb, act) : After{};
+      if (!a.legal) {
+        status |= BB_PLAY_ILLEGAL;
+        break;
+      }
+      B = a.board;
+      h = hand_use(h, act >> 6);
+      cb = a.combo1;
+      lines += a.lines;
+      score += a.gained;
+      status = (uint32_t)(k + 1) | (a.dead ? BB_PLAY_DEAD : 0u) | (a.refill ? BB_PLAY_REFILL : 0u);
+    }
+    if (out.board) out.board[i] = B;
+    if (out.hand) out.hand[i] = h;
+    if (out.combo) out.combo[i] = cb;
+    if (out.lines) out.lines[i] = lines;
+    if (out.score) out.score[i] = score;
+    if (out.status) out.status[i] = (int32_t)status;
+  }
+}
+
 }  // namespace
 
 #ifndef BB_BUILD_ID
@@ -932,6 +1021,33 @@ int bb_refill_census(bb_env* env, const bb_census_out* out, void* stream) {
   if (!env) return BB_ERR_ARG;
   if (int rc = refused(env, "bb_refill_census", R::refill_census(out))) return rc;
   refill_census_host(env->board.data(), env->n, *out);
+  return BB_OK;
+}
+
+int bb_refill_values_pos(const uint64_t* d_board, const int32_t* d_combo, const uint64_t* d_stream, int32_t n,
+                         const bb_greedy_weights* w, int32_t depth, int32_t deals, uint64_t seed,
+                         const bb_refill_values_out* out, void* stream) {
+  (void)stream;
+  if (int rc = refused(nullptr, "bb_refill_values_pos", R::refill_values_pos(d_board, n, w, depth, deals, out)))
+    return rc;
+  refill_values_host(d_board, d_combo, d_stream, n, *w, depth, deals, seed, *out);
+  return BB_OK;
+}
+
+int bb_refill_values(bb_env* env, const uint64_t* d_stream, const bb_greedy_weights* w, int32_t depth, int32_t deals,
+                     uint64_t seed, const bb_refill_values_out* out, void* stream) {
+  (void)stream;
+  if (!env) return BB_ERR_ARG;
+  if (int rc = refused(env, "bb_refill_values", R::refill_values(w, depth, deals, out))) return rc;
+  refill_values_host(env->board.data(), env->combo.data(), d_stream, env->n, *w, depth, deals, seed, *out);
+  return BB_OK;
+}
+
+int bb_play_plan_pos(const bb_positions* pos, int32_t n, const int32_t* d_plan, const bb_play_plan_out* out,
+                     void* stream) {
+  (void)stream;
+  if (int rc = refused(nullptr, "bb_play_plan_pos", R::play_plan_pos(pos, n, d_plan, out))) return rc;
+  play_plan_host(pos->board, pos->hand, pos->combo, n, d_plan, *out);
   return BB_OK;
 }
 

@@ -1,4 +1,4 @@
-// bb_look_rules.h -- the argument rules of the sixteen lookahead entry points of include/bbvec.h, one copy for
+// bb_look_rules.h -- the argument rules of the nineteen lookahead entry points of include/bbvec.h, one copy for
 // both backends (csrc/bb_capi.cpp and csrc/bb_host.cpp).  Plain C++, nothing from HIP.
 //
 // Each function returns the rule an argument set breaks, as the text that follows "<entry point>: " in
@@ -7,7 +7,8 @@
 //
 // Asymmetries that are part of the ABI as it stands: bb_afterstates_pos, bb_greedy_actions(_each)_pos and
 // bb_plan_actions(_each)_pos refuse n == 0 and answer every broken rule with one text; bb_plan_values_pos accepts n == 0
-// (and does nothing) and names the rule that broke, and so do bb_safe_mask_pos and bb_refill_census_pos.
+// (and does nothing) and names the rule that broke, and so do bb_safe_mask_pos, bb_refill_census_pos,
+// bb_refill_values_pos and bb_play_plan_pos.
 #pragma once
 #include <stdint.h>
 
@@ -102,6 +103,33 @@ inline const char* refill_census_pos(const uint64_t* board, int32_t n, const bb_
   if (!board) return "board is NULL";
   if (n < 0) return "n is negative";
   return refill_census(out);
+}
+
+// the dealt next-hand values: board (and combo, stream) columns, no bb_positions; n == 0 is accepted
+inline const char* refill_values(const bb_greedy_weights* w, int32_t depth, int32_t deals,
+                                 const bb_refill_values_out* out) {
+  if (!w) return "weights are NULL";
+  if (!out) return "out is NULL";
+  if (!out->hand && !out->value && !out->attempts) return "all three outputs are NULL";
+  if (bad_depth(depth)) return "depth must be 1..3";
+  if (deals < 1 || deals > BB_REFILL_MAX_DEALS) return "deals must be 1..1024";
+  return nullptr;
+}
+inline const char* refill_values_pos(const uint64_t* board, int32_t n, const bb_greedy_weights* w, int32_t depth,
+                                     int32_t deals, const bb_refill_values_out* out) {
+  if (!board) return "board is NULL";
+  if (n < 0) return "n is negative";
+  return refill_values(w, depth, deals, out);
+}
+
+inline const char* play_plan_pos(const bb_positions* pos, int32_t n, const int32_t* plan, const bb_play_plan_out* out) {
+  if (no_positions(pos)) return "positions (board, hand) are NULL";
+  if (n < 0) return "n is negative";
+  if (!plan) return "d_plan is NULL";
+  if (!out) return "out is NULL";
+  if (!out->board && !out->hand && !out->combo && !out->lines && !out->score && !out->status)
+    return "all six outputs are NULL";
+  return nullptr;
 }
 
 }  // namespace bb_look_rules

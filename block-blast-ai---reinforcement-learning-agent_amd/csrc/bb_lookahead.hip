@@ -611,6 +611,208 @@ safe_mask_kernel(LookTable t, LookPos pos, int n, int mode, uint64_t* __restrict
   }
 }
 
+// ---------------------------------------------------------------------------
+// Dealt next-hand values (bbvec.h bb_refill_values): the chance node behind a refill.  For (board i, deal j) the
+// dealer of engine.py:155-172 on Philox words, then plan_kernel's search of the dealt hand.
+//
+// One workgroup of four waves per (board, deal) pair; above the grid cap the workgroups stride over the pairs
+// (i, j advance by the grid size without a 64-bit division).
+//   deal    the four waves test four consecutive draws at once: round r, wave k takes draw t = 4r + k.  Everything
+//           of a draw is wave-uniform -- counter, Philox words and ids in scalar registers, the piece rows scalar
+//           loads from the by-value table.  The acceptance test is safe_mask_kernel's existence search with the
+//           wave leaving at the first lane that succeeds (census_kernel's full pass): lane = anchor of the first
+//           piece, trip k tries the k-th lowest anchor of either order of the other two, the three choices of a
+//           first piece in turn.  The waves post (ids, accepted) in LDS, one barrier per round (two buffers), and
+//           the lowest accepted draw of the round wins; every wave reads the same four words, so all leave the
+//           loop together.  At most 25 rounds; an open board ends in the first.
+//   search  plan_kernel's body on the position (board, dealt hand, combo): plan_ply1 / plan_compact /
+//           plan_record_turn<false> / plan_wave_join.  The key is carried and dropped at the end: it costs two
+//           registers a lane, and the body stays the one the plan kernels use.
+// Trip bounds: 25 rounds, 3 first pieces, 64 pair trips, <= 192 records, 3 slots, 64 mask bits.  No atomics, no
+// inline assembly, nothing between workgroups.
+// ---------------------------------------------------------------------------
+constexpr int64_t kRefillMaxGrid = 1 << 14;  // more (board, deal) pairs than this: the workgroups stride over them
+constexpr int kRefillRounds = kMaxAttempts / kPlanWaves;
+static_assert(kRefillRounds * kPlanWaves == kMaxAttempts, "a round is one draw per wave");
+constexpr uint32_t kRefillAccepted = 1u << 31;  // above the 18 id bits of a posted hand
+
+struct RefillCols {
+  const uint64_t* board;
+  const int32_t* combo;    // NULL: 0
+  const uint64_t* stream;  // NULL: i
+};
+
+// Can the whole hand (ids < kPieces, nothing used) be placed on B in some order?  Wave-uniform answer.
+__device__ __forceinline__ bool hand_fits(const LookTable& t, uint64_t B, uint32_t hand, int cell) {
+  bool found = false;
+#pragma unroll 1
+  for (int p = 0; p < kHand && !found; ++p) {
+    const PieceRow& pa = t.row[hand_id(hand, p)];
+    const PieceRow& pb = t.row[hand_id(hand, p == 0 ? 1 : 0)];
+    const PieceRow& pc = t.row[hand_id(hand, p == 2 ? 1 : 2)];
+    const bool legal = (anchors_of(pa, B) >> cell) & 1ull;
+    const uint64_t B1 = clear_full(B | (pa.shape << cell));
+    uint64_t mb = legal ? anchors_of(pb, B1) : 0ull;
+    uint64_t mc = legal ? anchors_of(pc, B1) : 0ull;
+#pragma unroll 1
+    for (int it = 0; it < 64; ++it) {
+      if (__ballot((mb | mc) != 0ull) == 0ull) break;  // every lane has run out of anchors
+      const int y = (__ffsll((unsigned long long)mb) - 1) & 63;
+      const int z = (__ffsll((unsigned long long)mc) - 1) & 63;
+      const bool leaf_b = (mb != 0ull) & (anchors_of(pc, clear_full(B1 | (pb.shape << y))) != 0ull);
+      const bool leaf_c = (mc != 0ull) & (anchors_of(pb, clear_full(B1 | (pc.shape << z))) != 0ull);
+      mb &= mb - 1ull;  // 0 stays 0
+      mc &= mc - 1ull;
+      if (__ballot(leaf_b | leaf_c) != 0ull) {
+        found = true;
+        break;
+      }
+    }
+  }
+  return found;
+}
+
+__global__ void __launch_bounds__(kPlanBlock)
+refill_values_kernel(LookTable t, RefillCols cols, int n, int m, bb_greedy_weights w, int depth, uint64_t seed,
+                     bb_refill_values_out out) {
+  __shared__ PlanRecord s_rec[kPlanRecords];
+  __shared__ int s_cnt[kHand];
+  __shared__ int64_t s_v[kPlanWaves];
+  __shared__ uint32_t s_deal[2][kPlanWaves];
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int cell = (int)(threadIdx.x & 63u);
+  const uint32_t um = (uint32_t)m;                                   // 1..1024
+  const uint32_t gi = gridDim.x / um, gj = gridDim.x - gi * um;      // the stride in (i, j)
+  int64_t i = (int64_t)(blockIdx.x / um);
+  uint32_t j = blockIdx.x - (uint32_t)i * um;
+  while (i < (int64_t)n) {
+    const uint64_t B = uniform64(cols.board[i]);
+    const int combo = (int)uniform32(cols.combo ? (uint32_t)cols.combo[i] : 0u);
+    const uint64_t idx = cols.stream ? uniform64(cols.stream[i]) : (uint64_t)i;
+
+    // ---- the deal
+    uint32_t ids = 0u;
+    int attempts = -kMaxAttempts;
+#pragma unroll 1
+    for (int r = 0; r < kRefillRounds; ++r) {
+      uint32_t wd[4];
+      philox_words(seed, idx, ((uint64_t)j << 7) | (uint64_t)(r * kPlanWaves + wave), wd);
+      const uint32_t a = uniform32((uint32_t)(((uint64_t)wd[0] * (uint32_t)kPieces) >> 32));
+      const uint32_t b = uniform32((uint32_t)(((uint64_t)wd[1] * (uint32_t)kPieces) >> 32));
+      const uint32_t c = uniform32((uint32_t)(((uint64_t)wd[2] * (uint32_t)kPieces) >> 32));
+      const uint32_t h = hand_pack(a, b, c, 0u, false, false);
+      const bool ok = hand_fits(t, B, h, cell);
+      if (cell == 0) s_deal[r & 1][wave] = h | (ok ? kRefillAccepted : 0u);
+      __syncthreads();  // the other buffer is rewritten only after the next round's barrier: every wave has read this one
+      const uint32_t d0 = uniform32(s_deal[r & 1][0]), d1 = uniform32(s_deal[r & 1][1]);
+      const uint32_t d2 = uniform32(s_deal[r & 1][2]), d3 = uniform32(s_deal[r & 1][3]);
+      const int k = (d0 & kRefillAccepted) ? 0 : (d1 & kRefillAccepted) ? 1 : (d2 & kRefillAccepted) ? 2 : 3;
+      const uint32_t dk = k == 0 ? d0 : (k == 1 ? d1 : (k == 2 ? d2 : d3));
+      ids = dk & kHandIds;  // the round's first accepted draw, else its last one (the 100th in the last round)
+      if (dk & kRefillAccepted) {
+        attempts = r * kPlanWaves + k + 1;
+        break;  // the same four words in every wave: the workgroup leaves together
+      }
+    }
+
+    // ---- the search of the dealt hand (plan_kernel's body)
+    const Position P{B, ids, combo};
+    int64_t best = INT64_MIN;  // below every legal value (see greedy_kernel)
+    uint32_t best_key = kPlanNoKey;
+    int leaves = 0;
+    bool unused = false;
+    const Ply1 ply1 = plan_ply1(t, P, depth, wave, cell);
+    if (ply1.closed) {
+      best = move_terms(w, ply1.a) + state_terms(w, ply1.a);
+      best_key = ((uint32_t)(wave * 64 + cell) << 16) | 0xFFFFu;
+    }
+    const int total = plan_compact(s_rec, s_cnt, w, ply1, wave, cell);
+    for (int r = wave; r < total; r += kPlanWaves)
+      plan_record_turn<false>(t, s_rec[r], P.hand, w, depth, cell, best, best_key, leaves, unused);
+    plan_wave_join(best, best_key, leaves);
+    if (cell == 0) s_v[wave] = best;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+      for (int k = 1; k < kPlanWaves; ++k) best = s_v[k] > best ? s_v[k] : best;
+      const int64_t o = i * (int64_t)m + (int64_t)j;
+      if (out.hand) out.hand[o] = ids;
+      if (out.value) out.value[o] = best == INT64_MIN ? (int64_t)w.dead : best;  // no legal first move
+      if (out.attempts) out.attempts[o] = attempts;
+    }
+    // no barrier here: the next pair's first LDS writes are s_deal, s_cnt and s_rec; s_v is rewritten only after
+    // barriers that thread 0 has to reach first
+
+    j += gj;
+    i += (int64_t)gi;
+    if (j >= um) {
+      j -= um;
+      ++i;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// A plan played to its leaf (bbvec.h bb_play_plan_pos): one lane per position, up to three one-ply moves
+// (eval_action, the move of every kernel above).  The pieces differ from lane to lane, so the table is copied into
+// LDS once per workgroup, as census_kernel does.  Trip bound: 3 plies.  No atomics, no inline assembly.
+// ---------------------------------------------------------------------------
+constexpr int kPlayBlock = 256;
+constexpr int64_t kPlayMaxGrid = 1 << 15;
+constexpr int kRowWords = (int)(sizeof(PieceRow) / sizeof(uint64_t));
+static_assert(sizeof(PieceRow) % sizeof(uint64_t) == 0, "the table is copied to LDS as 64-bit words");
+
+__global__ void __launch_bounds__(kPlayBlock)
+play_plan_kernel(LookTable t, LookPos pos, int n, const int32_t* __restrict__ plan, bb_play_plan_out out) {
+  __shared__ LookTable s_t;
+  {
+    const uint64_t* src = reinterpret_cast<const uint64_t*>(&t);
+    uint64_t* dst = reinterpret_cast<uint64_t*>(&s_t);
+    for (int k = (int)threadIdx.x; k < kPieces * kRowWords; k += kPlayBlock) dst[k] = src[k];
+  }
+  __syncthreads();
+  const int64_t stride = (int64_t)gridDim.x * kPlayBlock;
+  for (int64_t i = (int64_t)blockIdx.x * kPlayBlock + threadIdx.x; i < (int64_t)n; i += stride) {
+    uint64_t B = pos.board[i];
+    uint32_t hand = pos.hand[i];
+    int combo = pos.combo ? pos.combo[i] : 0;
+    int lines = 0;
+    int64_t score = 0;
+    uint32_t status = 0u;
+    bool go = true;
+#pragma unroll 1
+    for (int k = 0; k < kHand; ++k) {
+      const int act = plan[i * kHand + k];
+      go = go && act >= 0;
+      if (!go) continue;
+      const int p = act >> 6;
+      if (p >= kHand) {  // not an action
+        status |= BB_PLAY_ILLEGAL;
+        go = false;
+        continue;
+      }
+      const After a = eval_action(s_t, B, hand, combo, p, act & 63);
+      if (!a.legal) {
+        status |= BB_PLAY_ILLEGAL;
+        go = false;
+        continue;
+      }
+      B = a.board;
+      hand = hand_use(hand, p);
+      combo = a.combo1;
+      lines += a.lines;
+      score += a.gained;
+      status = (uint32_t)(k + 1) | (a.dead ? BB_PLAY_DEAD : 0u) | (a.refill ? BB_PLAY_REFILL : 0u);
+    }
+    if (out.board) out.board[i] = B;
+    if (out.hand) out.hand[i] = hand;
+    if (out.combo) out.combo[i] = combo;
+    if (out.lines) out.lines[i] = lines;
+    if (out.score) out.score[i] = score;
+    if (out.status) out.status[i] = (int32_t)status;
+  }
+}
+
 const LookTable& look_table() {
   static const LookTable t = [] {
     LookTable x;
@@ -678,6 +880,26 @@ hipError_t launch_safe_mask(const uint64_t* board, const uint32_t* hand, int n, 
   const int64_t blocks = ((int64_t)n + kSafeWaves - 1) / kSafeWaves;
   const dim3 grid((unsigned)(blocks < kSafeMaxGrid ? blocks : kSafeMaxGrid));
   hipLaunchKernelGGL(safe_mask_kernel, grid, dim3(kSafeBlock), 0, s, look_table(), pos, n, mode, mask);
+  return hipGetLastError();
+}
+
+hipError_t launch_refill_values(const uint64_t* board, const int32_t* combo, const uint64_t* stream_id, int n,
+                                const bb_greedy_weights& w, int depth, int deals, uint64_t seed,
+                                const bb_refill_values_out& out, hipStream_t s) {
+  const RefillCols cols{board, combo, stream_id};
+  const int64_t pairs = (int64_t)n * deals;
+  const dim3 grid((unsigned)(pairs < kRefillMaxGrid ? pairs : kRefillMaxGrid));
+  hipLaunchKernelGGL(refill_values_kernel, grid, dim3(kPlanBlock), 0, s, look_table(), cols, n, deals, w, depth, seed,
+                     out);
+  return hipGetLastError();
+}
+
+hipError_t launch_play_plan(const uint64_t* board, const uint32_t* hand, const int32_t* combo, int n,
+                            const int32_t* plan, const bb_play_plan_out& out, hipStream_t s) {
+  const LookPos pos{board, hand, combo, nullptr};
+  const int64_t blocks = ((int64_t)n + kPlayBlock - 1) / kPlayBlock;
+  const dim3 grid((unsigned)(blocks < kPlayMaxGrid ? blocks : kPlayMaxGrid));
+  hipLaunchKernelGGL(play_plan_kernel, grid, dim3(kPlayBlock), 0, s, look_table(), pos, n, plan, out);
   return hipGetLastError();
 }
 

@@ -15,6 +15,9 @@ Beyond the reference: ``--agent greedy`` / ``--agent plan`` / ``--agent random``
 compared with.  An agent with ``act_env(env_batch, out)`` picks its actions from the device env itself (the
 fused one-ply kernel); every other agent goes through ``act_device`` as before.
 
+``--agent plan2`` is ``TwoHandPlanAgent``: the full-hand search with a sampled look past the refill
+(``--candidates`` first moves, ``--deals`` dealt next hands each, ``bb_refill_values``; both defaults are untuned).
+
 ``--safe-mask`` (off by default) restricts the policy to hand-safe actions: the legal moves after which the rest of
 the hand can still be placed in some order (``bb_plan_values``' safe words, from ``bb_safe_mask``: one more launch per move).  For
 ``--agent ppo`` they are AND-ed into the mask the policy samples under, for ``--agent random`` the agent draws from
@@ -231,10 +234,15 @@ def print_results(results: Dict[str, Any]) -> None:
 def main() -> None:
     """evaluate.py:119-184 (same flags)."""
     ap = argparse.ArgumentParser(description="Evaluate Block Blast AI")
-    ap.add_argument("--agent", choices=("ppo", "greedy", "plan", "random"), default="ppo",
-                    help="ppo: the checkpoint's policy; greedy / plan / random: the untrained baselines "
-                         "(plan: exhaustive search over the whole hand)")
-    ap.add_argument("--depth", type=int, choices=(1, 2, 3), default=3, help="--agent plan: moves searched ahead")
+    ap.add_argument("--agent", choices=("ppo", "greedy", "plan", "plan2", "random"), default="ppo",
+                    help="ppo: the checkpoint's policy; greedy / plan / plan2 / random: the untrained baselines "
+                         "(plan: exhaustive search over the whole hand; plan2: that search with a sampled look past "
+                         "the refill, dealt next hands searched below its best first moves)")
+    ap.add_argument("--depth", type=int, choices=(1, 2, 3), default=3, help="--agent plan / plan2: moves searched ahead")
+    ap.add_argument("--candidates", type=int, default=8,
+                    help="--agent plan2: first moves looked past the refill (untuned default)")
+    ap.add_argument("--deals", type=int, default=16,
+                    help="--agent plan2: next hands dealt per candidate (untuned default)")
     ap.add_argument("--checkpoint", type=str, default=None, help="required for --agent ppo")
     ap.add_argument("--episodes", type=int, default=100)
     ap.add_argument("--deterministic", action="store_true")
@@ -265,17 +273,21 @@ def main() -> None:
         agent.load(args.checkpoint)
         print(f"Loaded model from {args.checkpoint}")
     else:
-        from agents.greedy import GreedyAgent, HandPlanAgent, RandomAgent
+        from agents.greedy import GreedyAgent, HandPlanAgent, RandomAgent, TwoHandPlanAgent
 
         if args.agent == "plan":
             agent = HandPlanAgent(device=args.device)
+        elif args.agent == "plan2":
+            agent = TwoHandPlanAgent(seed=args.seed, device=args.device)
         else:
             agent = (GreedyAgent(device=args.device) if args.agent == "greedy"
                      else RandomAgent(device=args.device, safe=args.safe_mask))
         if args.weights:
             agent.load(args.weights)
-        if args.agent == "plan":
+        if args.agent in ("plan", "plan2"):
             agent.depth = args.depth
+        if args.agent == "plan2":  # the command line decides, as it does for --depth
+            agent.candidates, agent.deals = args.candidates, args.deals
         print(f"Baseline agent: {args.agent}" + (" (hand-safe actions)" if getattr(agent, "safe", False) else ""))
     res = evaluate_agent(agent, num_episodes=args.episodes, deterministic=args.deterministic, render=args.render,
                          seed=args.seed, max_moves=args.max_moves, safe_mask=args.safe_mask,

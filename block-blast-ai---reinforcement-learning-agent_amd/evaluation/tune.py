@@ -12,6 +12,8 @@ per move serves the whole population, every env with the weights of its candidat
 ``tune``                 CEM with the mean score as fitness, or (``fitness="survival"``) the score discounted by the
                          probability of surviving ``horizon`` moves; writes the agents' weights JSON and a JSONL log
 ``compare``              score per move of several weight sets on shared held-out games
+``compare_two_hand``     the same records with every set played by a ``TwoHandPlanAgent`` (``--compare ... --agent
+                         plan2 --candidates K --deals M``; both defaults, 8 and 16, are untuned)
 
 Every default below (population 64, 8 games, 300 moves, 30 generations, elite fraction 0.25, sigma0 300, scale 1000,
 sigma floor 10, 32 held-out games, ``dead`` fixed, and for ``fitness="survival"`` the form score * survival **
@@ -159,14 +161,40 @@ def compare(weight_dicts: Sequence[Dict[str, int]], games: int, moves: int, seed
     hazards of all the set's refills summed over its games -- the number of games the census expects the dealer to
     have lost, beside ended_before_cut), survival (mean), min_solvable_fraction (lowest) and refills (mean)."""
     scores, lengths, extras = _play_population(weight_dicts, games, moves, seed, depth, device, census)
+    return _compare_records(weight_dicts, scores, lengths, extras, games, moves)
+
+
+def _compare_records(weight_dicts, scores, lengths, extras, games: int, moves: int) -> List[dict]:
+    """``compare``'s records from scores / lengths int64 [P, G] and the census extras (or None)."""
     per_move = scores.double() / lengths.clamp(min=1).double()
     return [{"weights": dict(w), "mean_score": float(scores[c].double().mean()),
              "mean_length": float(lengths[c].double().mean()),
              "ended_before_cut": int((lengths[c] < int(moves)).sum()),
              "score_per_move": float(per_move[c].mean()),
              "score_per_move_se": float(per_move[c].std(unbiased=True) / math.sqrt(games)) if games > 1 else 0.0,
-             **(_extras_means(extras, c) if census else {})}
+             **(_extras_means(extras, c) if extras is not None else {})}
             for c, w in enumerate(weight_dicts)]
+
+
+def compare_two_hand(weight_dicts: Sequence[Dict[str, int]], games: int, moves: int, seed: int, depth: int = 3,
+                     candidates: int = 8, deals: int = 16, device=None, census: bool = False) -> List[dict]:
+    """``compare`` with every weight set played by a ``TwoHandPlanAgent(depth, candidates, deals)`` (``--agent
+    plan2``): the same games (seeds seed + g) and the same records.  The agent takes one weight set, so the sets are
+    played one after another, ``games`` envs each, and every agent's deals are keyed by ``seed``."""
+    from agents.greedy import TwoHandPlanAgent
+
+    rows = []
+    for w in weight_dicts:
+        agent = TwoHandPlanAgent(w, depth=depth, candidates=candidates, deals=deals, seed=seed, device=device)
+        rows.append(evaluate_agent(agent, num_episodes=int(games), seeds=[seed + g for g in range(int(games))],
+                                   max_moves=int(moves), **({"census": True} if census else {})))
+    scores = torch.tensor([r["scores"] for r in rows], dtype=torch.int64)
+    lengths = torch.tensor([r["lengths"] for r in rows], dtype=torch.int64)
+    extras = None
+    if census:
+        extras = {k: torch.tensor([r[k] for r in rows], dtype=torch.int64 if k == "refills" else torch.float64)
+                  for k in EXTRAS}
+    return _compare_records(weight_dicts, scores, lengths, extras, games, moves)
 
 
 def tune(agent: str = "plan", depth: int = 3, population: int = 64, games: int = 8, moves: int = 300,
@@ -266,7 +294,10 @@ def tune(agent: str = "plan", depth: int = 3, population: int = 64, games: int =
 
 def main() -> None:
     ap = argparse.ArgumentParser(description="Tune the search agents' weights by the cross-entropy method")
-    ap.add_argument("--agent", choices=("plan", "greedy"), default="plan")
+    ap.add_argument("--agent", choices=("plan", "greedy", "plan2"), default="plan",
+                    help="plan2 (--compare only): the two-hand agent, a sampled look past the refill")
+    ap.add_argument("--candidates", type=int, default=8, help="--agent plan2: first moves looked past the refill (untuned)")
+    ap.add_argument("--deals", type=int, default=16, help="--agent plan2: next hands dealt per candidate (untuned)")
     ap.add_argument("--depth", type=int, choices=(1, 2, 3), default=3, help="--agent plan: moves searched ahead")
     ap.add_argument("--population", type=int, default=64)
     ap.add_argument("--games", type=int, default=8, help="games per candidate and generation (shared piece streams)")
@@ -293,14 +324,23 @@ def main() -> None:
         for path in args.compare:
             with open(path) as f:
                 others.append(json.load(f)["weights"])
-        res = compare([dict(DEFAULT_WEIGHTS), *others], args.games, args.moves, args.seed,
-                      _agent_depth(args.agent, args.depth), args.device, **({"census": True} if args.census else {}))
+        if args.agent == "plan2":
+            res = compare_two_hand([dict(DEFAULT_WEIGHTS), *others], args.games, args.moves, args.seed, args.depth,
+                                   args.candidates, args.deals, args.device, **({"census": True} if args.census else {}))
+        else:
+            res = compare([dict(DEFAULT_WEIGHTS), *others], args.games, args.moves, args.seed,
+                          _agent_depth(args.agent, args.depth), args.device,
+                          **({"census": True} if args.census else {}))
         rec = {"record": "compare", "seed0": args.seed, "games": args.games, "moves": args.moves,
                "agent": args.agent, "depth": args.depth, "init": res[0], "other": res[1]}
+        if args.agent == "plan2":
+            rec.update(candidates=args.candidates, deals=args.deals)
         if len(res) > 2:
             rec["more"] = [{"file": os.path.basename(p), **r} for p, r in zip(args.compare[1:], res[2:])]
         print(json.dumps(rec))
         return
+    if args.agent == "plan2":
+        ap.error("--agent plan2 is for --compare: the tuner's fitness does not look past the refill")
     final = tune(agent=args.agent, depth=args.depth, population=args.population, games=args.games, moves=args.moves,
                  generations=args.generations, elite_frac=args.elite_frac, seed=args.seed,
                  device=args.device, output=args.output, log=args.log, holdout_games=args.holdout_games,

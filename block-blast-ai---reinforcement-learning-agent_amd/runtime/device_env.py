@@ -370,6 +370,22 @@ class DeviceEnvBatch:
                 self.handle, self.lib)
         return out
 
+    def refill_values(self, weights, deals: int, seed: int, stream: Optional[torch.Tensor] = None, depth: int = 3,
+                      want=("value",), out: Optional[dict] = None) -> dict:
+        """bb_refill_values on the live boards and combos: ``deals`` next hands per env dealt by the reference
+        dealer's law and each searched (see ``runtime.kernels.refill_values``): a dict of [N, deals] tensors, "hand"
+        int32, "value" int64, "attempts" int32, those named in ``want`` or given in ``out``.  stream int64 [N] or
+        None (the env's index).  Reads the state and changes nothing, the piece stream included."""
+        from . import kernels as K
+
+        K._refill_column("stream", stream, torch.int64, self.num_envs, self.device)
+        out, o = K._refill_values_args(deals, depth, out, self.num_envs, self.device, want)
+        w = K._weights(weights)
+        L.check(self.lib.bb_refill_values(self.handle, _ptr(stream), C.byref(w), depth, deals,
+                                          int(seed) & (2 ** 64 - 1), C.byref(o), _stream(self.device)),
+                "bb_refill_values", self.handle, self.lib)
+        return out
+
     # ------------------------------------------------------------ host copies
     def state(self) -> dict:
         n = self.num_envs

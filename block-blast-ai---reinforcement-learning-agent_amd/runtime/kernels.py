@@ -466,6 +466,104 @@ def refill_hazard(count, attempts: int = 100) -> torch.Tensor:
     return torch.exp(attempts * log_q)
 
 
+# ---------------------------------------------------------------------------
+# Dealt next-hand values and a plan played to its leaf (csrc/bb_lookahead.hip; csrc/bb_host.cpp for CPU tensors)
+# ---------------------------------------------------------------------------
+REFILL_MAX_DEALS = L.BB_REFILL_MAX_DEALS
+REFILL_MAX_GRID = 1 << 14  # kRefillMaxGrid of csrc/bb_lookahead.hip: more (board, deal) pairs stride
+REFILL_VALUE_OUTPUTS = {"hand": torch.int32, "value": torch.int64, "attempts": torch.int32}
+
+
+def refill_value_outputs(n: int, deals: int, dev, want=("value",)) -> dict:
+    """Fresh [n, deals] output tensors for ``refill_values``: hand int32 (the bit pattern of the u32 hand word),
+    value int64, attempts int32."""
+    unknown = set(want) - set(REFILL_VALUE_OUTPUTS)
+    if unknown:
+        raise L.BBNativeError(f"refill_values: unknown outputs {sorted(unknown)}; they are {tuple(REFILL_VALUE_OUTPUTS)}")
+    return {k: torch.empty((n, deals), dtype=REFILL_VALUE_OUTPUTS[k], device=dev) for k in want}
+
+
+def _refill_values_args(deals, depth, out, n, dev, want=("value",)):
+    """The Python-side rules shared by ``refill_values`` and ``DeviceEnvBatch.refill_values``; returns (out dict,
+    struct), the dict freshly allocated from ``want`` when ``out`` is None."""
+    if not (isinstance(deals, int) and 1 <= deals <= REFILL_MAX_DEALS):
+        raise L.BBNativeError(f"refill_values: deals must be 1..{REFILL_MAX_DEALS}, not {deals!r}")
+    if not (isinstance(depth, int) and 1 <= depth <= 3):
+        raise L.BBNativeError(f"refill_values: depth must be 1..3, not {depth!r}")
+    out = refill_value_outputs(n, deals, dev, want) if out is None else out
+    table = {k: (k, dt, deals) for k, dt in REFILL_VALUE_OUTPUTS.items()}
+    return out, _look_out(L.RefillValuesOut, "refill_values", table, out, n, dev, at_least_one=True, known_only=True)
+
+
+def _refill_column(name: str, t, dt, n: int, dev):
+    if t is not None and not (isinstance(t, torch.Tensor) and t.dtype == dt and t.device == dev and t.is_contiguous()
+                              and t.dim() == 1 and t.numel() == n):
+        raise L.BBNativeError(f"refill_values: {name} must be a contiguous {dt} tensor of {n} elements on {dev}")
+    return t
+
+
+def refill_values(board: torch.Tensor, weights, deals: int, seed: int, combo: Optional[torch.Tensor] = None,
+                  stream: Optional[torch.Tensor] = None, depth: int = 3, want=("value",),
+                  out: Optional[dict] = None) -> dict:
+    """bb_refill_values_pos: for every board, ``deals`` next hands dealt by the reference dealer's law (up to 100
+    draws, the first solvable one kept; bbvec.h "dealt next-hand values") and each searched as ``plan_actions``
+    searches it, in one launch.  board int64 [n]; combo int32 [n] or None (0); stream int64 [n] or None (i): the
+    Philox counter of board i -- boards with the same stream id and seed meet the same draws.  Returns a dict of the
+    outputs named in ``want`` (or the tensors of ``out``, written in place), each [n, deals]: "hand" int32 the dealt
+    hand word, "value" int64 the best full-hand value of that hand on the board at combo[i] (``weights["dead"]``
+    for a hand with no legal first move), "attempts" int32 the draw that was accepted (1..100) or -100."""
+    if not (isinstance(board, torch.Tensor) and board.dtype == torch.int64 and board.dim() == 1
+            and board.is_contiguous()):
+        raise L.BBNativeError("refill_values: board must be a contiguous torch.int64 tensor of shape [n]")
+    n, dev = board.numel(), board.device
+    _refill_column("combo", combo, torch.int32, n, dev)
+    _refill_column("stream", stream, torch.int64, n, dev)
+    w = _weights(weights)
+    out, o = _refill_values_args(deals, depth, out, n, dev, want)
+    if n == 0:  # an empty tensor has no storage to point at; the entry point would do nothing either
+        return out
+    lib, s = _look_lib(dev)
+    L.check(lib.bb_refill_values_pos(_p(board), _p(combo), _p(stream), n, C.byref(w), depth, deals,
+                                     int(seed) & (2 ** 64 - 1), C.byref(o), s), "bb_refill_values_pos", lib=lib)
+    return out
+
+
+PLAY_PLAN_OUTPUTS = {"board": torch.int64, "hand": torch.int32, "combo": torch.int32, "lines": torch.int32,
+                     "score": torch.int64, "status": torch.int32}
+PLAY_PLIES, PLAY_DEAD, PLAY_REFILL, PLAY_ILLEGAL = L.BB_PLAY_PLIES, L.BB_PLAY_DEAD, L.BB_PLAY_REFILL, L.BB_PLAY_ILLEGAL
+
+
+def play_plan(board: torch.Tensor, hand: torch.Tensor, plan: torch.Tensor, combo: Optional[torch.Tensor] = None,
+              want=tuple(PLAY_PLAN_OUTPUTS), out: Optional[dict] = None) -> dict:
+    """bb_play_plan_pos: every position's plan (int32 [n, 3]: actions, negative = ply not played) played with the
+    one-ply move, in one launch.  Returns a dict of the [n] outputs named in ``want`` (or the tensors of ``out``,
+    written in place): "board" int64, "hand" int32 and "combo" int32 after the last ply played, "lines" int32 and
+    "score" int64 summed over the plies, "status" int32 = plies played | PLAY_DEAD | PLAY_REFILL (of the last
+    afterstate) | PLAY_ILLEGAL (a ply was illegal; play stopped before it).  n may be 0."""
+    n, dev = board.numel(), board.device
+    for t, dt, name in ((board, torch.int64, "board"), (hand, torch.int32, "hand"), (combo, torch.int32, "combo")):
+        if t is not None and not (t.dtype == dt and t.device == dev and t.is_contiguous() and t.numel() == n):
+            raise L.BBNativeError(f"play_plan: {name} must be a contiguous {dt} tensor of {n} elements on {dev}")
+    if not (isinstance(plan, torch.Tensor) and plan.dtype == torch.int32 and plan.device == dev
+            and plan.is_contiguous() and tuple(plan.shape) == (n, 3)):
+        raise L.BBNativeError(f"play_plan: plan must be a contiguous {torch.int32} [{n}, 3] tensor on {dev}")
+    if out is None:
+        unknown = set(want) - set(PLAY_PLAN_OUTPUTS)
+        if unknown:
+            raise L.BBNativeError(f"play_plan: unknown outputs {sorted(unknown)}; they are {tuple(PLAY_PLAN_OUTPUTS)}")
+        out = {k: torch.empty(n, dtype=PLAY_PLAN_OUTPUTS[k], device=dev) for k in want}
+    table = {k: (k, dt, 1) for k, dt in PLAY_PLAN_OUTPUTS.items()}
+    o = _look_out(L.PlayPlanOut, "play_plan", table, out, n, dev, shape="tensor of {numel} elements",
+                  at_least_one=True, known_only=True)
+    if n == 0:
+        return out
+    pos = L.Positions(board=board.data_ptr(), hand=hand.data_ptr(),
+                      combo=combo.data_ptr() if combo is not None else None, prev=None)
+    lib, s = _look_lib(dev)
+    L.check(lib.bb_play_plan_pos(C.byref(pos), n, _p(plan), C.byref(o), s), "bb_play_plan_pos", lib=lib)
+    return out
+
+
 def unpack_rest(rest):
     """(a2, a3) of bb_plan_values' rest words (torch or numpy), -1 for a ply not played or an illegal action."""
     a2, a3 = rest & 0xFF, (rest >> 8) & 0xFF

@@ -23,6 +23,8 @@ BB_OK = 0
 BB_ACTIONS = 192
 BB_NUM_PIECES = 37
 BB_NUM_HANDS = 50653  # 37^3 ordered hands
+BB_REFILL_MAX_DEALS = 1024
+BB_PLAY_PLIES, BB_PLAY_DEAD, BB_PLAY_REFILL, BB_PLAY_ILLEGAL = 3, 4, 8, 16  # bb_play_plan_out.status
 
 
 class BBNativeError(RuntimeError):
@@ -153,6 +155,17 @@ class CensusOut(C.Structure):
     _fields_ = [("count", C.c_void_p), ("solvable", C.c_void_p)]
 
 
+class RefillValuesOut(C.Structure):
+    """bb_refill_values_out: device arrays hand u32 / value i64 / attempts i32 [n][deals]; any may be NULL, not all."""
+    _fields_ = [("hand", C.c_void_p), ("value", C.c_void_p), ("attempts", C.c_void_p)]
+
+
+class PlayPlanOut(C.Structure):
+    """bb_play_plan_out: device arrays [n]; any may be NULL, not all six."""
+    _fields_ = [("board", C.c_void_p), ("hand", C.c_void_p), ("combo", C.c_void_p), ("lines", C.c_void_p),
+                ("score", C.c_void_p), ("status", C.c_void_p)]
+
+
 _P = C.c_void_p
 _I32 = C.c_int32
 _U64 = C.c_uint64
@@ -247,6 +260,10 @@ SIGNATURES = {
     "bb_safe_mask": (C.c_int, [_P, _I32, _P, _P]),
     "bb_refill_census_pos": (C.c_int, [_P, _I32, C.POINTER(CensusOut), _P]),
     "bb_refill_census": (C.c_int, [_P, C.POINTER(CensusOut), _P]),
+    "bb_refill_values_pos": (C.c_int, [_P, _P, _P, _I32, C.POINTER(GreedyWeights), _I32, _I32, _U64,
+                                       C.POINTER(RefillValuesOut), _P]),
+    "bb_refill_values": (C.c_int, [_P, _P, C.POINTER(GreedyWeights), _I32, _I32, _U64, C.POINTER(RefillValuesOut), _P]),
+    "bb_play_plan_pos": (C.c_int, [C.POINTER(Positions), _I32, _P, C.POINTER(PlayPlanOut), _P]),
     "bb_masked_sample": (C.c_int, [_P, _P, _I32, _P, _U64, _U64, _U64, _I32, _P, _P, _P, _P, _P]),
     "bb_masked_sample_dstep": (C.c_int, [_P, _P, _I32, _U64, _P, _U64, _U64, _I32, _P, _P, _P, _P]),
     "bb_gae": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _F, _F, _P, _P, _P]),
@@ -312,7 +329,8 @@ HOST_SYMBOLS = ("bb_abi_version", "bb_build_id", "bb_create", "bb_destroy", "bb_
                 "bb_greedy_actions_each_pos", "bb_greedy_actions_each", "bb_plan_actions_each_pos",
                 "bb_plan_actions_each",
                 "bb_plan_values_pos", "bb_plan_values", "bb_safe_mask_pos", "bb_safe_mask",
-                "bb_refill_census_pos", "bb_refill_census")
+                "bb_refill_census_pos", "bb_refill_census", "bb_refill_values_pos", "bb_refill_values",
+                "bb_play_plan_pos")
 
 _lib = None
 _host = None

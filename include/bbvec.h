@@ -64,7 +64,10 @@ extern "C" {
                                  (additive, still 9) bb_greedy_actions_each(_pos) and bb_plan_actions_each(_pos): one
                                  row of weights per position, read from the memory of the position columns;
                                  (additive, still 9) bb_census_out with bb_refill_census(_pos): the exact count of
-                                 the 37^3 hands a board can still be dealt (engine.py:155-224) */
+                                 the 37^3 hands a board can still be dealt (engine.py:155-224);
+                                 (additive, still 9) bb_refill_values_out with bb_refill_values(_pos): next hands
+                                 dealt by the dealer's law (engine.py:155-172) and searched, per board; bb_play_plan_out
+                                 with bb_play_plan_pos: a plan played to its leaf position */
 
 #define BB_OK 0
 #define BB_ERR_ARG (-1)
@@ -516,6 +519,84 @@ typedef struct bb_census_out {
 int bb_refill_census_pos(const uint64_t* d_board, int32_t n, const bb_census_out* out, void* stream);
 /* replaces engine.py:155-224 for the handle's live boards ([N] / [N][37][37] outputs) */
 int bb_refill_census(bb_env* env, const bb_census_out* out, void* stream);
+
+/* ---- dealt next-hand values (the chance node behind a refill) ----------------------
+ * Replaces engine.py:155-172 (_generate_valid_pieces: up to 100 uniform draws of three
+ * pieces, the first hand that _can_place_all_pieces accepts, else the 100th) for a
+ * board that is not a live env, with a counter-based generator in place of the env's
+ * PCG64 stream, and searches every dealt hand.  Integers only.  For board i and deal
+ * j < deals, draw t = 0..99 takes the four Philox4x32-10 words of counter
+ *   (idx, step) = (d_stream ? d_stream[i] : i, (uint64)j << 7 | t)  under key `seed`
+ * (bb_random_actions' generator: c0,c1 = idx lo,hi; c2,c3 = step lo,hi; k0,k1 = seed
+ * lo,hi) and makes the piece ids (word_k * 37) >> 32 for k = 0, 1, 2; word 3 is not
+ * used.  Bias: 2^32 = 37 * 116,080,197 + 7, so seven of the 37 ids have 116,080,198
+ * words each and thirty have 116,080,197 -- a relative excess of 8.6e-9, against the
+ * reference's exactly uniform Lemire draw.  The first draw whose hand is solvable on
+ * the board (the predicate of bb_refill_census: some order and anchors place all
+ * three, with the line clears in between) is kept; after 100 refusals the 100th is.
+ * Two boards given the same stream id and seed meet the same draws (common random
+ * numbers) and differ only where their acceptance differs.
+ *   hand     [n][deals] the dealt hand word a | b << 6 | c << 12: nothing used, not
+ *                       over, has_uint32 0
+ *   value    [n][deals] what bb_plan_actions_pos returns as `value` for the position
+ *                       (board i, that hand, combo[i]) under w and depth; a hand
+ *                       without a legal first move (INT64_MIN there) gets (int64)w.dead
+ *   attempts [n][deals] k in 1..100: the k-th draw was accepted; -100: all refused
+ * d_combo NULL reads as 0.  depth is 1..3, deals 1..BB_REFILL_MAX_DEALS; n == 0 does
+ * nothing.  BB_ERR_ARG (the rule named in bb_last_error, before any HIP call) for a
+ * NULL board, n < 0, a NULL w, a NULL out, all three outputs NULL, depth outside 1..3
+ * and deals outside 1..1024.  The handle form reads the live board and combo columns
+ * and changes nothing, the RNG included, and refuses a handle in BB_ERR_DEVICE /
+ * BB_ERR_STATE.  Asynchronous on `stream`, no allocation, no sync (graph-capturable
+ * from the first call); indexing is 64-bit. */
+#define BB_REFILL_MAX_DEALS 1024
+typedef struct bb_refill_values_out {
+  uint32_t* hand;      /* [n][m] the dealt hand word: ids a | b<<6 | c<<12, nothing used, not over, has_uint32 0 */
+  int64_t*  value;     /* [n][m] best full-hand value of that hand on the board (above)                          */
+  int32_t*  attempts;  /* [n][m] k in 1..100: the k-th draw was accepted; -100: all refused, the 100th is kept    */
+} bb_refill_values_out;  /* device pointers (host pointers for libbbvec_host.so); any may be NULL, not all three */
+/* replaces engine.py:155-172 for boards given as columns, and searches the hands */
+int bb_refill_values_pos(const uint64_t* d_board, const int32_t* d_combo /* NULL = 0 */,
+                         const uint64_t* d_stream /* NULL = i */, int32_t n, const bb_greedy_weights* w,
+                         int32_t depth, int32_t deals /* m */, uint64_t seed,
+                         const bb_refill_values_out* out, void* stream);
+/* the same for the handle's live boards and combos ([N][m] outputs) */
+int bb_refill_values(bb_env* env, const uint64_t* d_stream, const bb_greedy_weights* w, int32_t depth,
+                     int32_t deals, uint64_t seed, const bb_refill_values_out* out, void* stream);
+
+/* ---- a plan played to its leaf ------------------------------------------------------
+ * Plays d_plan[i][0..2] from position i with the one-ply move of bb_afterstates
+ * (engine.py:326-346 legality, 390-431 place / clear / combo / score).  A plan entry
+ * is an action 0..191, or negative for a ply not played (as bb_plan_out.plan and the
+ * decoded rest of bb_plan_values give them): play ends at the first negative entry.
+ * An entry that is not a legal action of the position reached (>= 192 included) sets
+ * status bit 4 and play stops before it; the outputs describe the state reached.
+ *   board, hand, combo [n]  after the last ply played (hand: the slots played marked
+ *                           used, the other bits as they came); the inputs when none
+ *   lines  [n]  lines cleared, summed over the plies played
+ *   score  [n]  score_gained, summed over the plies played (combo carried)
+ *   status [n]  bits 0-1 plies played (0..3) | bit 2 the last afterstate is dead (no
+ *               unused slot fits, not a refill) | bit 3 it is a refill (all three slots
+ *               used) | bit 4 a ply was illegal
+ * pos->combo NULL reads as 0; pos->prev is not read.  Any output may be NULL, not all
+ * six; n == 0 does nothing.  BB_ERR_ARG (the rule named in bb_last_error, before any
+ * HIP call) for NULL positions, n < 0, a NULL d_plan, a NULL out and all outputs NULL.
+ * Asynchronous on `stream`, no allocation, no sync (graph-capturable from the first
+ * call); indexing is 64-bit. */
+#define BB_PLAY_PLIES 3u     /* status & BB_PLAY_PLIES: plies played */
+#define BB_PLAY_DEAD 4u
+#define BB_PLAY_REFILL 8u
+#define BB_PLAY_ILLEGAL 16u
+typedef struct bb_play_plan_out {
+  uint64_t* board;   /* [n] */
+  uint32_t* hand;    /* [n] */
+  int32_t*  combo;   /* [n] */
+  int32_t*  lines;   /* [n] */
+  int64_t*  score;   /* [n] */
+  int32_t*  status;  /* [n] */
+} bb_play_plan_out;  /* device pointers (host pointers for libbbvec_host.so); any may be NULL, not all six */
+int bb_play_plan_pos(const bb_positions* pos, int32_t n, const int32_t* d_plan /* [n][3] */,
+                     const bb_play_plan_out* out, void* stream);
 
 /* Fused masked-categorical tail of BlockBlastNetwork.get_action_and_value
  * (network.py:173-180, 210-262; Categorical clamp semantics of torch 2.10):
