@@ -9,7 +9,9 @@ Philox random-legal policy ``bb_random_actions``.  ``HandPlanAgent`` searches ev
 ``TwoHandPlanAgent`` looks past the refill that search stops at: below its best first moves it deals next hands by the
 dealer's law and searches them (``bb_play_plan_pos``, ``bb_refill_values``; ``evaluate.py --agent plan2``).
 ``PopulationPlanAgent`` is that search with weights of its own for every env (``bb_plan_actions_each``), which
-``evaluation/tune.py`` tunes the weights with.  ``device="cpu"`` runs them on the host backend.
+``evaluation/tune.py`` tunes the weights with.  ``HandPlanAgent`` and ``PopulationPlanAgent`` also take the four shape
+weights of ``L.TERM_FIELDS`` (perimeter, room3, room5, fits) and then search with ``bb_plan_actions_ext``.
+``device="cpu"`` runs them on the host backend.
 """
 from __future__ import annotations
 
@@ -65,8 +67,17 @@ class GreedyAgent(BaseAgent):
         super().__init__(resolve_device(device))
         self.weights = dict(DEFAULT_WEIGHTS)
         if weights:
-            L.greedy_weights(weights)  # rejects unknown names
+            self._check_weights(weights)  # rejects unknown names
             self.weights.update({k: int(v) for k, v in weights.items()})
+
+    def _check_weights(self, weights: Dict[str, int]) -> None:
+        """Rejects names this agent's kernels have no term for.  The shape terms of ``L.TERM_FIELDS`` exist only in
+        the full-hand search (``bb_plan_actions_ext``), which ``HandPlanAgent`` plays through."""
+        shape = sorted(set(weights) & set(L.TERM_FIELDS))
+        if shape:
+            raise ValueError(f"{type(self).__name__} has no extended kernel yet: the shape weights {shape} are "
+                             f"searched by HandPlanAgent and PopulationPlanAgent only")
+        L.greedy_weights(weights)
 
     def act_env(self, env_batch, out: torch.Tensor) -> torch.Tensor:
         """The action of every env of a ``DeviceEnvBatch`` into out (int32 [N]), in one fused launch."""
@@ -93,7 +104,7 @@ class GreedyAgent(BaseAgent):
     def load(self, path: str) -> None:
         with open(path) as f:
             data = json.load(f)
-        L.greedy_weights(data["weights"])
+        self._check_weights(data["weights"])
         self.weights = dict(DEFAULT_WEIGHTS)
         self.weights.update({k: int(v) for k, v in data["weights"].items()})
 
@@ -102,16 +113,41 @@ class HandPlanAgent(GreedyAgent):
     """Plays the first move of the best way to play out the whole hand: the exhaustive search of
     ``bb_plan_actions`` over every order and placement of the unused pieces, up to ``depth`` (1..3) moves, under
     the same integer weights (move terms summed along the sequence, state terms of its last afterstate; ties:
-    the lexicographically lowest sequence).  ``depth=1`` is ``GreedyAgent``.  One fused launch per move."""
+    the lexicographically lowest sequence).  ``depth=1`` is ``GreedyAgent``.  One fused launch per move.
+
+    The weights may also name the shape terms of ``L.TERM_FIELDS`` (perimeter, room3, room5, fits of the last
+    afterstate's board).  When one of them is not 0 the agent searches with ``bb_plan_actions_ext``; otherwise it
+    plays through ``bb_plan_actions`` as it always did."""
 
     def __init__(self, weights: Optional[Dict[str, int]] = None, depth: int = 3, device=None):
         super().__init__(weights, device)
         if int(depth) not in (1, 2, 3):
             raise ValueError(f"depth must be 1, 2 or 3, not {depth}")
         self.depth = int(depth)
+        self._rows = None  # the [1, 12] row of plan_actions_ext, made on first use where the positions are
+
+    def _check_weights(self, weights: Dict[str, int]) -> None:
+        L.eval_weights(weights)
+
+    def _ext_rows(self, dev) -> Optional[torch.Tensor]:
+        """The agent's weights as one shared row of ``plan_actions_ext`` on dev; None when no shape weight is set."""
+        if not any(int(self.weights.get(k, 0)) != 0 for k in L.TERM_FIELDS):
+            return None
+        from runtime import kernels as K
+
+        want = [int(self.weights.get(k, 0)) for k in L.EVAL_FIELDS]
+        if self._rows is None or self._rows[0] != want or self._rows[1].device != dev:
+            self._rows = (want, K.eval_rows(self.weights, device=dev))
+        return self._rows[1]
+
+    def _base_weights(self) -> Dict[str, int]:
+        return {k: v for k, v in self.weights.items() if k in L.GREEDY_FIELDS}
 
     def act_env(self, env_batch, out: torch.Tensor) -> torch.Tensor:
-        return env_batch.plan_actions(out, self.weights, self.depth)
+        rows = self._ext_rows(env_batch.device)
+        if rows is not None:
+            return env_batch.plan_actions_ext(out, rows, self.depth)
+        return env_batch.plan_actions(out, self._base_weights(), self.depth)
 
     def select_action(self, observation: Dict[str, Any], deterministic: bool = True) -> Tuple[int, Dict[str, Any]]:
         """From a Gym observation (no combo count in it: see ``GreedyAgent.select_action``)."""
@@ -120,7 +156,11 @@ class HandPlanAgent(GreedyAgent):
         bits, hand = _position_of(observation)
         board = torch.tensor([bits - (1 << 64) if bits >= 1 << 63 else bits], dtype=torch.int64, device=self.device)
         hand_t = torch.tensor([hand], dtype=torch.int32, device=self.device)
-        res = K.plan_actions(board, hand_t, self.weights, self.depth, want_plan=True)
+        rows = self._ext_rows(self.device)
+        if rows is not None:
+            res = K.plan_actions_ext(board, hand_t, rows, self.depth, want_plan=True)
+        else:
+            res = K.plan_actions(board, hand_t, self._base_weights(), self.depth, want_plan=True)
         return int(res["action"].cpu().item()), {"value": int(res["value"].cpu().item()),
                                                  "plan": res["plan"].cpu().view(3).tolist()}
 
@@ -163,6 +203,9 @@ class TwoHandPlanAgent(HandPlanAgent):
             raise ValueError(f"deals must be 1..{L.BB_REFILL_MAX_DEALS}, not {deals}")
         self.candidates, self.deals, self.seed = int(candidates), int(deals), int(seed)
         self.moves = 0  # decisions made so far: mixed into the deals' seed
+
+    def _check_weights(self, weights: Dict[str, int]) -> None:
+        GreedyAgent._check_weights(self, weights)  # plan_values / refill_values have no extended form
 
     @staticmethod
     def deal_seed(seed: int, move: int) -> int:
@@ -241,7 +284,9 @@ class TwoHandPlanAgent(HandPlanAgent):
 class PopulationPlanAgent(BaseAgent):
     """One ``HandPlanAgent`` per env, each with weights of its own, all searched in one launch per move
     (``bb_plan_actions_each``).  ``rows``: int32 [N, 8], env i's weights in the order of ``L.GREEDY_FIELDS``
-    (``runtime.kernels.weight_rows`` makes them from dicts); they are moved to the agent's device.  ``depth`` 1..3
+    (``runtime.kernels.weight_rows`` makes them from dicts), or int32 [N, 12] in the order of ``L.EVAL_FIELDS``
+    (``eval_rows``), which are searched with the shape terms by ``bb_plan_actions_ext`` at depth 1..3; they are moved
+    to the agent's device.  ``depth`` 1..3
     is the search depth; ``depth=0`` asks for the one-ply greedy kernel (``bb_greedy_actions_each``), which chooses
     what depth 1 chooses.  Only ``act_env`` is offered: the agent is tied to a ``DeviceEnvBatch`` of N envs
     (``evaluation/tune.py`` plays a population of candidate weights with it)."""
@@ -254,8 +299,13 @@ class PopulationPlanAgent(BaseAgent):
             raise ValueError(f"depth must be 0 (the one-ply greedy kernel), 1, 2 or 3, not {depth}")
         self.depth = int(depth)
         self.rows = rows.to(self.device).contiguous()
+        self.ext = self.rows.dim() == 2 and self.rows.shape[1] == len(L.EVAL_FIELDS)
+        if self.ext and self.depth == 0:
+            raise ValueError("rows of twelve weights need depth 1..3: the one-ply greedy kernel has no extended form")
 
     def act_env(self, env_batch, out: torch.Tensor) -> torch.Tensor:
+        if self.ext:
+            return env_batch.plan_actions_ext(out, self.rows, self.depth)
         if self.depth == 0:
             return env_batch.greedy_actions_each(out, self.rows)
         return env_batch.plan_actions_each(out, self.rows, self.depth)

@@ -674,6 +674,36 @@ int bb_plan_actions_each(bb_env* env, const bb_greedy_weights* d_w, int32_t dept
   });
 }
 
+// The shape terms (board_terms_kernel) and the search with them (plan_ext_kernel): d_w is device memory
+int bb_board_terms_pos(const uint64_t* d_board, int32_t n, int32_t* d_terms, void* stream) {
+  const char* rule = bb_look_rules::board_terms_pos(d_board, n, d_terms);
+  if (!rule && n == 0) return BB_OK;  // accepted, and nothing to do
+  return look_pos_call("bb_board_terms_pos", rule,
+                       [&] { return launch_board_terms(d_board, n, d_terms, (hipStream_t)stream); });
+}
+
+int bb_board_terms(bb_env* env, int32_t* d_terms, void* stream) {
+  return look_env_call(env, "bb_board_terms", bb_look_rules::board_terms(d_terms),
+                       [&] { return launch_board_terms(env->d.board, env->n, d_terms, (hipStream_t)stream); });
+}
+
+int bb_plan_actions_ext_pos(const bb_positions* pos, int32_t n, const bb_eval_weights* d_w, int64_t w_stride,
+                            int32_t depth, const bb_plan_out* out, void* stream) {
+  const char* rule = bb_look_rules::plan_actions_ext_pos(pos, n, d_w, w_stride, depth, out);
+  if (!rule && n == 0) return BB_OK;  // accepted, and nothing to do
+  return look_pos_call("bb_plan_actions_ext_pos", rule, [&] {
+    return launch_plan_ext(pos->board, pos->hand, pos->combo, n, d_w, w_stride, depth, *out, (hipStream_t)stream);
+  });
+}
+
+int bb_plan_actions_ext(bb_env* env, const bb_eval_weights* d_w, int64_t w_stride, int32_t depth,
+                        const bb_plan_out* out, void* stream) {
+  return look_env_call(env, "bb_plan_actions_ext", bb_look_rules::plan_actions_ext(d_w, w_stride, depth, out), [&] {
+    return launch_plan_ext(env->d.board, env->d.hand, env->d.combo, env->n, d_w, w_stride, depth, *out,
+                           (hipStream_t)stream);
+  });
+}
+
 // Per-action full-hand values (plan_values_kernel)
 int bb_plan_values_pos(const bb_positions* pos, int32_t n, const bb_greedy_weights* w, int32_t depth,
                        const bb_plan_values_out* out, void* stream) {

@@ -105,6 +105,12 @@ hipError_t launch_greedy_each(const uint64_t* board, const uint32_t* hand, const
                               const bb_greedy_weights* rows, int32_t* action, int64_t* value, hipStream_t s);
 hipError_t launch_plan_each(const uint64_t* board, const uint32_t* hand, const int32_t* combo, int n,
                             const bb_greedy_weights* rows, int depth, const bb_plan_out& out, hipStream_t s);
+// launch_plan_each under bb_eval_weights (bb_lookahead.hip): position i takes rows[i * w_stride], w_stride 0 or 1, n > 0
+hipError_t launch_plan_ext(const uint64_t* board, const uint32_t* hand, const int32_t* combo, int n,
+                           const bb_eval_weights* rows, int64_t w_stride, int depth, const bb_plan_out& out,
+                           hipStream_t s);
+// the shape terms of a board column (bb_lookahead.hip): n > 0, terms [n][4]
+hipError_t launch_board_terms(const uint64_t* board, int n, int32_t* terms, hipStream_t s);
 // full-hand lookahead (bb_lookahead.hip): depth 1..3, out.action required
 hipError_t launch_plan(const uint64_t* board, const uint32_t* hand, const int32_t* combo, int n,
                        const bb_greedy_weights& w, int depth, const bb_plan_out& out, hipStream_t s);

@@ -397,8 +397,9 @@ struct PlanBest {
   bool alive;  // a maximal sequence ended in an afterstate that is not dead (bb_plan_values' safe)
 };
 
-void plan_dfs(uint64_t B, uint32_t hand, int combo, int depth, int ply, int64_t sum, int32_t* seq,
-              const bb_greedy_weights& w, PlanBest& best) {
+template <class W>  // bb_greedy_weights, or bb_eval_weights (plan_ext_host): move_terms / state_terms of bb_rules.h
+void plan_dfs(uint64_t B, uint32_t hand, int combo, int depth, int ply, int64_t sum, int32_t* seq, const W& w,
+              PlanBest& best) {
   if (hand_over(hand)) return;  // game over: nothing is legal
   for (int p = 0; p < 3; ++p) {
     const uint32_t id = hand_id(hand, p);
@@ -436,6 +437,30 @@ void plan_host(const uint64_t* board, const uint32_t* hand, const int32_t* combo
       for (int k = 0; k < 3; ++k) out.plan[3 * (size_t)i + k] = best.plan[k];
     if (out.leaves) out.leaves[i] = best.leaves;
   }
+}
+
+// bbvec.h bb_plan_actions_ext (the host twin of plan_ext_kernel): the same DFS under a twelve-int row, whose state
+// terms add the shape terms of the leaf's board; position i takes rows[i * w_stride], w_stride 0 or 1
+void plan_ext_host(const uint64_t* board, const uint32_t* hand, const int32_t* combo, int32_t n,
+                   const bb_eval_weights* rows, int64_t w_stride, int depth, const bb_plan_out& out) {
+#pragma omp parallel for schedule(dynamic, 1)
+  for (int32_t i = 0; i < n; ++i) {
+    const bb_eval_weights w = rows[(int64_t)i * w_stride];
+    PlanBest best{INT64_MIN, {-1, -1, -1}, 0, false};
+    int32_t seq[3];
+    plan_dfs(board[i], hand[i], combo ? combo[i] : 0, depth, 0, 0, seq, w, best);
+    out.action[i] = best.leaves ? best.plan[0] : 0;
+    if (out.value) out.value[i] = best.value;
+    if (out.plan)
+      for (int k = 0; k < 3; ++k) out.plan[3 * (size_t)i + k] = best.plan[k];
+    if (out.leaves) out.leaves[i] = best.leaves;
+  }
+}
+
+// bbvec.h bb_board_terms: board_terms of bb_rules.h for every board
+void board_terms_host(const uint64_t* board, int32_t n, int32_t* terms) {
+#pragma omp parallel for schedule(static)
+  for (int32_t i = 0; i < n; ++i) bb::board_terms(board[i], &terms[4 * (size_t)i]);
 }
 
 // bbvec.h bb_plan_values (the host twin of plan_values_kernel): the same DFS, started below each first move
@@ -975,6 +1000,41 @@ int bb_plan_actions_each(bb_env* env, const bb_greedy_weights* d_w, int32_t dept
   if (!env) return BB_ERR_ARG;
   if (int rc = refused(env, "bb_plan_actions_each", R::plan_actions_each(d_w, depth, out))) return rc;
   plan_host(env->board.data(), env->hand.data(), env->combo.data(), env->n, d_w, true, depth, *out);
+  return BB_OK;
+}
+
+// The shape terms and the search with them: d_w is host memory here
+
+int bb_board_terms_pos(const uint64_t* d_board, int32_t n, int32_t* d_terms, void* stream) {
+  (void)stream;
+  if (int rc = refused(nullptr, "bb_board_terms_pos", R::board_terms_pos(d_board, n, d_terms))) return rc;
+  board_terms_host(d_board, n, d_terms);
+  return BB_OK;
+}
+
+int bb_board_terms(bb_env* env, int32_t* d_terms, void* stream) {
+  (void)stream;
+  if (!env) return BB_ERR_ARG;
+  if (int rc = refused(env, "bb_board_terms", R::board_terms(d_terms))) return rc;
+  board_terms_host(env->board.data(), env->n, d_terms);
+  return BB_OK;
+}
+
+int bb_plan_actions_ext_pos(const bb_positions* pos, int32_t n, const bb_eval_weights* d_w, int64_t w_stride,
+                            int32_t depth, const bb_plan_out* out, void* stream) {
+  (void)stream;
+  if (int rc = refused(nullptr, "bb_plan_actions_ext_pos", R::plan_actions_ext_pos(pos, n, d_w, w_stride, depth, out)))
+    return rc;
+  plan_ext_host(pos->board, pos->hand, pos->combo, n, d_w, w_stride, depth, *out);
+  return BB_OK;
+}
+
+int bb_plan_actions_ext(bb_env* env, const bb_eval_weights* d_w, int64_t w_stride, int32_t depth,
+                        const bb_plan_out* out, void* stream) {
+  (void)stream;
+  if (!env) return BB_ERR_ARG;
+  if (int rc = refused(env, "bb_plan_actions_ext", R::plan_actions_ext(d_w, w_stride, depth, out))) return rc;
+  plan_ext_host(env->board.data(), env->hand.data(), env->combo.data(), env->n, d_w, w_stride, depth, *out);
   return BB_OK;
 }
 

@@ -1,4 +1,4 @@
-// bb_look_rules.h -- the argument rules of the nineteen lookahead entry points of include/bbvec.h, one copy for
+// bb_look_rules.h -- the argument rules of the twenty-three lookahead entry points of include/bbvec.h, one copy for
 // both backends (csrc/bb_capi.cpp and csrc/bb_host.cpp).  Plain C++, nothing from HIP.
 //
 // Each function returns the rule an argument set breaks, as the text that follows "<entry point>: " in
@@ -8,7 +8,7 @@
 // Asymmetries that are part of the ABI as it stands: bb_afterstates_pos, bb_greedy_actions(_each)_pos and
 // bb_plan_actions(_each)_pos refuse n == 0 and answer every broken rule with one text; bb_plan_values_pos accepts n == 0
 // (and does nothing) and names the rule that broke, and so do bb_safe_mask_pos, bb_refill_census_pos,
-// bb_refill_values_pos and bb_play_plan_pos.
+// bb_refill_values_pos, bb_play_plan_pos, bb_board_terms_pos and bb_plan_actions_ext_pos.
 #pragma once
 #include <stdint.h>
 
@@ -130,6 +130,31 @@ inline const char* play_plan_pos(const bb_positions* pos, int32_t n, const int32
   if (!out->board && !out->hand && !out->combo && !out->lines && !out->score && !out->status)
     return "all six outputs are NULL";
   return nullptr;
+}
+
+// the shape terms of a board column: as the refill census, n == 0 is accepted
+inline const char* board_terms(const int32_t* d_terms) { return d_terms ? nullptr : "d_terms is NULL"; }
+inline const char* board_terms_pos(const uint64_t* board, int32_t n, const int32_t* d_terms) {
+  if (!board) return "board is NULL";
+  if (n < 0) return "n is negative";
+  return board_terms(d_terms);
+}
+
+// the search with the shape terms: rows of bb_eval_weights, shared (w_stride 0) or one per position (1)
+inline const char* plan_actions_ext(const bb_eval_weights* d_w, int64_t w_stride, int32_t depth,
+                                    const bb_plan_out* out) {
+  if (!d_w) return "weight rows are NULL";
+  if (w_stride != 0 && w_stride != 1) return "w_stride must be 0 or 1";
+  if (bad_depth(depth)) return "depth must be 1..3";
+  if (!out) return "out is NULL";
+  if (!out->action) return "out->action is NULL";
+  return nullptr;
+}
+inline const char* plan_actions_ext_pos(const bb_positions* pos, int32_t n, const bb_eval_weights* d_w,
+                                        int64_t w_stride, int32_t depth, const bb_plan_out* out) {
+  if (no_positions(pos)) return "positions (board, hand) are NULL";
+  if (n < 0) return "n is negative";
+  return plan_actions_ext(d_w, w_stride, depth, out);
 }
 
 }  // namespace bb_look_rules

@@ -266,8 +266,9 @@ __device__ __forceinline__ Ply1 plan_ply1(const LookTable& t, const Position& P,
 // prefix popcount).  Returns total <= kPlanRecords; both barriers have passed.  The kernels call this after the
 // lanes that are not open have used their afterstate (scored themselves, filled their staging entry): from here
 // on only an open lane's board, move terms and combo' are needed, so nothing else of it is live across the barriers.
-__device__ __forceinline__ int plan_compact(PlanRecord* s_rec, int* s_cnt, const bb_greedy_weights& w,
-                                            const Ply1& p1, int wave, int cell) {
+template <class W>  // bb_greedy_weights, or bb_eval_weights (plan_ext_kernel): move_terms / state_terms of bb_rules.h
+__device__ __forceinline__ int plan_compact(PlanRecord* s_rec, int* s_cnt, const W& w, const Ply1& p1, int wave,
+                                            int cell) {
   const uint64_t open_mask = __ballot(p1.open);
   if (wave < kHand && cell == 0) s_cnt[wave] = __popcll(open_mask);
   __syncthreads();
@@ -288,9 +289,9 @@ __device__ __forceinline__ int plan_compact(PlanRecord* s_rec, int* s_cnt, const
 // goes into the lane's (best, best_key, leaves).  kPerFirstMove = false (plan_kernel): the key carries a1,
 // key = a1 << 16 | a2 << 8 | a3, and `alive` is not touched.  true (plan_values_kernel): key = a2 << 8 | a3, and
 // `alive` is set by a leaf that is not dead.  Returns a1, the record's action (< 192).
-template <bool kPerFirstMove>
+template <bool kPerFirstMove, class W>
 __device__ __forceinline__ int plan_record_turn(const LookTable& t, const PlanRecord& rec, uint32_t hand,
-                                                const bb_greedy_weights& w, int depth, int cell, int64_t& best,
+                                                const W& w, int depth, int cell, int64_t& best,
                                                 uint32_t& best_key, int& leaves, bool& alive) {
   const uint64_t B1 = uniform64(rec.board);
   const int64_t sum1 = (int64_t)uniform64((uint64_t)rec.sum);
@@ -456,6 +457,124 @@ plan_each_kernel(LookTable t, LookPos pos, int n, const bb_greedy_weights* __res
     }
     // no barrier here, as in plan_kernel: thread 0 reads only s_v / s_key / s_leaves, which the next position
     // writes after two more barriers; its row is in this wave's own registers
+  }
+}
+
+// ---------------------------------------------------------------------------
+// The search with the shape terms (bbvec.h bb_plan_actions_ext): plan_each_kernel under bb_eval_weights.  The same
+// search body -- plan_compact and plan_record_turn instantiated for the twelve-int row, whose state_terms adds
+// shape_terms of the leaf's board (bb_rules.h) -- the same LDS, barriers and join.  The row of position i is
+// rows[i * w_stride], w_stride 0 (one row for all) or 1; it is read inside the position loop into scalar registers,
+// so the tests "is this term's weight 0" are scalar branches, the same for the whole workgroup, and a term that is
+// switched off costs a position nothing else.  fits is the dear one: a leaf on whose board the 3x3 square fits
+// pays four bar tests, any other leaf 36 anchor boards of two to three ands each.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ bb_eval_weights load_eval_weights(const bb_eval_weights* __restrict__ rows, int64_t i) {
+  const int32_t* r = reinterpret_cast<const int32_t*>(rows + i);
+  bb_eval_weights w;
+  w.base.lines = (int32_t)uniform32((uint32_t)r[0]);
+  w.base.score = (int32_t)uniform32((uint32_t)r[1]);
+  w.base.holes = (int32_t)uniform32((uint32_t)r[2]);
+  w.base.filled = (int32_t)uniform32((uint32_t)r[3]);
+  w.base.centre = (int32_t)uniform32((uint32_t)r[4]);
+  w.base.mobility = (int32_t)uniform32((uint32_t)r[5]);
+  w.base.dead = (int32_t)uniform32((uint32_t)r[6]);
+  w.base.refill = (int32_t)uniform32((uint32_t)r[7]);
+  w.perimeter = (int32_t)uniform32((uint32_t)r[8]);
+  w.room3 = (int32_t)uniform32((uint32_t)r[9]);
+  w.room5 = (int32_t)uniform32((uint32_t)r[10]);
+  w.fits = (int32_t)uniform32((uint32_t)r[11]);
+  return w;
+}
+
+// plan_kernel's search of one position up to the wave join, under either weight type (plan_ext_kernel's two sides)
+template <class W>
+__device__ __forceinline__ void plan_search(const LookTable& t, const Position& P, const W& w, int depth, int wave,
+                                            int cell, PlanRecord* s_rec, int* s_cnt, int64_t& best,
+                                            uint32_t& best_key, int& leaves) {
+  bool unused = false;  // `alive` is plan_values_kernel's
+  const Ply1 ply1 = plan_ply1(t, P, depth, wave, cell);
+  if (ply1.closed) {
+    best = move_terms(w, ply1.a) + state_terms(w, ply1.a);
+    best_key = ((uint32_t)(wave * 64 + cell) << 16) | 0xFFFFu;
+    leaves = 1;
+  }
+  const int total = plan_compact(s_rec, s_cnt, w, ply1, wave, cell);
+  for (int r = wave; r < total; r += kPlanWaves)
+    plan_record_turn<false>(t, s_rec[r], P.hand, w, depth, cell, best, best_key, leaves, unused);
+}
+
+__global__ void __launch_bounds__(kPlanBlock)
+plan_ext_kernel(LookTable t, LookPos pos, int n, const bb_eval_weights* __restrict__ rows, int64_t w_stride,
+                int depth, bb_plan_out out) {
+  __shared__ PlanRecord s_rec[kPlanRecords];
+  __shared__ int s_cnt[kHand];
+  __shared__ int64_t s_v[kPlanWaves];
+  __shared__ uint32_t s_key[kPlanWaves];
+  __shared__ int s_leaves[kPlanWaves];
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int cell = (int)(threadIdx.x & 63u);
+  for (int64_t i = blockIdx.x; i < (int64_t)n; i += gridDim.x) {
+    const Position P = load_position(pos, i);
+    const bb_eval_weights w = load_eval_weights(rows, i * w_stride);
+    const bool shaped = (w.perimeter | w.room3 | w.room5 | w.fits) != 0;  // scalar: one answer for the workgroup
+    int64_t best = INT64_MIN;
+    uint32_t best_key = kPlanNoKey;
+    int leaves = 0;
+
+    // a row with the four shape weights 0 takes plan_each_kernel's search, the eight-weight instantiation: the shape
+    // code, skipped branch by branch, still lengthened the twelve-weight leaf loop ("Shape terms").
+    // The barriers inside are met by the whole workgroup on either side: every wave read the same row.
+    if (shaped)
+      plan_search(t, P, w, depth, wave, cell, s_rec, s_cnt, best, best_key, leaves);
+    else
+      plan_search(t, P, w.base, depth, wave, cell, s_rec, s_cnt, best, best_key, leaves);
+
+    plan_wave_join(best, best_key, leaves);
+    if (cell == 0) {
+      s_v[wave] = best;
+      s_key[wave] = best_key;
+      s_leaves[wave] = leaves;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+      for (int k = 1; k < kPlanWaves; ++k) {
+        take_plan(best, best_key, s_v[k], s_key[k]);
+        leaves += s_leaves[k];
+      }
+      const bool found = best_key != kPlanNoKey;
+      const int p1 = (int)(best_key >> 16), p2 = (int)((best_key >> 8) & 0xFFu), p3 = (int)(best_key & 0xFFu);
+      out.action[i] = found ? p1 : 0;
+      if (out.value) out.value[i] = best;
+      if (out.plan) {
+        out.plan[i * 3 + 0] = found ? p1 : -1;
+        out.plan[i * 3 + 1] = found && p2 != 0xFF ? p2 : -1;
+        out.plan[i * 3 + 2] = found && p3 != 0xFF ? p3 : -1;
+      }
+      if (out.leaves) out.leaves[i] = leaves;
+    }
+    // no barrier here, as in plan_kernel
+  }
+}
+
+// ---------------------------------------------------------------------------
+// The shape terms of a board column (bbvec.h bb_board_terms): one lane per board, board_terms of bb_rules.h, four
+// int32 per board.  Above the grid cap the lanes stride.  No LDS, no atomics, no inline assembly.
+// ---------------------------------------------------------------------------
+constexpr int kTermsBlock = 256;
+constexpr int64_t kTermsMaxGrid = 1 << 10;
+
+__global__ void __launch_bounds__(kTermsBlock)
+board_terms_kernel(const uint64_t* __restrict__ board, int n, int32_t* __restrict__ terms) {
+  const int64_t stride = (int64_t)gridDim.x * kTermsBlock;
+  for (int64_t i = (int64_t)blockIdx.x * kTermsBlock + threadIdx.x; i < (int64_t)n; i += stride) {
+    int32_t v[4];
+    board_terms(board[i], v);
+    terms[i * 4 + 0] = v[0];
+    terms[i * 4 + 1] = v[1];
+    terms[i * 4 + 2] = v[2];
+    terms[i * 4 + 3] = v[3];
   }
 }
 
@@ -862,6 +981,22 @@ hipError_t launch_plan_each(const uint64_t* board, const uint32_t* hand, const i
                             const bb_greedy_weights* rows, int depth, const bb_plan_out& out, hipStream_t s) {
   const LookPos pos{board, hand, combo, nullptr};
   hipLaunchKernelGGL(plan_each_kernel, plan_grid(n), dim3(kPlanBlock), 0, s, look_table(), pos, n, rows, depth, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_plan_ext(const uint64_t* board, const uint32_t* hand, const int32_t* combo, int n,
+                           const bb_eval_weights* rows, int64_t w_stride, int depth, const bb_plan_out& out,
+                           hipStream_t s) {
+  const LookPos pos{board, hand, combo, nullptr};
+  hipLaunchKernelGGL(plan_ext_kernel, plan_grid(n), dim3(kPlanBlock), 0, s, look_table(), pos, n, rows, w_stride, depth,
+                     out);
+  return hipGetLastError();
+}
+
+hipError_t launch_board_terms(const uint64_t* board, int n, int32_t* terms, hipStream_t s) {
+  const int64_t blocks = ((int64_t)n + kTermsBlock - 1) / kTermsBlock;
+  const dim3 grid((unsigned)(blocks < kTermsMaxGrid ? blocks : kTermsMaxGrid));
+  hipLaunchKernelGGL(board_terms_kernel, grid, dim3(kTermsBlock), 0, s, board, n, terms);
   return hipGetLastError();
 }
 

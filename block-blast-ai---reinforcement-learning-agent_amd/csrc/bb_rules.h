@@ -68,6 +68,113 @@ BB_RULE int count_holes(uint64_t B) {
 }
 
 // --------------------------------------------------------------------------
+// Shape terms of a board (bbvec.h bb_board_terms / bb_eval_weights): what the board can still take.
+// --------------------------------------------------------------------------
+// perimeter: the pairs (empty cell, side) whose neighbour across that side is filled or off the board -- the four
+// neighbour boards of count_holes, counted side by side instead of and-ed.
+BB_RULE int perimeter(uint64_t B) {
+  const uint64_t n = (B << 8) | kRow0;
+  const uint64_t s = (B >> 8) | kRow7;
+  const uint64_t w = ((B << 1) & ~kCol0) | kCol0;
+  const uint64_t e = ((B >> 1) & ~kCol7) | kCol7;
+  return __builtin_popcountll(~B & n) + __builtin_popcountll(~B & s) + __builtin_popcountll(~B & w) +
+         __builtin_popcountll(~B & e);
+}
+
+// Where pieces fit (Board.can_place, board.py:71-93), as anchor boards.  With E the empty cells, `a` `b` `c` are E
+// seen 0, 1, 2 columns to the right of the anchor -- bit (r, c) of b says (r, c+1) is on the board and empty -- and
+// X >> 8k is X seen k rows below (rows off the board shift in as zeros: not empty).  A piece's anchor board is the
+// and of one such board per cell; the runs h2..h5 (cells to the right) and v2..v5 (cells below) are shared.
+struct Fit {
+  uint64_t a, b, c, h2, h3, h4, h5, v2, v3, v4, v5;
+};
+BB_RULE Fit fit_runs(uint64_t B) {
+  Fit f;
+  const uint64_t E = ~B;
+  f.a = E;
+  f.b = (E >> 1) & ~kCol7;
+  f.c = (E >> 2) & ~(kCol7 | (kCol7 >> 1));
+  f.h2 = f.a & f.b;
+  f.h3 = f.h2 & f.c;
+  f.h4 = f.h3 & ((E >> 3) & (kCol0 * 0x1Full));
+  f.h5 = f.h4 & ((E >> 4) & (kCol0 * 0x0Full));
+  f.v2 = E & (E >> 8);
+  f.v3 = f.v2 & (E >> 16);
+  f.v4 = f.v3 & (E >> 24);
+  f.v5 = f.v4 & (E >> 32);
+  return f;
+}
+// the anchors of SQUARE_3x3 (piece 36)
+BB_RULE uint64_t square3_anchors(const Fit& f) { return f.h3 & (f.h3 >> 8) & (f.h3 >> 16); }
+
+BB_RULE int room3(uint64_t B) { return __builtin_popcountll(square3_anchors(fit_runs(B))); }
+BB_RULE int room5(uint64_t B) {
+  const Fit f = fit_runs(B);
+  return __builtin_popcountll(f.h5) + __builtin_popcountll(f.v5);  // I5_H (15), I5_V (16)
+}
+
+// fits: the piece ids that fit somewhere.  A piece fits wherever a piece containing it fits, so where the 3x3 square
+// fits, the 33 pieces inside a 3x3 box do and only the four long bars are left to test; otherwise each of the 33 is
+// tested by its own anchor board (game/pieces.py names and cell sets, ids in the comments).
+BB_RULE int fits_of(const Fit& f, uint64_t sq) {
+  const int bars = (f.h4 != 0) + (f.v4 != 0) + (f.h5 != 0) + (f.v5 != 0);  // I_H 13, I_V 14, I5_H 15, I5_V 16
+  if (sq != 0) return 33 + bars;
+  const uint64_t a = f.a, b = f.b, c = f.c, h2 = f.h2, h3 = f.h3, v3 = f.v3;
+  const uint64_t a1 = a >> 8, b1 = b >> 8, c1 = c >> 8, a2 = a >> 16, b2 = b >> 16, c2 = c >> 16;
+  const uint64_t h21 = h2 >> 8, h31 = h3 >> 8;
+  const uint64_t vb3 = b & b1 & b2;  // the column right of the anchor, three cells down
+  const uint64_t bc = b & c;         // (0,1), (0,2)
+  int k = bars;
+  k += a != 0;                       //  0 SINGLE
+  k += h2 != 0;                      //  1 DOMINO_H
+  k += f.v2 != 0;                    //  2 DOMINO_V
+  k += (a & b1) != 0;                //  3 DIAG2_TL_BR
+  k += (b & a1) != 0;                //  4 DIAG2_TR_BL
+  k += h3 != 0;                      //  5 TRIO_H
+  k += v3 != 0;                      //  6 TRIO_V
+  k += (a & b1 & c2) != 0;           //  7 DIAG3_TL_BR
+  k += (c & b1 & a2) != 0;           //  8 DIAG3_TR_BL
+  k += (a & h21) != 0;               //  9 TRIO_L1
+  k += (h2 & b1) != 0;               // 10 TRIO_L2
+  k += (h2 & a1) != 0;               // 11 TRIO_L3
+  k += (b & h21) != 0;               // 12 TRIO_L4
+  k += (h2 & h21) != 0;              // 17 O
+  k += (b & h31) != 0;               // 18 T_UP
+  k += (h3 & b1) != 0;               // 19 T_DOWN
+  k += (v3 & b1) != 0;               // 20 T_LEFT
+  k += (vb3 & a1) != 0;              // 21 T_RIGHT
+  k += (bc & h21) != 0;              // 22 S_H
+  k += (a & h21 & b2) != 0;          // 23 S_V
+  k += (h2 & (bc >> 8)) != 0;        // 24 Z_H
+  k += (b & h21 & a2) != 0;          // 25 Z_V
+  k += (v3 & b2) != 0;               // 26 L_1
+  k += (h3 & a1) != 0;               // 27 L_2
+  k += (a & vb3) != 0;               // 28 L_3
+  k += (c & h31) != 0;               // 29 L_4
+  k += (vb3 & a2) != 0;              // 30 J_1
+  k += (a & h31) != 0;               // 31 J_2
+  k += (v3 & b) != 0;                // 32 J_3
+  k += (h3 & c1) != 0;               // 33 J_4
+  k += (h3 & h31) != 0;              // 34 RECT_2x3_H
+  k += (h2 & h21 & (h2 >> 16)) != 0; // 35 RECT_2x3_V
+  return k;                          // 36 SQUARE_3x3 does not fit here
+}
+BB_RULE int fits(uint64_t B) {
+  const Fit f = fit_runs(B);
+  return fits_of(f, square3_anchors(f));
+}
+
+// the four in the order of bb_board_terms
+BB_RULE void board_terms(uint64_t B, int32_t out[4]) {
+  const Fit f = fit_runs(B);
+  const uint64_t sq = square3_anchors(f);
+  out[0] = perimeter(B);
+  out[1] = __builtin_popcountll(sq);
+  out[2] = __builtin_popcountll(f.h5) + __builtin_popcountll(f.v5);
+  out[3] = fits_of(f, sq);
+}
+
+// --------------------------------------------------------------------------
 // Score of a move (engine.py:240-262, 406-429), select-only so that the branch-free move of the rollout kernel
 // uses it as it is.  `lines` lines cleared at combo `combo`:
 // --------------------------------------------------------------------------
@@ -165,6 +272,27 @@ BB_RULE int64_t move_terms(const bb_greedy_weights& w, const After& a) {
 BB_RULE int64_t state_terms(const bb_greedy_weights& w, const After& a) {
   return (int64_t)w.holes * a.holes + (int64_t)w.filled * a.filled + (int64_t)w.centre * a.centre +
          (int64_t)w.mobility * a.mobility + (int64_t)w.dead * (int)a.dead + (int64_t)w.refill * (int)a.refill;
+}
+
+// The same two under bb_eval_weights (bbvec.h bb_plan_actions_ext): the base terms, and on the state side the shape
+// terms of the afterstate's board.  A term whose weight is 0 is not computed; the runs are formed once for the
+// terms that need them.
+static_assert(sizeof(bb_eval_weights) == 12 * sizeof(int32_t), "an extended weight row is twelve int32");
+BB_RULE int64_t shape_terms(const bb_eval_weights& w, uint64_t B) {
+  int64_t v = 0;
+  if (w.perimeter != 0) v += (int64_t)w.perimeter * perimeter(B);
+  if ((w.room3 | w.room5 | w.fits) != 0) {
+    const Fit f = fit_runs(B);
+    const uint64_t sq = square3_anchors(f);
+    if (w.room3 != 0) v += (int64_t)w.room3 * __builtin_popcountll(sq);
+    if (w.room5 != 0) v += (int64_t)w.room5 * (__builtin_popcountll(f.h5) + __builtin_popcountll(f.v5));
+    if (w.fits != 0) v += (int64_t)w.fits * fits_of(f, sq);
+  }
+  return v;
+}
+BB_RULE int64_t move_terms(const bb_eval_weights& w, const After& a) { return move_terms(w.base, a); }
+BB_RULE int64_t state_terms(const bb_eval_weights& w, const After& a) {
+  return state_terms(w.base, a) + shape_terms(w, a.board);
 }
 
 // --------------------------------------------------------------------------

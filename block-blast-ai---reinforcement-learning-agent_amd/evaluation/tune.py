@@ -49,7 +49,10 @@ def _play_population(weight_dicts: Sequence[Dict[str, int]], games: int, moves: 
     """(scores, lengths, extras), int64 [P, G] each: env c * G + g plays candidate c on the piece stream seeded
     seed + g.  extras: None, or with census the EXTRAS of ``evaluate_agent(census=True)`` as [P, G] tensors."""
     p, g = len(weight_dicts), int(games)
-    rows = K.weight_rows(list(weight_dicts)).repeat_interleave(g, dim=0)
+    if any(set(w) & set(L.TERM_FIELDS) for w in weight_dicts):  # a shape weight is named: rows of twelve
+        rows = K.eval_rows(list(weight_dicts)).repeat_interleave(g, dim=0)
+    else:
+        rows = K.weight_rows(list(weight_dicts)).repeat_interleave(g, dim=0)
     agent = PopulationPlanAgent(rows, depth=depth, device=device)
     res = evaluate_agent(agent, num_episodes=p * g, seeds=[seed + e % g for e in range(p * g)], max_moves=int(moves),
                          **({"census": True} if census else {}))
@@ -132,8 +135,8 @@ def cem(fitness: Callable[[np.ndarray, int], np.ndarray], mean0, sigma0, populat
     return history
 
 
-def _dict_of(theta) -> Dict[str, int]:
-    return {k: int(v) for k, v in zip(L.GREEDY_FIELDS, theta)}
+def _dict_of(theta, fields: Sequence[str] = L.GREEDY_FIELDS) -> Dict[str, int]:
+    return {k: int(v) for k, v in zip(fields, theta)}
 
 
 def _agent_depth(agent: str, depth: int) -> int:
@@ -201,7 +204,7 @@ def tune(agent: str = "plan", depth: int = 3, population: int = 64, games: int =
          generations: int = 30, elite_frac: float = 0.25, seed: int = 1, init: Optional[Dict[str, int]] = None,
          fixed: Sequence[str] = ("dead",), device=None, output: Optional[str] = None, log: Optional[str] = None,
          sigma0: float = 300.0, scale: float = 1000, sigma_floor: float = 10, holdout_games: int = 32,
-         fitness: str = "score", horizon: Optional[int] = None) -> dict:
+         fitness: str = "score", horizon: Optional[int] = None, terms: Sequence[str] = ()) -> dict:
     """CEM over the weights of ``HandPlanAgent(depth)`` (agent "plan") or ``GreedyAgent`` (agent "greedy").
 
     Fitness is a candidate's mean final score over ``games`` games of at most ``moves`` moves
@@ -222,24 +225,40 @@ def tune(agent: str = "plan", depth: int = 3, population: int = 64, games: int =
     (``evaluate_population(census=True)``); ``horizon`` defaults to ``moves``.  Its generation records gain
     "mean_played_extras" and "best_extras" (the per-candidate means of the extras), the held-out comparison the
     census columns, and the final record "fitness" and "horizon".  With ``fitness="score"`` the records are what they
-    were.  The form of the objective and the horizon are untuned."""
+    were.  The form of the objective and the horizon are untuned.
+
+    ``terms``: names of ``L.TERM_FIELDS`` (perimeter, room3, room5, fits) to add to the searched vector (agent "plan"
+    only: the search with them is ``bb_plan_actions_ext``).  They start at init's value, 0 by default, and share
+    sigma0 and the normalisation with the eight; the dicts of the records then carry them and the settings name
+    them.  With no terms every record, candidate and random draw is what it was."""
     if fitness not in ("score", "survival"):
         raise ValueError(f"fitness must be 'score' or 'survival', not {fitness!r}")
+    terms = tuple(terms)
+    if set(terms) - set(L.TERM_FIELDS) or len(set(terms)) != len(terms):
+        raise ValueError(f"terms must be distinct names of {L.TERM_FIELDS}, not {list(terms)}")
+    if terms and agent != "plan":
+        raise ValueError("terms need agent 'plan': the one-ply greedy kernel has no extended form")
+    fields = L.GREEDY_FIELDS + tuple(k for k in L.TERM_FIELDS if k in terms)
     priced = fitness == "survival"
     horizon = int(moves) if horizon is None else int(horizon)
     extras_log: Dict[int, dict] = {}
     eval_depth = _agent_depth(agent, depth)
     init = dict(DEFAULT_WEIGHTS) if init is None else {**{k: 0 for k in L.GREEDY_FIELDS}, **init}
-    L.greedy_weights(init)  # rejects unknown names
-    unknown = set(fixed) - set(L.GREEDY_FIELDS)
+    if terms:
+        init = {**{k: 0 for k in fields}, **init}
+        if set(init) - set(fields):
+            raise ValueError(f"unknown init weights {sorted(set(init) - set(fields))}; the fields are {fields}")
+    else:
+        L.greedy_weights(init)  # rejects unknown names
+    unknown = set(fixed) - set(fields)
     if unknown:
-        raise ValueError(f"unknown fixed weights {sorted(unknown)}; the fields are {L.GREEDY_FIELDS}")
-    free = [i for i, k in enumerate(L.GREEDY_FIELDS) if k not in fixed]
-    mean0 = np.array([init[k] for k in L.GREEDY_FIELDS], dtype=np.float64)
+        raise ValueError(f"unknown fixed weights {sorted(unknown)}; the fields are {fields}")
+    free = [i for i, k in enumerate(fields) if k not in fixed]
+    mean0 = np.array([init[k] for k in fields], dtype=np.float64)
     t0 = time.perf_counter()
 
     def objective(cand: np.ndarray, k: int) -> np.ndarray:
-        sets = [_dict_of(c) for c in cand]
+        sets = [_dict_of(c, fields) for c in cand]
         if not priced:
             scores = evaluate_population(sets, games, moves, seed + k * games, eval_depth, device)
             return scores.double().mean(dim=1).numpy()
@@ -250,7 +269,7 @@ def tune(agent: str = "plan", depth: int = 3, population: int = 64, games: int =
     history = cem(objective, mean0, sigma0, population, elite_frac, generations, np.random.default_rng(seed), free,
                   scale=scale, sigma_floor=sigma_floor)
     final_theta = np.rint(normalise(history[-1]["mean"] if history else mean0, free, scale)).astype(np.int64)
-    weights = _dict_of(final_theta)
+    weights = _dict_of(final_theta, fields)
     held = compare([init, weights], holdout_games, moves, seed + HOLDOUT_SEED_OFFSET, eval_depth, device,
                    **({"census": True} if priced else {}))
     host = device is not None and torch.device(device).type == "cpu"
@@ -265,6 +284,8 @@ def tune(agent: str = "plan", depth: int = 3, population: int = 64, games: int =
              "wall_s": round(time.perf_counter() - t0, 3)}
     if priced:
         final["fitness"], final["horizon"] = fitness, horizon
+    if terms:
+        final["settings"]["terms"] = list(fields[len(L.GREEDY_FIELDS):])
     if output:
         doc = {"agent": agent, "weights": weights}
         if agent == "plan":
@@ -285,8 +306,9 @@ def tune(agent: str = "plan", depth: int = 3, population: int = 64, games: int =
                     "record": "generation", "generation": h["generation"],
                     "seeds": [seed + h["generation"] * games + g for g in range(games)],
                     "best_fitness": h["best_fitness"], "mean_fitness": h["mean_fitness"],
-                    "mean_played": _dict_of(h["candidates"][0]), "mean_played_fitness": float(h["fitness"][0]),
-                    "best": _dict_of(h["candidates"][best]),
+                    "mean_played": _dict_of(h["candidates"][0], fields),
+                    "mean_played_fitness": float(h["fitness"][0]),
+                    "best": _dict_of(h["candidates"][best], fields),
                     "mean": [float(x) for x in h["mean"]], "sigma": [float(x) for x in h["sigma"]], **more}) + "\n")
             f.write(json.dumps(final) + "\n")
     return final
@@ -318,6 +340,9 @@ def main() -> None:
     ap.add_argument("--fitness", choices=("score", "survival"), default="score",
                     help="survival: the score discounted by the census' probability of surviving --horizon moves")
     ap.add_argument("--horizon", type=int, default=None, help="--fitness survival: moves to survive (default --moves)")
+    ap.add_argument("--terms", type=str, default=None,
+                    help="--agent plan: shape terms to tune beside the eight, comma-separated names of "
+                         "perimeter,room3,room5,fits (they start at 0)")
     args = ap.parse_args()
     if args.compare:
         others = []
@@ -344,7 +369,8 @@ def main() -> None:
     final = tune(agent=args.agent, depth=args.depth, population=args.population, games=args.games, moves=args.moves,
                  generations=args.generations, elite_frac=args.elite_frac, seed=args.seed,
                  device=args.device, output=args.output, log=args.log, holdout_games=args.holdout_games,
-                 **({"fitness": args.fitness, "horizon": args.horizon} if args.fitness != "score" else {}))
+                 **({"fitness": args.fitness, "horizon": args.horizon} if args.fitness != "score" else {}),
+                 **({"terms": [t for t in args.terms.split(",") if t]} if args.terms else {}))
     print(json.dumps(final))
 
 

@@ -318,6 +318,31 @@ class DeviceEnvBatch:
                 "bb_plan_actions_each", self.handle, self.lib)
         return out
 
+    def board_terms(self, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """bb_board_terms on the live boards: int32 [N, 4], the shape terms in the order of ``L.TERM_FIELDS``
+        (perimeter, room3, room5, fits)."""
+        n = self.num_envs
+        out = torch.empty((n, 4), dtype=torch.int32, device=self.device) if out is None else out
+        assert out.dtype == torch.int32 and out.device == self.device and out.is_contiguous() and out.numel() == n * 4
+        L.check(self.lib.bb_board_terms(self.handle, _ptr(out), _stream(self.device)), "bb_board_terms", self.handle,
+                self.lib)
+        return out
+
+    def plan_actions_ext(self, out: torch.Tensor, rows: torch.Tensor, depth: int = 3,
+                         value: Optional[torch.Tensor] = None, plan: Optional[torch.Tensor] = None,
+                         leaves: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """bb_plan_actions_ext on the live state: ``plan_actions`` with the shape terms in every leaf's value.  rows:
+        int32 [1, 12] (one row for all envs) or [N, 12] on this device (``runtime.kernels.eval_rows``), read when the
+        launch runs."""
+        from . import kernels as K
+
+        o = K._plan_out({"action": out, "value": value, "plan": plan, "leaves": leaves}, self.num_envs, self.device)
+        stride = K._eval_rows("plan_actions_ext", rows, self.num_envs, self.device)
+        L.check(self.lib.bb_plan_actions_ext(self.handle, _ptr(rows), stride, int(depth), C.byref(o),
+                                             _stream(self.device)),
+                "bb_plan_actions_ext", self.handle, self.lib)
+        return out
+
     def plan_values(self, weights, depth: int = 3, out: Optional[dict] = None) -> dict:
         """bb_plan_values on the live state: the search of ``plan_actions`` kept per first move.  ``out``: a dict
         with any of "q" i64 / "rest" i32 / "leaves" i32 [N, 192] and "safe" i64 [N, 3] tensors to write (missing

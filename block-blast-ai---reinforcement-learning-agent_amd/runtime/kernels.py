@@ -350,6 +350,74 @@ def plan_actions_each(board: torch.Tensor, hand: torch.Tensor, rows: torch.Tenso
     return res
 
 
+def eval_rows(weights, n: Optional[int] = None, device=None) -> torch.Tensor:
+    """Rows of bb_eval_weights for ``plan_actions_ext``: ``weight_rows`` with the four shape weights after the
+    eight -- a contiguous int32 [n, 12] tensor on ``device`` (default the CPU), the columns in the order of
+    ``L.EVAL_FIELDS``.  ``weights``: a dict (missing = 0), repeated n times (once without n), or a list of dicts,
+    one per row.  Unknown names are rejected as ``L.eval_weights`` rejects them."""
+    dicts = [weights] * (1 if n is None else int(n)) if isinstance(weights, dict) else list(weights)
+    if n is not None and len(dicts) != int(n):
+        raise ValueError(f"eval_rows: {len(dicts)} weight sets for n = {n}")
+    if not dicts:
+        raise ValueError("eval_rows: at least one row is required")
+    for d in {id(d): d for d in dicts}.values():  # one check per distinct dict
+        L.eval_weights(d)
+    rows = [[int(d.get(k, 0)) for k in L.EVAL_FIELDS] for d in dicts]
+    return torch.tensor(rows, dtype=torch.int32).to(device if device is not None else "cpu").contiguous()
+
+
+def _eval_rows(call: str, rows, n: int, dev) -> int:
+    """The rows tensor of a ``*_ext`` call, checked: twelve int32 per row, one row for all positions or one per
+    position, where the positions are.  Returns w_stride (0: shared, 1: per position)."""
+    width = len(L.EVAL_FIELDS)
+    if not (isinstance(rows, torch.Tensor) and rows.dtype == torch.int32 and rows.device == dev
+            and rows.is_contiguous() and rows.dim() == 2 and rows.shape[1] == width and rows.shape[0] in (1, n)):
+        raise L.BBNativeError(f"{call}: rows must be a contiguous {torch.int32} [1, {width}] or [{n}, {width}] "
+                              f"tensor on {dev} (see eval_rows)")
+    return 1 if rows.shape[0] == n and n > 1 else 0
+
+
+def board_terms(board: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """bb_board_terms_pos: the four shape terms of every board, int32 [n, 4] in the order of ``L.TERM_FIELDS``
+    (perimeter, room3, room5, fits), in one launch.  board int64 [n] (bit r*8+c); n may be 0."""
+    n, dev = board.numel(), board.device
+    if not (board.dtype == torch.int64 and board.is_contiguous()):
+        raise L.BBNativeError(f"board_terms: board must be a contiguous {torch.int64} tensor")
+    out = torch.empty((n, 4), dtype=torch.int32, device=dev) if out is None else out
+    if not (out.dtype == torch.int32 and out.device == dev and out.is_contiguous() and out.numel() == n * 4):
+        raise L.BBNativeError(f"board_terms: out must be a contiguous {torch.int32} [{n}, 4] tensor on {dev}")
+    if n == 0:
+        return out
+    lib, stream = _look_lib(dev)
+    L.check(lib.bb_board_terms_pos(_p(board), n, _p(out), stream), "bb_board_terms_pos", lib=lib)
+    return out
+
+
+def plan_actions_ext(board: torch.Tensor, hand: torch.Tensor, rows: torch.Tensor, depth: int = 3,
+                     combo: Optional[torch.Tensor] = None, action: Optional[torch.Tensor] = None,
+                     value: Optional[torch.Tensor] = None, plan: Optional[torch.Tensor] = None,
+                     leaves: Optional[torch.Tensor] = None, want_value: bool = True, want_plan: bool = False,
+                     want_leaves: bool = False) -> dict:
+    """bb_plan_actions_ext_pos: ``plan_actions`` with the shape terms (perimeter, room3, room5, fits of the last
+    afterstate's board) added to every leaf's value.  rows: int32 [1, 12] (one row for all positions) or [n, 12]
+    (position i takes rows[i]), ``eval_rows``, where the positions are; they are read when the launch runs.  With
+    the four shape weights 0 the outputs are those of ``plan_actions_each`` under the first eight columns.  The
+    returned dict is ``plan_actions``'."""
+    pos, n, dev = _positions(board, hand, combo, None)
+    stride = _eval_rows("plan_actions_ext", rows, n, dev)
+    res = {"action": torch.empty(n, dtype=torch.int32, device=dev) if action is None else action}
+    for k, given, want in (("value", value, want_value), ("plan", plan, want_plan), ("leaves", leaves, want_leaves)):
+        if given is not None:
+            res[k] = given
+        elif want:
+            res[k] = torch.empty((n, 3) if k == "plan" else n, dtype=PLAN_OUTPUTS[k][0], device=dev)
+    o = _plan_out(res, n, dev)
+    lib, stream = _look_lib(dev)
+    L.check(lib.bb_plan_actions_ext_pos(C.byref(pos), n, _p(rows), stride, int(depth), C.byref(o), stream),
+            "bb_plan_actions_ext_pos", lib=lib)
+    return res
+
+
 PLAN_VALUE_OUTPUTS = {"q": (torch.int64, 192), "rest": (torch.int32, 192), "leaves": (torch.int32, 192),
                       "safe": (torch.int64, 3)}
 

@@ -139,6 +139,25 @@ def greedy_weights(weights: dict) -> GreedyWeights:
     return GreedyWeights(**{k: int(weights.get(k, 0)) for k in GREEDY_FIELDS})
 
 
+# the shape terms of a board (bb_board_terms writes them in this order) and bb_eval_weights: the eight, then one
+# weight per shape term
+TERM_FIELDS = ("perimeter", "room3", "room5", "fits")
+EVAL_FIELDS = GREEDY_FIELDS + TERM_FIELDS
+
+
+class EvalWeights(C.Structure):
+    """bb_eval_weights: bb_greedy_weights, then the four int32 weights of the shape terms (twelve int32)."""
+    _fields_ = [("base", GreedyWeights)] + [(k, C.c_int32) for k in TERM_FIELDS]
+
+
+def eval_weights(weights: dict) -> EvalWeights:
+    unknown = set(weights) - set(EVAL_FIELDS)
+    if unknown:
+        raise ValueError(f"unknown evaluation weights {sorted(unknown)}; the fields are {EVAL_FIELDS}")
+    return EvalWeights(base=greedy_weights({k: v for k, v in weights.items() if k in GREEDY_FIELDS}),
+                       **{k: int(weights.get(k, 0)) for k in TERM_FIELDS})
+
+
 class PlanOut(C.Structure):
     """bb_plan_out: device arrays action i32 [n] (required), value i64 [n], plan i32 [n][3], leaves i32 [n]."""
     _fields_ = [("action", C.c_void_p), ("value", C.c_void_p), ("plan", C.c_void_p), ("leaves", C.c_void_p)]
@@ -253,6 +272,10 @@ SIGNATURES = {
     "bb_greedy_actions_each": (C.c_int, [_P, _P, _P, _P, _P]),
     "bb_plan_actions_each_pos": (C.c_int, [C.POINTER(Positions), _I32, _P, _I32, C.POINTER(PlanOut), _P]),
     "bb_plan_actions_each": (C.c_int, [_P, _P, _I32, C.POINTER(PlanOut), _P]),
+    "bb_board_terms_pos": (C.c_int, [_P, _I32, _P, _P]),
+    "bb_board_terms": (C.c_int, [_P, _P, _P]),
+    "bb_plan_actions_ext_pos": (C.c_int, [C.POINTER(Positions), _I32, _P, C.c_int64, _I32, C.POINTER(PlanOut), _P]),
+    "bb_plan_actions_ext": (C.c_int, [_P, _P, C.c_int64, _I32, C.POINTER(PlanOut), _P]),
     "bb_plan_values_pos": (C.c_int, [C.POINTER(Positions), _I32, C.POINTER(GreedyWeights), _I32,
                                      C.POINTER(PlanValuesOut), _P]),
     "bb_plan_values": (C.c_int, [_P, C.POINTER(GreedyWeights), _I32, C.POINTER(PlanValuesOut), _P]),
@@ -328,6 +351,7 @@ HOST_SYMBOLS = ("bb_abi_version", "bb_build_id", "bb_create", "bb_destroy", "bb_
                 "bb_greedy_actions_pos", "bb_greedy_actions", "bb_plan_actions_pos", "bb_plan_actions",
                 "bb_greedy_actions_each_pos", "bb_greedy_actions_each", "bb_plan_actions_each_pos",
                 "bb_plan_actions_each",
+                "bb_board_terms_pos", "bb_board_terms", "bb_plan_actions_ext_pos", "bb_plan_actions_ext",
                 "bb_plan_values_pos", "bb_plan_values", "bb_safe_mask_pos", "bb_safe_mask",
                 "bb_refill_census_pos", "bb_refill_census", "bb_refill_values_pos", "bb_refill_values",
                 "bb_play_plan_pos")

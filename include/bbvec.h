@@ -67,7 +67,10 @@ extern "C" {
                                  the 37^3 hands a board can still be dealt (engine.py:155-224);
                                  (additive, still 9) bb_refill_values_out with bb_refill_values(_pos): next hands
                                  dealt by the dealer's law (engine.py:155-172) and searched, per board; bb_play_plan_out
-                                 with bb_play_plan_pos: a plan played to its leaf position */
+                                 with bb_play_plan_pos: a plan played to its leaf position;
+                                 (additive, still 9) bb_eval_weights with bb_board_terms(_pos) and
+                                 bb_plan_actions_ext(_pos): four shape terms of a board (perimeter, room3, room5,
+                                 fits) and the full-hand search with them added to every leaf's value */
 
 #define BB_OK 0
 #define BB_ERR_ARG (-1)
@@ -414,6 +417,45 @@ int bb_plan_actions(bb_env* env, const bb_greedy_weights* w, int32_t depth, cons
 int bb_plan_actions_each_pos(const bb_positions* pos, int32_t n, const bb_greedy_weights* d_w, int32_t depth,
                              const bb_plan_out* out, void* stream);
 int bb_plan_actions_each(bb_env* env, const bb_greedy_weights* d_w, int32_t depth, const bb_plan_out* out, void* stream);
+
+/* ---- shape terms ---------------------------------------------------------------
+ * Four exact integer terms of a board B (bit r*8+c set: cell filled).  "Fits" is
+ * Board.can_place (board.py:71-93): every cell of the piece on the board and empty.
+ *   perimeter  the pairs (empty cell, one of its four sides) whose neighbour across
+ *              that side is filled or off the board.  Empty board 32, full board 0.
+ *   room3      the anchors at which SQUARE_3x3 (piece 36) fits, 0..36
+ *   room5      the anchors at which I5_H (piece 15) fits plus those of I5_V (16), 0..64
+ *   fits       the piece ids 0..36 that fit at one anchor or more, 0..37
+ * bb_board_terms(_pos) writes them in this order, d_terms[i][0..3], for every board
+ * (the handle form: the live boards).  One launch, no allocation, no sync
+ * (graph-capturable), 64-bit indexing; n == 0 does nothing.  BB_ERR_ARG (the rule named
+ * in bb_last_error, before any HIP call) for a NULL board, n < 0 and a NULL d_terms. */
+int bb_board_terms_pos(const uint64_t* d_board, int32_t n, int32_t* d_terms /* [n][4] */, void* stream);
+int bb_board_terms(bb_env* env, int32_t* d_terms /* [N][4] */, void* stream);
+
+/* bb_plan_actions with the shape terms in the value: search(P, depth) above, move for
+ * move, with the same tie rule, outputs and "no legal action" answer.  The value of a
+ * maximal sequence is the sum above plus
+ *   w.perimeter*perimeter(B_k) + w.room3*room3(B_k) + w.room5*room5(B_k) + w.fits*fits(B_k)
+ * with B_k the board of the last afterstate after its clears, at dead and refill leaves
+ * alike.  d_w are rows of twelve int32 in the struct's field order, in the memory of the
+ * position columns (device memory for libbbvec.so, host memory for libbbvec_host.so),
+ * read when the launch runs.  w_stride 0: every position uses d_w[0]; 1: position i uses
+ * d_w[i]; any other value is refused.  A term whose weight is 0 in a position's row is
+ * not computed for that position, and with all four 0 the answers are those of
+ * bb_plan_actions_each(_pos) for `base`.  BB_ERR_ARG (the rule named, before any HIP
+ * call) for NULL positions, n < 0 (n == 0 does nothing), NULL weight rows, a w_stride
+ * that is not 0 or 1, depth outside 1..3 and a NULL out or out->action.  The handle form
+ * refuses a handle in BB_ERR_DEVICE / BB_ERR_STATE.  One launch, asynchronous, no
+ * allocation, graph-capturable from the first call. */
+typedef struct bb_eval_weights {
+  bb_greedy_weights base;                /* the eight terms, unchanged */
+  int32_t perimeter, room3, room5, fits; /* state terms of the last afterstate's board */
+} bb_eval_weights;                       /* twelve int32, 48 bytes */
+int bb_plan_actions_ext_pos(const bb_positions* pos, int32_t n, const bb_eval_weights* d_w, int64_t w_stride,
+                            int32_t depth, const bb_plan_out* out, void* stream);
+int bb_plan_actions_ext(bb_env* env, const bb_eval_weights* d_w, int64_t w_stride, int32_t depth,
+                        const bb_plan_out* out, void* stream);
 
 /* ---- per-action full-hand values and the hand-safe mask -----------------------
  * What bb_plan_actions folds into one maximum, kept per first move.  The search
