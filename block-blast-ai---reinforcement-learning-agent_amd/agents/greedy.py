@@ -7,7 +7,8 @@ integer value over the afterstates of the 192 actions, csrc/bb_lookahead.hip), `
 Philox random-legal policy ``bb_random_actions``.  ``HandPlanAgent`` searches every way to play out the hand
 (``bb_plan_actions``, the fused search kernel of the same file; ``evaluate.py --agent plan``).
 ``TwoHandPlanAgent`` looks past the refill that search stops at: below its best first moves it deals next hands by the
-dealer's law and searches them (``bb_play_plan_pos``, ``bb_refill_values``; ``evaluate.py --agent plan2``).
+dealer's law and searches them (``bb_play_plan_pos``, ``bb_refill_values``; ``evaluate.py --agent plan2``); ``TwoHandShapeAgent`` is that agent under
+the twelve weights (``bb_plan_values_ext``, ``bb_refill_values_ext``).
 ``PopulationPlanAgent`` is that search with weights of its own for every env (``bb_plan_actions_each``), which
 ``evaluation/tune.py`` tunes the weights with.  ``HandPlanAgent`` and ``PopulationPlanAgent`` also take the four shape
 weights of ``L.TERM_FIELDS`` (perimeter, room3, room5, fits) and then search with ``bb_plan_actions_ext``.
@@ -71,8 +72,10 @@ class GreedyAgent(BaseAgent):
             self.weights.update({k: int(v) for k, v in weights.items()})
 
     def _check_weights(self, weights: Dict[str, int]) -> None:
-        """Rejects names this agent's kernels have no term for.  The shape terms of ``L.TERM_FIELDS`` exist only in
-        the full-hand search (``bb_plan_actions_ext``), which ``HandPlanAgent`` plays through."""
+        """Rejects names this agent's kernels have no term for.  The shape terms of ``L.TERM_FIELDS`` exist in the
+        full-hand search and its per-action and dealt-hand forms (``bb_plan_actions_ext``, ``bb_plan_values_ext``,
+        ``bb_refill_values_ext``), which ``HandPlanAgent`` and ``TwoHandShapeAgent`` play through; the one-ply
+        ``bb_greedy_actions`` has no extended form."""
         shape = sorted(set(weights) & set(L.TERM_FIELDS))
         if shape:
             raise ValueError(f"{type(self).__name__} has no extended kernel yet: the shape weights {shape} are "
@@ -212,6 +215,20 @@ class TwoHandPlanAgent(HandPlanAgent):
         """The Philox key of the deals of decision ``move`` (0-based): seed + (move + 1) * 0x9E3779B97F4A7C15 mod 2^64."""
         return (int(seed) + (int(move) + 1) * 0x9E3779B97F4A7C15) & (2 ** 64 - 1)
 
+    # the three kernel calls of a decision, which TwoHandShapeAgent makes under twelve weights
+    def _plan_values_env(self, env_batch, out: dict) -> dict:
+        return env_batch.plan_values(self.weights, self.depth, out=out)
+
+    def _plan_values_pos(self, board, hand) -> dict:
+        from runtime import kernels as K
+
+        return K.plan_values(board, hand, self.weights, self.depth, want=("q", "rest"))
+
+    def _refill_values(self, board, deals: int, seed: int, combo, stream) -> torch.Tensor:
+        from runtime import kernels as K
+
+        return K.refill_values(board, self.weights, deals, seed, combo=combo, stream=stream, depth=self.depth)["value"]
+
     def _decide(self, board, hand, combo, q, rest) -> torch.Tensor:
         """Steps 2-6 for n positions: board i64 / hand i32 / combo i32 [n], q i64 / rest i32 [n, 192] -> int64 [n]."""
         from runtime import kernels as K
@@ -231,9 +248,8 @@ class TwoHandPlanAgent(HandPlanAgent):
         idx = torch.nonzero(refill).view(-1)
         if idx.numel():
             root = torch.arange(n, dtype=torch.int64, device=board.device).repeat_interleave(k)
-            v = K.refill_values(leaf["board"][idx].contiguous(), self.weights, m, self.deal_seed(self.seed, self.moves),
-                                combo=leaf["combo"][idx].contiguous(), stream=root[idx].contiguous(),
-                                depth=self.depth)["value"]
+            v = self._refill_values(leaf["board"][idx].contiguous(), m, self.deal_seed(self.seed, self.moves),
+                                    leaf["combo"][idx].contiguous(), root[idx].contiguous())
             moved = self.weights["lines"] * leaf["lines"][idx].long() + self.weights["score"] * leaf["score"][idx]
             q2[idx] = m * moved + v.sum(dim=1)
         q2 = q2.view(n, k)
@@ -245,9 +261,8 @@ class TwoHandPlanAgent(HandPlanAgent):
     def act_env(self, env_batch, out: torch.Tensor) -> torch.Tensor:
         """The action of every env of a ``DeviceEnvBatch`` into out (int32 [N]); one decision of the move counter."""
         n, dev = env_batch.num_envs, env_batch.device
-        pv = env_batch.plan_values(self.weights, self.depth,
-                                   out={"q": torch.empty((n, 192), dtype=torch.int64, device=dev),
-                                        "rest": torch.empty((n, 192), dtype=torch.int32, device=dev)})
+        pv = self._plan_values_env(env_batch, {"q": torch.empty((n, 192), dtype=torch.int64, device=dev),
+                                               "rest": torch.empty((n, 192), dtype=torch.int32, device=dev)})
         board = torch.empty(n, dtype=torch.int64, device=dev)
         hand = torch.empty(n, dtype=torch.int32, device=dev)
         combo = torch.empty(n, dtype=torch.int32, device=dev)
@@ -258,12 +273,10 @@ class TwoHandPlanAgent(HandPlanAgent):
 
     def select_action(self, observation: Dict[str, Any], deterministic: bool = True) -> Tuple[int, Dict[str, Any]]:
         """From a Gym observation (no combo count in it: see ``GreedyAgent.select_action``)."""
-        from runtime import kernels as K
-
         bits, hand = _position_of(observation)
         board = torch.tensor([bits - (1 << 64) if bits >= 1 << 63 else bits], dtype=torch.int64, device=self.device)
         hand_t = torch.tensor([hand], dtype=torch.int32, device=self.device)
-        pv = K.plan_values(board, hand_t, self.weights, self.depth, want=("q", "rest"))
+        pv = self._plan_values_pos(board, hand_t)
         action = self._decide(board, hand_t, torch.zeros(1, dtype=torch.int32, device=self.device), pv["q"], pv["rest"])
         return int(action.cpu().item()), {}
 
@@ -279,6 +292,47 @@ class TwoHandPlanAgent(HandPlanAgent):
         self.candidates = int(data.get("candidates", self.candidates))
         self.deals = int(data.get("deals", self.deals))
         self.seed = int(data.get("seed", self.seed))
+
+
+class TwoHandShapeAgent(TwoHandPlanAgent):
+    """``TwoHandPlanAgent`` under the twelve weights: its weights (and ``load``'s JSON) may name the shape terms of
+    ``L.TERM_FIELDS``.  When one of them is not 0, steps 1 and 4 run ``plan_values_ext`` and ``refill_values_ext``
+    under one shared row, made once per device as ``HandPlanAgent`` makes its own, so q and the dealt hands' values
+    carry the shape terms of their leaf boards; the move terms of step 4 stay ``weights["lines"]`` and
+    ``weights["score"]``.  With the four shape weights 0 it calls exactly what ``TwoHandPlanAgent`` calls."""
+
+    def _check_weights(self, weights: Dict[str, int]) -> None:
+        L.eval_weights(weights)
+
+    def _plan_values_env(self, env_batch, out: dict) -> dict:
+        rows = self._ext_rows(env_batch.device)
+        if rows is not None:
+            return env_batch.plan_values_ext(rows, self.depth, out=out)
+        return env_batch.plan_values(self._base_weights(), self.depth, out=out)
+
+    def _plan_values_pos(self, board, hand) -> dict:
+        from runtime import kernels as K
+
+        rows = self._ext_rows(board.device)
+        if rows is not None:
+            return K.plan_values_ext(board, hand, rows, self.depth, want=("q", "rest"))
+        return K.plan_values(board, hand, self._base_weights(), self.depth, want=("q", "rest"))
+
+    def _refill_values(self, board, deals: int, seed: int, combo, stream) -> torch.Tensor:
+        from runtime import kernels as K
+
+        rows = self._ext_rows(board.device)
+        if rows is not None:
+            return K.refill_values_ext(board, rows, deals, seed, combo=combo, stream=stream, depth=self.depth)["value"]
+        return K.refill_values(board, self._base_weights(), deals, seed, combo=combo, stream=stream,
+                               depth=self.depth)["value"]
+
+
+def two_hand_agent_class(weights: Optional[Dict[str, int]]):
+    """The two-hand agent for a weight set: ``TwoHandShapeAgent`` when it names a shape weight that is not 0,
+    ``TwoHandPlanAgent`` otherwise (``evaluate.py --agent plan2``, ``tune.py --compare ... --agent plan2``)."""
+    shaped = any(int((weights or {}).get(k, 0)) != 0 for k in L.TERM_FIELDS)
+    return TwoHandShapeAgent if shaped else TwoHandPlanAgent
 
 
 class PopulationPlanAgent(BaseAgent):

@@ -1029,6 +1029,34 @@ class PPOAgent(BaseAgent):
         self._optimizer_step(loss)
         return stats
 
+    @staticmethod
+    def search_labeller(weights, depth: int):
+        """The call that labels a minibatch with the teacher's values: label(board, hand, combo, q) writes q int64
+        [n, 192] in place.  Weights that name a shape term (``L.TERM_FIELDS``) other than 0 are searched by
+        ``K.plan_values_ext`` under one shared row, made once where the positions are; any other weights by
+        ``K.plan_values`` under the eight, the call made before the shape terms existed."""
+        from runtime import lib as L
+
+        if isinstance(weights, dict) and any(int(weights.get(k, 0)) != 0 for k in L.TERM_FIELDS):
+            L.eval_weights(weights)  # rejects unknown names
+            rows = {}
+
+            def label_ext(board, hand, combo, q):
+                r = rows.get(board.device)
+                if r is None:
+                    r = rows[board.device] = K.eval_rows(weights, device=board.device)
+                K.plan_values_ext(board, hand, r, depth, combo=combo, out={"q": q})
+
+            return label_ext
+        if isinstance(weights, dict):
+            weights = {k: v for k, v in weights.items() if k not in L.TERM_FIELDS}  # shape weights that are all 0
+        w = K._weights(weights)
+
+        def label(board, hand, combo, q):
+            K.plan_values(board, hand, w, depth, combo=combo, out={"q": q})
+
+        return label
+
     def distill(self, buffer, weights, depth: int = 3, tau: float = 50.0, epochs: int = 1,
                 batch_size: Optional[int] = None) -> Dict[str, float]:
         """Supervised epochs on the stored positions of ``buffer`` (PackedRolloutBuffer(positions=True)), labelled
@@ -1036,7 +1064,7 @@ class PPOAgent(BaseAgent):
         a scratch kept per minibatch size), the forward pass, the fused loss and the optimizer step, with no host
         read inside the loop.  Returns the mean statistics under DISTILL_KEYS."""
         bs = int(batch_size or self.config.batch_size)
-        w = K._weights(weights)
+        label = self.search_labeller(weights, depth)
         acc = torch.zeros(6, dtype=torch.float32, device=self.device)
         n = 0
         for _ in range(int(epochs)):
@@ -1045,7 +1073,7 @@ class PPOAgent(BaseAgent):
                 if q is None:
                     q = self._distill_q[board.numel()] = torch.empty((board.numel(), 192), dtype=torch.int64,
                                                                      device=board.device)
-                K.plan_values(board, hand, w, depth, combo=combo, out={"q": q})
+                label(board, hand, combo, q)
                 acc += self.distill_minibatch(x, mask_bits, q, tau)
                 n += 1
         m = (acc / max(n, 1)).tolist()
@@ -1131,7 +1159,7 @@ class PPOAgent(BaseAgent):
         if isinstance(last_values, np.ndarray):
             last_values = torch.from_numpy(last_values)
         buffer.compute_returns_and_advantages(last_values, cfg.gamma, cfg.gae_lambda)
-        w = K._weights(weights)
+        label = self.search_labeller(weights, depth)
         coefs = (*(float(c) for c in coefs), float(tau))
         if len(coefs) != 5:
             raise ValueError("update_guided: coefs = (policy, value, entropy, distill)")
@@ -1145,7 +1173,7 @@ class PPOAgent(BaseAgent):
                 if q is None:
                     q = self._distill_q[board.numel()] = torch.empty((board.numel(), 192), dtype=torch.int64,
                                                                      device=board.device)
-                K.plan_values(board, hand, w, depth, combo=combo, out={"q": q})
+                label(board, hand, combo, q)
                 acc += self.guided_minibatch(x, mask_bits, actions, old_lp, adv, ret, q, coefs)
                 n += 1
         m = (acc / max(n, 1)).tolist()

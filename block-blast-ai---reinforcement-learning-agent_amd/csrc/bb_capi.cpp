@@ -767,6 +767,45 @@ int bb_refill_values(bb_env* env, const uint64_t* d_stream, const bb_greedy_weig
   });
 }
 
+// The two above under rows of bb_eval_weights (plan_values_ext_kernel, refill_values_ext_kernel): d_w is device memory
+int bb_plan_values_ext_pos(const bb_positions* pos, int32_t n, const bb_eval_weights* d_w, int64_t w_stride,
+                           int32_t depth, const bb_plan_values_out* out, void* stream) {
+  const char* rule = bb_look_rules::plan_values_ext_pos(pos, n, d_w, w_stride, depth, out);
+  if (!rule && n == 0) return BB_OK;  // accepted, and nothing to do
+  return look_pos_call("bb_plan_values_ext_pos", rule, [&] {
+    return launch_plan_values_ext(pos->board, pos->hand, pos->combo, n, d_w, w_stride, depth, *out,
+                                  (hipStream_t)stream);
+  });
+}
+
+int bb_plan_values_ext(bb_env* env, const bb_eval_weights* d_w, int64_t w_stride, int32_t depth,
+                       const bb_plan_values_out* out, void* stream) {
+  return look_env_call(env, "bb_plan_values_ext", bb_look_rules::plan_values_ext(d_w, w_stride, depth, out), [&] {
+    return launch_plan_values_ext(env->d.board, env->d.hand, env->d.combo, env->n, d_w, w_stride, depth, *out,
+                                  (hipStream_t)stream);
+  });
+}
+
+int bb_refill_values_ext_pos(const uint64_t* d_board, const int32_t* d_combo, const uint64_t* d_stream, int32_t n,
+                             const bb_eval_weights* d_w, int64_t w_stride, int32_t depth, int32_t deals,
+                             uint64_t seed, const bb_refill_values_out* out, void* stream) {
+  const char* rule = bb_look_rules::refill_values_ext_pos(d_board, n, d_w, w_stride, depth, deals, out);
+  if (!rule && n == 0) return BB_OK;  // accepted, and nothing to do
+  return look_pos_call("bb_refill_values_ext_pos", rule, [&] {
+    return launch_refill_values_ext(d_board, d_combo, d_stream, n, d_w, w_stride, depth, deals, seed, *out,
+                                    (hipStream_t)stream);
+  });
+}
+
+int bb_refill_values_ext(bb_env* env, const uint64_t* d_stream, const bb_eval_weights* d_w, int64_t w_stride,
+                         int32_t depth, int32_t deals, uint64_t seed, const bb_refill_values_out* out, void* stream) {
+  return look_env_call(
+      env, "bb_refill_values_ext", bb_look_rules::refill_values_ext(d_w, w_stride, depth, deals, out), [&] {
+        return launch_refill_values_ext(env->d.board, env->d.combo, d_stream, env->n, d_w, w_stride, depth, deals, seed,
+                                        *out, (hipStream_t)stream);
+      });
+}
+
 // A plan played to its leaf (play_plan_kernel, csrc/bb_lookahead.hip)
 int bb_play_plan_pos(const bb_positions* pos, int32_t n, const int32_t* d_plan, const bb_play_plan_out* out,
                      void* stream) {

@@ -127,6 +127,14 @@ hipError_t launch_refill_census(const uint64_t* board, int n, const bb_census_ou
 hipError_t launch_refill_values(const uint64_t* board, const int32_t* combo, const uint64_t* stream_id, int n,
                                 const bb_greedy_weights& w, int depth, int deals, uint64_t seed,
                                 const bb_refill_values_out& out, hipStream_t s);
+// launch_plan_values / launch_refill_values under bb_eval_weights (bb_lookahead.hip): position (board) i takes
+// rows[i * w_stride], w_stride 0 or 1, n > 0
+hipError_t launch_plan_values_ext(const uint64_t* board, const uint32_t* hand, const int32_t* combo, int n,
+                                  const bb_eval_weights* rows, int64_t w_stride, int depth,
+                                  const bb_plan_values_out& out, hipStream_t s);
+hipError_t launch_refill_values_ext(const uint64_t* board, const int32_t* combo, const uint64_t* stream_id, int n,
+                                    const bb_eval_weights* rows, int64_t w_stride, int depth, int deals, uint64_t seed,
+                                    const bb_refill_values_out& out, hipStream_t s);
 // a plan played to its leaf (bb_lookahead.hip): n > 0, plan [n][3], the outputs [n], not all NULL
 hipError_t launch_play_plan(const uint64_t* board, const uint32_t* hand, const int32_t* combo, int n,
                             const int32_t* plan, const bb_play_plan_out& out, hipStream_t s);

@@ -463,33 +463,55 @@ void board_terms_host(const uint64_t* board, int32_t n, int32_t* terms) {
   for (int32_t i = 0; i < n; ++i) bb::board_terms(board[i], &terms[4 * (size_t)i]);
 }
 
-// bbvec.h bb_plan_values (the host twin of plan_values_kernel): the same DFS, started below each first move
+// One position of bb_plan_values under either weight type: the same DFS, started below each first move
+template <class W>
+void plan_values_one(uint64_t board, uint32_t hand, int cb, size_t i, const W& w, int depth,
+                     const bb_plan_values_out& out) {
+  uint64_t safe[3] = {0, 0, 0};
+  for (int act = 0; act < 192; ++act) {
+    const After a = eval_action(board, hand, cb, act);
+    PlanBest best{INT64_MIN, {-1, -1, -1}, 0, false};
+    if (a.legal) {
+      int32_t seq[3] = {act, -1, -1};
+      if (depth == 1 || a.refill || a.dead) {
+        best = PlanBest{move_terms(w, a) + state_terms(w, a), {act, -1, -1}, 1, !a.dead};
+      } else {
+        plan_dfs(a.board, hand_use(hand, act >> 6), a.combo1, depth - 1, 1, move_terms(w, a), seq, w, best);
+      }
+    }
+    const size_t o = i * 192 + (size_t)act;
+    if (out.q) out.q[o] = best.value;
+    if (out.rest) out.rest[o] = a.legal ? (best.plan[1] & 0xFF) | ((best.plan[2] & 0xFF) << 8) : -1;
+    if (out.leaves) out.leaves[o] = best.leaves;
+    if (best.alive) safe[act >> 6] |= 1ull << (act & 63);
+  }
+  if (out.safe)
+    for (int p = 0; p < 3; ++p) out.safe[3 * i + p] = safe[p];
+}
+
+// bbvec.h bb_plan_values (the host twin of plan_values_kernel)
 void plan_values_host(const uint64_t* board, const uint32_t* hand, const int32_t* combo, int32_t n,
                       const bb_greedy_weights& w, int depth, const bb_plan_values_out& out) {
   if (depth == 3 && !out.q && !out.rest && !out.leaves) depth = 2;  // the same safe set (bbvec.h)
 #pragma omp parallel for schedule(dynamic, 1)
+  for (int32_t i = 0; i < n; ++i) plan_values_one(board[i], hand[i], combo ? combo[i] : 0, (size_t)i, w, depth, out);
+}
+
+inline bool shaped(const bb_eval_weights& w) { return (w.perimeter | w.room3 | w.room5 | w.fits) != 0; }
+
+// bbvec.h bb_plan_values_ext (the host twin of plan_values_ext_kernel): position i takes rows[i * w_stride], w_stride
+// 0 or 1; a row with the four shape weights 0 is searched under its base, as the kernel does
+void plan_values_ext_host(const uint64_t* board, const uint32_t* hand, const int32_t* combo, int32_t n,
+                          const bb_eval_weights* rows, int64_t w_stride, int depth, const bb_plan_values_out& out) {
+  if (depth == 3 && !out.q && !out.rest && !out.leaves) depth = 2;  // the same safe set (bbvec.h)
+#pragma omp parallel for schedule(dynamic, 1)
   for (int32_t i = 0; i < n; ++i) {
+    const bb_eval_weights w = rows[(int64_t)i * w_stride];
     const int cb = combo ? combo[i] : 0;
-    uint64_t safe[3] = {0, 0, 0};
-    for (int act = 0; act < 192; ++act) {
-      const After a = eval_action(board[i], hand[i], cb, act);
-      PlanBest best{INT64_MIN, {-1, -1, -1}, 0, false};
-      if (a.legal) {
-        int32_t seq[3] = {act, -1, -1};
-        if (depth == 1 || a.refill || a.dead) {
-          best = PlanBest{move_terms(w, a) + state_terms(w, a), {act, -1, -1}, 1, !a.dead};
-        } else {
-          plan_dfs(a.board, hand_use(hand[i], act >> 6), a.combo1, depth - 1, 1, move_terms(w, a), seq, w, best);
-        }
-      }
-      const size_t o = (size_t)i * 192 + (size_t)act;
-      if (out.q) out.q[o] = best.value;
-      if (out.rest) out.rest[o] = a.legal ? (best.plan[1] & 0xFF) | ((best.plan[2] & 0xFF) << 8) : -1;
-      if (out.leaves) out.leaves[o] = best.leaves;
-      if (best.alive) safe[act >> 6] |= 1ull << (act & 63);
-    }
-    if (out.safe)
-      for (int p = 0; p < 3; ++p) out.safe[3 * (size_t)i + p] = safe[p];
+    if (shaped(w))
+      plan_values_one(board[i], hand[i], cb, (size_t)i, w, depth, out);
+    else
+      plan_values_one(board[i], hand[i], cb, (size_t)i, w.base, depth, out);
   }
 }
 
@@ -597,8 +619,34 @@ void philox_w012(uint64_t seed, uint64_t idx, uint64_t step, uint32_t out[3]) {
   out[2] = c2;
 }
 
-// bbvec.h bb_refill_values (the host twin of refill_values_kernel): the dealer of engine.py:155-172 on Philox words
-// with this file's own solvable(), then plan_dfs on the dealt hand.  One (board, deal) pair per iteration.
+// The deal of pair (board B, stream idx, deal j): the dealer of engine.py:155-172 on Philox words with this file's own
+// solvable().  Returns the hand; attempts is negative when nothing was accepted.  No weights are read.
+uint32_t refill_deal(uint64_t B, uint64_t seed, uint64_t idx, int64_t j, int32_t& attempts) {
+  uint32_t id[3] = {0, 0, 0};
+  attempts = -100;
+  for (int t = 0; t < 100; ++t) {
+    uint32_t wd[3];
+    philox_w012(seed, idx, ((uint64_t)j << 7) | (uint64_t)t, wd);
+    for (int q = 0; q < 3; ++q) id[q] = (uint32_t)(((uint64_t)wd[q] * 37ull) >> 32);
+    if (solvable(B, id)) {
+      attempts = t + 1;
+      break;  // after 100 refusals the last draw stays (engine.py:171-172)
+    }
+  }
+  return hand_pack(id[0], id[1], id[2], 0u, false, false);
+}
+
+// plan_dfs on a dealt hand under either weight type; `dead` stands in when the hand has no legal first move
+template <class W>
+int64_t refill_search(uint64_t B, uint32_t hand, int combo, int depth, const W& w, int32_t dead) {
+  PlanBest best{INT64_MIN, {-1, -1, -1}, 0, false};
+  int32_t seq[3];
+  plan_dfs(B, hand, combo, depth, 0, 0, seq, w, best);
+  return best.leaves ? best.value : (int64_t)dead;
+}
+
+// bbvec.h bb_refill_values (the host twin of refill_values_kernel): the deal, then plan_dfs on the dealt hand.  One
+// (board, deal) pair per iteration.
 void refill_values_host(const uint64_t* board, const int32_t* combo, const uint64_t* stream_id, int32_t n,
                         const bb_greedy_weights& w, int depth, int32_t deals, uint64_t seed,
                         const bb_refill_values_out& out) {
@@ -607,25 +655,33 @@ void refill_values_host(const uint64_t* board, const int32_t* combo, const uint6
   for (int64_t k = 0; k < pairs; ++k) {
     const int64_t i = k / deals, j = k % deals;
     const uint64_t B = board[i], idx = stream_id ? stream_id[i] : (uint64_t)i;
-    uint32_t id[3] = {0, 0, 0};
-    int32_t attempts = -100;
-    for (int t = 0; t < 100; ++t) {
-      uint32_t wd[3];
-      philox_w012(seed, idx, ((uint64_t)j << 7) | (uint64_t)t, wd);
-      for (int q = 0; q < 3; ++q) id[q] = (uint32_t)(((uint64_t)wd[q] * 37ull) >> 32);
-      if (solvable(B, id)) {
-        attempts = t + 1;
-        break;  // after 100 refusals the last draw stays (engine.py:171-172)
-      }
-    }
-    const uint32_t hand = hand_pack(id[0], id[1], id[2], 0u, false, false);
+    int32_t attempts;
+    const uint32_t hand = refill_deal(B, seed, idx, j, attempts);
+    if (out.hand) out.hand[k] = hand;
+    if (out.attempts) out.attempts[k] = attempts;
+    if (out.value) out.value[k] = refill_search(B, hand, combo ? combo[i] : 0, depth, w, w.dead);
+  }
+}
+
+// bbvec.h bb_refill_values_ext (the host twin of refill_values_ext_kernel): every deal of board i is searched under
+// rows[i * w_stride], w_stride 0 or 1; a hand without a legal first move gets the row's base.dead alone
+void refill_values_ext_host(const uint64_t* board, const int32_t* combo, const uint64_t* stream_id, int32_t n,
+                            const bb_eval_weights* rows, int64_t w_stride, int depth, int32_t deals, uint64_t seed,
+                            const bb_refill_values_out& out) {
+  const int64_t pairs = (int64_t)n * deals;
+#pragma omp parallel for schedule(dynamic, 1)
+  for (int64_t k = 0; k < pairs; ++k) {
+    const int64_t i = k / deals, j = k % deals;
+    const uint64_t B = board[i], idx = stream_id ? stream_id[i] : (uint64_t)i;
+    const bb_eval_weights w = rows[i * w_stride];
+    int32_t attempts;
+    const uint32_t hand = refill_deal(B, seed, idx, j, attempts);
     if (out.hand) out.hand[k] = hand;
     if (out.attempts) out.attempts[k] = attempts;
     if (out.value) {
-      PlanBest best{INT64_MIN, {-1, -1, -1}, 0, false};
-      int32_t seq[3];
-      plan_dfs(B, hand, combo ? combo[i] : 0, depth, 0, 0, seq, w, best);
-      out.value[k] = best.leaves ? best.value : (int64_t)w.dead;
+      const int cb = combo ? combo[i] : 0;
+      out.value[k] = shaped(w) ? refill_search(B, hand, cb, depth, w, w.base.dead)
+                               : refill_search(B, hand, cb, depth, w.base, w.base.dead);
     }
   }
 }
@@ -1100,6 +1156,45 @@ int bb_refill_values(bb_env* env, const uint64_t* d_stream, const bb_greedy_weig
   if (!env) return BB_ERR_ARG;
   if (int rc = refused(env, "bb_refill_values", R::refill_values(w, depth, deals, out))) return rc;
   refill_values_host(env->board.data(), env->combo.data(), d_stream, env->n, *w, depth, deals, seed, *out);
+  return BB_OK;
+}
+
+int bb_plan_values_ext_pos(const bb_positions* pos, int32_t n, const bb_eval_weights* d_w, int64_t w_stride,
+                           int32_t depth, const bb_plan_values_out* out, void* stream) {
+  (void)stream;
+  if (int rc = refused(nullptr, "bb_plan_values_ext_pos", R::plan_values_ext_pos(pos, n, d_w, w_stride, depth, out)))
+    return rc;
+  plan_values_ext_host(pos->board, pos->hand, pos->combo, n, d_w, w_stride, depth, *out);
+  return BB_OK;
+}
+
+int bb_plan_values_ext(bb_env* env, const bb_eval_weights* d_w, int64_t w_stride, int32_t depth,
+                       const bb_plan_values_out* out, void* stream) {
+  (void)stream;
+  if (!env) return BB_ERR_ARG;
+  if (int rc = refused(env, "bb_plan_values_ext", R::plan_values_ext(d_w, w_stride, depth, out))) return rc;
+  plan_values_ext_host(env->board.data(), env->hand.data(), env->combo.data(), env->n, d_w, w_stride, depth, *out);
+  return BB_OK;
+}
+
+int bb_refill_values_ext_pos(const uint64_t* d_board, const int32_t* d_combo, const uint64_t* d_stream, int32_t n,
+                             const bb_eval_weights* d_w, int64_t w_stride, int32_t depth, int32_t deals,
+                             uint64_t seed, const bb_refill_values_out* out, void* stream) {
+  (void)stream;
+  if (int rc = refused(nullptr, "bb_refill_values_ext_pos",
+                       R::refill_values_ext_pos(d_board, n, d_w, w_stride, depth, deals, out)))
+    return rc;
+  refill_values_ext_host(d_board, d_combo, d_stream, n, d_w, w_stride, depth, deals, seed, *out);
+  return BB_OK;
+}
+
+int bb_refill_values_ext(bb_env* env, const uint64_t* d_stream, const bb_eval_weights* d_w, int64_t w_stride,
+                         int32_t depth, int32_t deals, uint64_t seed, const bb_refill_values_out* out, void* stream) {
+  (void)stream;
+  if (!env) return BB_ERR_ARG;
+  if (int rc = refused(env, "bb_refill_values_ext", R::refill_values_ext(d_w, w_stride, depth, deals, out))) return rc;
+  refill_values_ext_host(env->board.data(), env->combo.data(), d_stream, env->n, d_w, w_stride, depth, deals, seed,
+                         *out);
   return BB_OK;
 }
 

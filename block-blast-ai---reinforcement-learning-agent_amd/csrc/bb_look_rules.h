@@ -1,4 +1,4 @@
-// bb_look_rules.h -- the argument rules of the twenty-three lookahead entry points of include/bbvec.h, one copy for
+// bb_look_rules.h -- the argument rules of the twenty-seven lookahead entry points of include/bbvec.h, one copy for
 // both backends (csrc/bb_capi.cpp and csrc/bb_host.cpp).  Plain C++, nothing from HIP.
 //
 // Each function returns the rule an argument set breaks, as the text that follows "<entry point>: " in
@@ -8,7 +8,8 @@
 // Asymmetries that are part of the ABI as it stands: bb_afterstates_pos, bb_greedy_actions(_each)_pos and
 // bb_plan_actions(_each)_pos refuse n == 0 and answer every broken rule with one text; bb_plan_values_pos accepts n == 0
 // (and does nothing) and names the rule that broke, and so do bb_safe_mask_pos, bb_refill_census_pos,
-// bb_refill_values_pos, bb_play_plan_pos, bb_board_terms_pos and bb_plan_actions_ext_pos.
+// bb_refill_values_pos, bb_play_plan_pos, bb_board_terms_pos, bb_plan_actions_ext_pos, bb_plan_values_ext_pos and
+// bb_refill_values_ext_pos.
 #pragma once
 #include <stdint.h>
 
@@ -155,6 +156,41 @@ inline const char* plan_actions_ext_pos(const bb_positions* pos, int32_t n, cons
   if (no_positions(pos)) return "positions (board, hand) are NULL";
   if (n < 0) return "n is negative";
   return plan_actions_ext(d_w, w_stride, depth, out);
+}
+
+// the per-action values and the dealt next-hand values with the shape terms: the rules of bb_plan_values /
+// bb_refill_values with "weight rows" for "weights", and the stride rule of bb_plan_actions_ext
+inline const char* plan_values_ext(const bb_eval_weights* d_w, int64_t w_stride, int32_t depth,
+                                   const bb_plan_values_out* out) {
+  if (!d_w) return "weight rows are NULL";
+  if (w_stride != 0 && w_stride != 1) return "w_stride must be 0 or 1";
+  if (!out) return "out is NULL";
+  if (!out->q && !out->rest && !out->leaves && !out->safe) return "all four outputs are NULL";
+  if (bad_depth(depth)) return "depth must be 1..3";
+  return nullptr;
+}
+inline const char* plan_values_ext_pos(const bb_positions* pos, int32_t n, const bb_eval_weights* d_w,
+                                       int64_t w_stride, int32_t depth, const bb_plan_values_out* out) {
+  if (no_positions(pos)) return "positions (board, hand) are NULL";
+  if (n < 0) return "n is negative";
+  return plan_values_ext(d_w, w_stride, depth, out);
+}
+inline const char* refill_values_ext(const bb_eval_weights* d_w, int64_t w_stride, int32_t depth, int32_t deals,
+                                     const bb_refill_values_out* out) {
+  if (!d_w) return "weight rows are NULL";
+  if (w_stride != 0 && w_stride != 1) return "w_stride must be 0 or 1";
+  if (!out) return "out is NULL";
+  if (!out->hand && !out->value && !out->attempts) return "all three outputs are NULL";
+  if (bad_depth(depth)) return "depth must be 1..3";
+  if (deals < 1 || deals > BB_REFILL_MAX_DEALS) return "deals must be 1..1024";
+  return nullptr;
+}
+inline const char* refill_values_ext_pos(const uint64_t* board, int32_t n, const bb_eval_weights* d_w,
+                                         int64_t w_stride, int32_t depth, int32_t deals,
+                                         const bb_refill_values_out* out) {
+  if (!board) return "board is NULL";
+  if (n < 0) return "n is negative";
+  return refill_values_ext(d_w, w_stride, depth, deals, out);
 }
 
 }  // namespace bb_look_rules

@@ -649,6 +649,86 @@ plan_values_kernel(LookTable t, LookPos pos, int n, bb_greedy_weights w, int dep
   }
 }
 
+// plan_values_kernel's search of one position up to the barrier before the stores, restated as a template over the
+// weight type for plan_values_ext_kernel's two sides: the ply-1 staging, the compaction, the record turns with their
+// fresh accumulators, the wave join and the ballot.  Both barriers of plan_compact are inside; the stores and the two
+// barriers around them are the kernel's.  plan_values_kernel keeps its own text, as plan_kernel does beside
+// plan_search: called through this template it no longer compiled to its listing (54 -> 57 VGPRs;
+// profiles/values_ext/isa_compare.txt).
+template <class W>
+__device__ __forceinline__ void plan_values_search(const LookTable& t, const Position& P, const W& w, int depth,
+                                                   int wave, int cell, PlanRecord* s_rec, int* s_cnt, int64_t* s_q,
+                                                   int32_t* s_rest, int32_t* s_leaves, uint8_t* s_safe) {
+  // ---- ply 1: threadIdx.x is the action of waves 0..2.  A lane that is not open (illegal, or a sequence of
+  // one move) fills its staging entry, then the open ones are compacted
+  const Ply1 ply1 = plan_ply1(t, P, depth, wave, cell);
+  if (wave < kHand && !ply1.open) {
+    s_q[threadIdx.x] = ply1.closed ? move_terms(w, ply1.a) + state_terms(w, ply1.a) : INT64_MIN;
+    s_rest[threadIdx.x] = ply1.closed ? (int32_t)kRestNone : -1;
+    s_leaves[threadIdx.x] = ply1.closed ? 1 : 0;
+    s_safe[threadIdx.x] = (uint8_t)(ply1.closed && !ply1.a.dead);
+  }
+  const int total = plan_compact(s_rec, s_cnt, w, ply1, wave, cell);
+
+  // ---- ply 2 (and 3): one record = one first move per wave and turn, the accumulators fresh for each
+  for (int r = wave; r < total; r += kPlanWaves) {
+    int64_t best = INT64_MIN;  // below every legal value (see greedy_kernel)
+    uint32_t best_key = kPlanNoKey;
+    int leaves = 0;
+    bool alive = false;  // a leaf with dead == 0
+    const int act1 = plan_record_turn<true>(t, s_rec[r], P.hand, w, depth, cell, best, best_key, leaves, alive);
+    // the record's turn ends: join the lanes (the whole wave is here, the loops of the turn are wave-uniform)
+    plan_wave_join(best, best_key, leaves);
+    const bool any_alive = __ballot(alive) != 0ull;
+    if (cell == 0) {  // an open record has a leaf: its afterstate is not dead.  act1 indexes the staging arrays
+      s_q[act1] = best;
+      s_rest[act1] = (int32_t)(((best_key >> 8) & 0xFFu) | ((best_key & 0xFFu) << 8));
+      s_leaves[act1] = leaves;
+      s_safe[act1] = (uint8_t)any_alive;
+    }
+  }
+}
+
+// plan_values_kernel under rows of bb_eval_weights (bbvec.h bb_plan_values_ext): position i takes
+// rows[i * w_stride], w_stride 0 or 1, read inside the position loop into scalar registers.  Two sides, as
+// plan_ext_kernel: a row whose four shape weights are 0 takes the eight-weight instantiation under w.base, any
+// other the twelve-weight one.  Every wave reads the same row, so the branch is the workgroup's, and both sides
+// meet the same barriers (the two of plan_compact); the barrier before the stores and the one at the end of a
+// position are outside the branch.  The same LDS, trip bounds and grid cap as plan_values_kernel.
+__global__ void __launch_bounds__(kPlanBlock)
+plan_values_ext_kernel(LookTable t, LookPos pos, int n, const bb_eval_weights* __restrict__ rows, int64_t w_stride,
+                       int depth, bb_plan_values_out out) {
+  __shared__ PlanRecord s_rec[kPlanRecords];
+  __shared__ int s_cnt[kHand];
+  __shared__ int64_t s_q[BB_ACTIONS];
+  __shared__ int32_t s_rest[BB_ACTIONS];
+  __shared__ int32_t s_leaves[BB_ACTIONS];
+  __shared__ uint8_t s_safe[BB_ACTIONS];
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int cell = (int)(threadIdx.x & 63u);
+  for (int64_t i = blockIdx.x; i < (int64_t)n; i += gridDim.x) {
+    const Position P = load_position(pos, i);
+    const bb_eval_weights w = load_eval_weights(rows, i * w_stride);
+    const bool shaped = (w.perimeter | w.room3 | w.room5 | w.fits) != 0;  // scalar: one answer for the workgroup
+    if (shaped)
+      plan_values_search(t, P, w, depth, wave, cell, s_rec, s_cnt, s_q, s_rest, s_leaves, s_safe);
+    else
+      plan_values_search(t, P, w.base, depth, wave, cell, s_rec, s_cnt, s_q, s_rest, s_leaves, s_safe);
+    __syncthreads();
+
+    // ---- store the rows: thread = action
+    if (wave < kHand) {
+      const int64_t o = i * BB_ACTIONS + (int64_t)threadIdx.x;
+      if (out.q) out.q[o] = s_q[threadIdx.x];
+      if (out.rest) out.rest[o] = s_rest[threadIdx.x];
+      if (out.leaves) out.leaves[o] = s_leaves[threadIdx.x];
+      const uint64_t safe = __ballot(s_safe[threadIdx.x] != 0);
+      if (out.safe && cell == 0) out.safe[i * kHand + wave] = safe;
+    }
+    __syncthreads();  // the staging arrays are rewritten by the first lanes to reach the workgroup's next position
+  }
+}
+
 // ---------------------------------------------------------------------------
 // The hand-safe mask alone (bbvec.h bb_safe_mask): plan_values_kernel's safe words of depth >= 2 by an existence
 // search.  No values, so no weights, no combo, no record list: after first move a, can the rest of the hand still
@@ -871,6 +951,118 @@ refill_values_kernel(LookTable t, RefillCols cols, int n, int m, bb_greedy_weigh
   }
 }
 
+// refill_values_kernel's two halves restated for refill_values_ext_kernel; the parent keeps its own text for the
+// reason given at plan_values_search (49 -> 52 VGPRs when it called these).
+// The deal of pair (board B, stream idx, deal j): the hand's ids and the attempts (negative: nothing accepted).  The
+// one barrier per round is met by the whole workgroup.  No weights are read, so this half is no template.
+__device__ __forceinline__ void refill_deal(const LookTable& t, uint64_t B, uint64_t seed, uint64_t idx, uint32_t j,
+                                            int wave, int cell, uint32_t (*s_deal)[kPlanWaves], uint32_t& ids,
+                                            int& attempts) {
+  ids = 0u;
+  attempts = -kMaxAttempts;
+#pragma unroll 1
+  for (int r = 0; r < kRefillRounds; ++r) {
+    uint32_t wd[4];
+    philox_words(seed, idx, ((uint64_t)j << 7) | (uint64_t)(r * kPlanWaves + wave), wd);
+    const uint32_t a = uniform32((uint32_t)(((uint64_t)wd[0] * (uint32_t)kPieces) >> 32));
+    const uint32_t b = uniform32((uint32_t)(((uint64_t)wd[1] * (uint32_t)kPieces) >> 32));
+    const uint32_t c = uniform32((uint32_t)(((uint64_t)wd[2] * (uint32_t)kPieces) >> 32));
+    const uint32_t h = hand_pack(a, b, c, 0u, false, false);
+    const bool ok = hand_fits(t, B, h, cell);
+    if (cell == 0) s_deal[r & 1][wave] = h | (ok ? kRefillAccepted : 0u);
+    __syncthreads();  // the other buffer is rewritten only after the next round's barrier: every wave has read this one
+    const uint32_t d0 = uniform32(s_deal[r & 1][0]), d1 = uniform32(s_deal[r & 1][1]);
+    const uint32_t d2 = uniform32(s_deal[r & 1][2]), d3 = uniform32(s_deal[r & 1][3]);
+    const int k = (d0 & kRefillAccepted) ? 0 : (d1 & kRefillAccepted) ? 1 : (d2 & kRefillAccepted) ? 2 : 3;
+    const uint32_t dk = k == 0 ? d0 : (k == 1 ? d1 : (k == 2 ? d2 : d3));
+    ids = dk & kHandIds;  // the round's first accepted draw, else its last one (the 100th in the last round)
+    if (dk & kRefillAccepted) {
+      attempts = r * kPlanWaves + k + 1;
+      break;  // the same four words in every wave: the workgroup leaves together
+    }
+  }
+}
+
+// The search of the dealt hand under either weight type (refill_values_ext_kernel's two sides): plan_kernel's body up
+// to the wave join, the value alone kept.  Both barriers of plan_compact are inside.
+template <class W>
+__device__ __forceinline__ int64_t refill_search(const LookTable& t, const Position& P, const W& w, int depth, int wave,
+                                                 int cell, PlanRecord* s_rec, int* s_cnt) {
+  int64_t best = INT64_MIN;  // below every legal value (see greedy_kernel)
+  uint32_t best_key = kPlanNoKey;
+  int leaves = 0;
+  bool unused = false;
+  const Ply1 ply1 = plan_ply1(t, P, depth, wave, cell);
+  if (ply1.closed) {
+    best = move_terms(w, ply1.a) + state_terms(w, ply1.a);
+    best_key = ((uint32_t)(wave * 64 + cell) << 16) | 0xFFFFu;
+  }
+  const int total = plan_compact(s_rec, s_cnt, w, ply1, wave, cell);
+  for (int r = wave; r < total; r += kPlanWaves)
+    plan_record_turn<false>(t, s_rec[r], P.hand, w, depth, cell, best, best_key, leaves, unused);
+  plan_wave_join(best, best_key, leaves);
+  return best;
+}
+
+// refill_values_kernel under rows of bb_eval_weights (bbvec.h bb_refill_values_ext): every deal of board i is searched
+// under rows[i * w_stride], w_stride 0 or 1, read inside the pair loop into scalar registers.  The deal reads no
+// weights and is the parent's.  The search has plan_ext_kernel's two sides; the branch is the workgroup's (every wave
+// read the same row) and both sides meet the two barriers of plan_compact.  A hand without a legal first move gets
+// w.base.dead alone: there is no afterstate whose board the shape terms could read.
+__global__ void __launch_bounds__(kPlanBlock)
+refill_values_ext_kernel(LookTable t, RefillCols cols, int n, int m, const bb_eval_weights* __restrict__ rows,
+                         int64_t w_stride, int depth, uint64_t seed, bb_refill_values_out out) {
+  __shared__ PlanRecord s_rec[kPlanRecords];
+  __shared__ int s_cnt[kHand];
+  __shared__ int64_t s_v[kPlanWaves];
+  __shared__ uint32_t s_deal[2][kPlanWaves];
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int cell = (int)(threadIdx.x & 63u);
+  const uint32_t um = (uint32_t)m;                                   // 1..1024
+  const uint32_t gi = gridDim.x / um, gj = gridDim.x - gi * um;      // the stride in (i, j)
+  int64_t i = (int64_t)(blockIdx.x / um);
+  uint32_t j = blockIdx.x - (uint32_t)i * um;
+  while (i < (int64_t)n) {
+    const uint64_t B = uniform64(cols.board[i]);
+    const int combo = (int)uniform32(cols.combo ? (uint32_t)cols.combo[i] : 0u);
+    const uint64_t idx = cols.stream ? uniform64(cols.stream[i]) : (uint64_t)i;
+    const bb_eval_weights w = load_eval_weights(rows, i * w_stride);  // every deal of board i: board i's row
+    const bool shaped = (w.perimeter | w.room3 | w.room5 | w.fits) != 0;  // scalar: one answer for the workgroup
+
+    // ---- the deal
+    uint32_t ids;
+    int attempts;
+    refill_deal(t, B, seed, idx, j, wave, cell, s_deal, ids, attempts);
+
+    // ---- the search of the dealt hand (plan_kernel's body)
+    const Position P{B, ids, combo};
+    int64_t best;
+    if (shaped)
+      best = refill_search(t, P, w, depth, wave, cell, s_rec, s_cnt);
+    else
+      best = refill_search(t, P, w.base, depth, wave, cell, s_rec, s_cnt);
+    if (cell == 0) s_v[wave] = best;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+      for (int k = 1; k < kPlanWaves; ++k) best = s_v[k] > best ? s_v[k] : best;
+      const int64_t o = i * (int64_t)m + (int64_t)j;
+      if (out.hand) out.hand[o] = ids;
+      if (out.value) out.value[o] = best == INT64_MIN ? (int64_t)w.base.dead : best;  // no legal first move
+      if (out.attempts) out.attempts[o] = attempts;
+    }
+    // no barrier here: the next pair's first LDS writes are s_deal, s_cnt and s_rec; s_v is rewritten only after
+    // barriers that thread 0 has to reach first
+
+    j += gj;
+    i += (int64_t)gi;
+    if (j >= um) {
+      j -= um;
+      ++i;
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------
 // A plan played to its leaf (bbvec.h bb_play_plan_pos): one lane per position, up to three one-ply moves
 // (eval_action, the move of every kernel above).  The pieces differ from lane to lane, so the table is copied into
@@ -1009,6 +1201,16 @@ hipError_t launch_plan_values(const uint64_t* board, const uint32_t* hand, const
   return hipGetLastError();
 }
 
+hipError_t launch_plan_values_ext(const uint64_t* board, const uint32_t* hand, const int32_t* combo, int n,
+                                  const bb_eval_weights* rows, int64_t w_stride, int depth,
+                                  const bb_plan_values_out& out, hipStream_t s) {
+  const LookPos pos{board, hand, combo, nullptr};
+  if (depth == 3 && !out.q && !out.rest && !out.leaves) depth = 2;  // as launch_plan_values
+  hipLaunchKernelGGL(plan_values_ext_kernel, plan_grid(n), dim3(kPlanBlock), 0, s, look_table(), pos, n, rows, w_stride,
+                     depth, out);
+  return hipGetLastError();
+}
+
 hipError_t launch_safe_mask(const uint64_t* board, const uint32_t* hand, int n, int mode, uint64_t* mask,
                             hipStream_t s) {
   const LookPos pos{board, hand, nullptr, nullptr};
@@ -1026,6 +1228,17 @@ hipError_t launch_refill_values(const uint64_t* board, const int32_t* combo, con
   const dim3 grid((unsigned)(pairs < kRefillMaxGrid ? pairs : kRefillMaxGrid));
   hipLaunchKernelGGL(refill_values_kernel, grid, dim3(kPlanBlock), 0, s, look_table(), cols, n, deals, w, depth, seed,
                      out);
+  return hipGetLastError();
+}
+
+hipError_t launch_refill_values_ext(const uint64_t* board, const int32_t* combo, const uint64_t* stream_id, int n,
+                                    const bb_eval_weights* rows, int64_t w_stride, int depth, int deals, uint64_t seed,
+                                    const bb_refill_values_out& out, hipStream_t s) {
+  const RefillCols cols{board, combo, stream_id};
+  const int64_t pairs = (int64_t)n * deals;
+  const dim3 grid((unsigned)(pairs < kRefillMaxGrid ? pairs : kRefillMaxGrid));
+  hipLaunchKernelGGL(refill_values_ext_kernel, grid, dim3(kPlanBlock), 0, s, look_table(), cols, n, deals, rows,
+                     w_stride, depth, seed, out);
   return hipGetLastError();
 }
 

@@ -273,12 +273,16 @@ def main() -> None:
         agent.load(args.checkpoint)
         print(f"Loaded model from {args.checkpoint}")
     else:
-        from agents.greedy import GreedyAgent, HandPlanAgent, RandomAgent, TwoHandPlanAgent
+        from agents.greedy import GreedyAgent, HandPlanAgent, RandomAgent, two_hand_agent_class
 
         if args.agent == "plan":
             agent = HandPlanAgent(device=args.device)
         elif args.agent == "plan2":
-            agent = TwoHandPlanAgent(seed=args.seed, device=args.device)
+            named = None
+            if args.weights:  # a file that names a shape weight other than 0 is played by TwoHandShapeAgent
+                with open(args.weights) as f:
+                    named = json.load(f).get("weights")
+            agent = two_hand_agent_class(named)(seed=args.seed, device=args.device)
         else:
             agent = (GreedyAgent(device=args.device) if args.agent == "greedy"
                      else RandomAgent(device=args.device, safe=args.safe_mask))

@@ -183,12 +183,13 @@ def compare_two_hand(weight_dicts: Sequence[Dict[str, int]], games: int, moves: 
                      candidates: int = 8, deals: int = 16, device=None, census: bool = False) -> List[dict]:
     """``compare`` with every weight set played by a ``TwoHandPlanAgent(depth, candidates, deals)`` (``--agent
     plan2``): the same games (seeds seed + g) and the same records.  The agent takes one weight set, so the sets are
-    played one after another, ``games`` envs each, and every agent's deals are keyed by ``seed``."""
-    from agents.greedy import TwoHandPlanAgent
+    played one after another, ``games`` envs each, and every agent's deals are keyed by ``seed``.  A set that names a
+    shape weight other than 0 is played by a ``TwoHandShapeAgent``."""
+    from agents.greedy import two_hand_agent_class
 
     rows = []
     for w in weight_dicts:
-        agent = TwoHandPlanAgent(w, depth=depth, candidates=candidates, deals=deals, seed=seed, device=device)
+        agent = two_hand_agent_class(w)(w, depth=depth, candidates=candidates, deals=deals, seed=seed, device=device)
         rows.append(evaluate_agent(agent, num_episodes=int(games), seeds=[seed + g for g in range(int(games))],
                                    max_moves=int(moves), **({"census": True} if census else {})))
     scores = torch.tensor([r["scores"] for r in rows], dtype=torch.int64)

@@ -411,6 +411,35 @@ class DeviceEnvBatch:
                 "bb_refill_values", self.handle, self.lib)
         return out
 
+    def plan_values_ext(self, rows: torch.Tensor, depth: int = 3, out: Optional[dict] = None) -> dict:
+        """bb_plan_values_ext on the live state: ``plan_values`` with the shape terms in every sequence's value.
+        rows: int32 [1, 12] (one row for all envs) or [N, 12] on this device (``runtime.kernels.eval_rows``), read
+        when the launch runs.  ``out`` as ``plan_values``.  Reads the state and changes nothing."""
+        from . import kernels as K
+
+        out = K.plan_value_outputs(self.num_envs, self.device) if out is None else out
+        o = K._plan_values_out(out, self.num_envs, self.device)
+        stride = K._eval_rows("plan_values_ext", rows, self.num_envs, self.device)
+        L.check(self.lib.bb_plan_values_ext(self.handle, _ptr(rows), stride, int(depth), C.byref(o),
+                                            _stream(self.device)),
+                "bb_plan_values_ext", self.handle, self.lib)
+        return out
+
+    def refill_values_ext(self, rows: torch.Tensor, deals: int, seed: int, stream: Optional[torch.Tensor] = None,
+                          depth: int = 3, want=("value",), out: Optional[dict] = None) -> dict:
+        """bb_refill_values_ext on the live boards and combos: ``refill_values`` with the shape terms in every dealt
+        hand's value, every deal of env i under rows[i] (or the one shared row).  Reads the state and changes
+        nothing, the piece stream included."""
+        from . import kernels as K
+
+        K._refill_column("stream", stream, torch.int64, self.num_envs, self.device)
+        out, o = K._refill_values_args(deals, depth, out, self.num_envs, self.device, want)
+        stride = K._eval_rows("refill_values_ext", rows, self.num_envs, self.device)
+        L.check(self.lib.bb_refill_values_ext(self.handle, _ptr(stream), _ptr(rows), stride, depth, deals,
+                                              int(seed) & (2 ** 64 - 1), C.byref(o), _stream(self.device)),
+                "bb_refill_values_ext", self.handle, self.lib)
+        return out
+
     # ------------------------------------------------------------ host copies
     def state(self) -> dict:
         n = self.num_envs

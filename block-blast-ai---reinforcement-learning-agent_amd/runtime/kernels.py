@@ -457,6 +457,25 @@ def plan_values(board: torch.Tensor, hand: torch.Tensor, weights, depth: int = 3
     return out
 
 
+def plan_values_ext(board: torch.Tensor, hand: torch.Tensor, rows: torch.Tensor, depth: int = 3,
+                    combo: Optional[torch.Tensor] = None, prev: Optional[torch.Tensor] = None,
+                    want=("q", "rest", "leaves", "safe"), out: Optional[dict] = None) -> dict:
+    """bb_plan_values_ext_pos: ``plan_values`` with the shape terms (perimeter, room3, room5, fits of the last
+    afterstate's board) added to every sequence's value.  rows: int32 [1, 12] (one row for all positions) or
+    [n, 12] (position i takes rows[i]), ``eval_rows``, where the positions are; they are read when the launch runs.
+    With the four shape weights 0 in a row the outputs of that position are those of ``plan_values`` under the
+    first eight columns.  ``prev`` is checked like the other columns and not read.  Outputs, ``want`` and ``out``
+    are ``plan_values``'."""
+    pos, n, dev = _positions(board, hand, combo, prev)
+    stride = _eval_rows("plan_values_ext", rows, n, dev)
+    out = plan_value_outputs(n, dev, want) if out is None else out
+    o = _plan_values_out(out, n, dev)
+    lib, stream = _look_lib(dev)
+    L.check(lib.bb_plan_values_ext_pos(C.byref(pos), n, _p(rows), stride, int(depth), C.byref(o), stream),
+            "bb_plan_values_ext_pos", lib=lib)
+    return out
+
+
 SAFE_WORDS, SAFE_OR_LEGAL = 0, 1  # bbvec.h BB_SAFE_WORDS / BB_SAFE_OR_LEGAL
 
 
@@ -593,6 +612,30 @@ def refill_values(board: torch.Tensor, weights, deals: int, seed: int, combo: Op
     lib, s = _look_lib(dev)
     L.check(lib.bb_refill_values_pos(_p(board), _p(combo), _p(stream), n, C.byref(w), depth, deals,
                                      int(seed) & (2 ** 64 - 1), C.byref(o), s), "bb_refill_values_pos", lib=lib)
+    return out
+
+
+def refill_values_ext(board: torch.Tensor, rows: torch.Tensor, deals: int, seed: int,
+                      combo: Optional[torch.Tensor] = None, stream: Optional[torch.Tensor] = None, depth: int = 3,
+                      want=("value",), out: Optional[dict] = None) -> dict:
+    """bb_refill_values_ext_pos: ``refill_values`` with the shape terms in the value of every dealt hand.  rows:
+    int32 [1, 12] (one row for all boards) or [n, 12] (every deal of board i takes rows[i]), ``eval_rows``, where
+    the boards are.  "hand" and "attempts" are ``refill_values``' bit for bit; "value" is ``plan_actions_ext``'s
+    for (board i, that hand, combo[i]), and the row's ``dead`` alone for a hand with no legal first move."""
+    if not (isinstance(board, torch.Tensor) and board.dtype == torch.int64 and board.dim() == 1
+            and board.is_contiguous()):
+        raise L.BBNativeError("refill_values_ext: board must be a contiguous torch.int64 tensor of shape [n]")
+    n, dev = board.numel(), board.device
+    _refill_column("combo", combo, torch.int32, n, dev)
+    _refill_column("stream", stream, torch.int64, n, dev)
+    stride = _eval_rows("refill_values_ext", rows, n, dev)
+    out, o = _refill_values_args(deals, depth, out, n, dev, want)
+    if n == 0:  # an empty tensor has no storage to point at; the entry point would do nothing either
+        return out
+    lib, s = _look_lib(dev)
+    L.check(lib.bb_refill_values_ext_pos(_p(board), _p(combo), _p(stream), n, _p(rows), stride, depth, deals,
+                                         int(seed) & (2 ** 64 - 1), C.byref(o), s), "bb_refill_values_ext_pos",
+            lib=lib)
     return out
 
 

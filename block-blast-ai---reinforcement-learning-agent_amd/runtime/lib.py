@@ -286,6 +286,12 @@ SIGNATURES = {
     "bb_refill_values_pos": (C.c_int, [_P, _P, _P, _I32, C.POINTER(GreedyWeights), _I32, _I32, _U64,
                                        C.POINTER(RefillValuesOut), _P]),
     "bb_refill_values": (C.c_int, [_P, _P, C.POINTER(GreedyWeights), _I32, _I32, _U64, C.POINTER(RefillValuesOut), _P]),
+    "bb_plan_values_ext_pos": (C.c_int, [C.POINTER(Positions), _I32, _P, C.c_int64, _I32, C.POINTER(PlanValuesOut),
+                                         _P]),
+    "bb_plan_values_ext": (C.c_int, [_P, _P, C.c_int64, _I32, C.POINTER(PlanValuesOut), _P]),
+    "bb_refill_values_ext_pos": (C.c_int, [_P, _P, _P, _I32, _P, C.c_int64, _I32, _I32, _U64,
+                                           C.POINTER(RefillValuesOut), _P]),
+    "bb_refill_values_ext": (C.c_int, [_P, _P, _P, C.c_int64, _I32, _I32, _U64, C.POINTER(RefillValuesOut), _P]),
     "bb_play_plan_pos": (C.c_int, [C.POINTER(Positions), _I32, _P, C.POINTER(PlayPlanOut), _P]),
     "bb_masked_sample": (C.c_int, [_P, _P, _I32, _P, _U64, _U64, _U64, _I32, _P, _P, _P, _P, _P]),
     "bb_masked_sample_dstep": (C.c_int, [_P, _P, _I32, _U64, _P, _U64, _U64, _I32, _P, _P, _P, _P]),
@@ -354,6 +360,7 @@ HOST_SYMBOLS = ("bb_abi_version", "bb_build_id", "bb_create", "bb_destroy", "bb_
                 "bb_board_terms_pos", "bb_board_terms", "bb_plan_actions_ext_pos", "bb_plan_actions_ext",
                 "bb_plan_values_pos", "bb_plan_values", "bb_safe_mask_pos", "bb_safe_mask",
                 "bb_refill_census_pos", "bb_refill_census", "bb_refill_values_pos", "bb_refill_values",
+                "bb_plan_values_ext_pos", "bb_plan_values_ext", "bb_refill_values_ext_pos", "bb_refill_values_ext",
                 "bb_play_plan_pos")
 
 _lib = None

@@ -278,6 +278,8 @@ def train(config: Dict[str, Any], resume_path: Optional[str] = None, seed: int =
     # on from those weights (the iterations of this call are counted: a resumed run distils again).  tau is in the
     # units of the values: the default is half a cleared line under the default weights, a hyper-parameter nobody
     # has tuned.
+    # `weights` may name the shape terms (perimeter, room3, room5, fits): when one is not 0 the labels come from
+    # bb_plan_values_ext_pos (PPOAgent.search_labeller); the same holds for training.guide.weights.
     distill_cfg = train_cfg.get("distill") or {}
     distill_updates = int(distill_cfg.get("updates", 0))
     # training.distill.value_coef (default 0: the path above): when above 0 the distillation iterations run the

@@ -70,7 +70,9 @@ extern "C" {
                                  with bb_play_plan_pos: a plan played to its leaf position;
                                  (additive, still 9) bb_eval_weights with bb_board_terms(_pos) and
                                  bb_plan_actions_ext(_pos): four shape terms of a board (perimeter, room3, room5,
-                                 fits) and the full-hand search with them added to every leaf's value */
+                                 fits) and the full-hand search with them added to every leaf's value;
+                                 (additive, still 9) bb_plan_values_ext(_pos) and bb_refill_values_ext(_pos): the
+                                 per-action values and the dealt next-hand values under rows of bb_eval_weights */
 
 #define BB_OK 0
 #define BB_ERR_ARG (-1)
@@ -605,6 +607,46 @@ int bb_refill_values_pos(const uint64_t* d_board, const int32_t* d_combo /* NULL
 /* the same for the handle's live boards and combos ([N][m] outputs) */
 int bb_refill_values(bb_env* env, const uint64_t* d_stream, const bb_greedy_weights* w, int32_t depth,
                      int32_t deals, uint64_t seed, const bb_refill_values_out* out, void* stream);
+
+/* ---- per-action values and dealt next-hand values with the shape terms ---------------
+ * bb_plan_values and bb_refill_values under rows of bb_eval_weights, as bb_plan_actions_ext
+ * is to bb_plan_actions.  d_w are rows of twelve int32 in the struct's field order, in the
+ * memory of the position columns (device memory for libbbvec.so, host memory for
+ * libbbvec_host.so), read when the launch runs.  w_stride 0: every position (board) uses
+ * d_w[0]; 1: position (board) i uses d_w[i]; any other value is refused.
+ *
+ * bb_plan_values_ext: q, rest, leaves and safe as bb_plan_values defines them, with the
+ * value of a maximal sequence gaining
+ *   w.perimeter*perimeter(B_k) + w.room3*room3(B_k) + w.room5*room5(B_k) + w.fits*fits(B_k)
+ * for B_k the board of its last afterstate after the clears, at dead and refill leaves
+ * alike, a sequence that ends at ply 1 included.  safe and leaves do not depend on the
+ * row.  With the same row and depth, bb_plan_actions_ext's value is max_a q, its action
+ * the lowest a attaining it, its plan[1:] the decoded rest[action] and its leaves the sum
+ * of leaves over a.
+ *
+ * bb_refill_values_ext: hand and attempts are bit for bit bb_refill_values' (the deal reads
+ * no weights); every deal of board i is searched under board i's row, and value is what
+ * bb_plan_actions_ext_pos returns for (board i, that hand, combo[i]).  A dealt hand with no
+ * legal first move gets (int64)w.base.dead and nothing else: there is no afterstate whose
+ * board the terms could read.
+ *
+ * With the four shape weights 0 in a row the answers for that position (board) are those
+ * of bb_plan_values(_pos) / bb_refill_values(_pos) under `base`.  Refusals (BB_ERR_ARG, the
+ * rule named in bb_last_error, before any HIP call) are those of bb_plan_values /
+ * bb_refill_values with "weight rows" for "weights", plus a w_stride that is not 0 or 1;
+ * n == 0 does nothing.  The handle forms read the live columns, change nothing, the RNG
+ * included, and refuse a handle in BB_ERR_DEVICE / BB_ERR_STATE.  One launch, integers
+ * only, asynchronous, no allocation, no sync (graph-capturable from the first call);
+ * indexing is 64-bit. */
+int bb_plan_values_ext_pos(const bb_positions* pos, int32_t n, const bb_eval_weights* d_w, int64_t w_stride,
+                           int32_t depth, const bb_plan_values_out* out, void* stream);
+int bb_plan_values_ext(bb_env* env, const bb_eval_weights* d_w, int64_t w_stride, int32_t depth,
+                       const bb_plan_values_out* out, void* stream);
+int bb_refill_values_ext_pos(const uint64_t* d_board, const int32_t* d_combo, const uint64_t* d_stream, int32_t n,
+                             const bb_eval_weights* d_w, int64_t w_stride, int32_t depth, int32_t deals,
+                             uint64_t seed, const bb_refill_values_out* out, void* stream);
+int bb_refill_values_ext(bb_env* env, const uint64_t* d_stream, const bb_eval_weights* d_w, int64_t w_stride,
+                         int32_t depth, int32_t deals, uint64_t seed, const bb_refill_values_out* out, void* stream);
 
 /* ---- a plan played to its leaf ------------------------------------------------------
  * Plays d_plan[i][0..2] from position i with the one-ply move of bb_afterstates
