@@ -377,6 +377,61 @@ class PopulationPlanAgent(BaseAgent):
         raise NotImplementedError("a population has no single weights file; load a HandPlanAgent")
 
 
+class PopulationTwoHandAgent(BaseAgent):
+    """One two-hand agent per env, each with weights of its own, decided in one ``bb_plan2_values`` call per move: no
+    host read, no torch arithmetic, one cached workspace.  ``rows``: int32 [N, 12] (or [1, 12] for one shared set) in
+    the order of ``L.EVAL_FIELDS`` (``runtime.kernels.eval_rows``); they are moved to the agent's device.  ``stream``:
+    int64 [N] stream ids of the deals (None: env i draws from stream i); envs given the same id meet the same dealt
+    hands.  The deals of move t are keyed by ``TwoHandPlanAgent.deal_seed(seed, t)``.  With every row equal to one
+    weight set and ``stream=None`` it plays move for move what ``two_hand_agent_class(w)(w, depth, candidates, deals,
+    seed)`` plays.  Only ``act_env`` is offered, as with ``PopulationPlanAgent``."""
+
+    def __init__(self, rows: torch.Tensor, depth: int = 3, candidates: int = 8, deals: int = 16, seed: int = 0,
+                 stream: Optional[torch.Tensor] = None, device=None):
+        from runtime.device_env import resolve_device
+
+        super().__init__(resolve_device(device))
+        if int(depth) not in (1, 2, 3):
+            raise ValueError(f"depth must be 1, 2 or 3, not {depth}")
+        if not 1 <= int(candidates) <= 192:
+            raise ValueError(f"candidates must be 1..192, not {candidates}")
+        if not 1 <= int(deals) <= L.BB_REFILL_MAX_DEALS:
+            raise ValueError(f"deals must be 1..{L.BB_REFILL_MAX_DEALS}, not {deals}")
+        if not (isinstance(rows, torch.Tensor) and rows.dim() == 2 and rows.shape[1] == len(L.EVAL_FIELDS)):
+            raise ValueError(f"rows must be an int32 [N, {len(L.EVAL_FIELDS)}] tensor (runtime.kernels.eval_rows)")
+        self.depth, self.candidates, self.deals, self.seed = int(depth), int(candidates), int(deals), int(seed)
+        self.rows = rows.to(self.device).contiguous()
+        self.stream = None if stream is None else stream.to(self.device).contiguous()
+        self.moves = 0  # decisions made so far: mixed into the deals' seed
+        self._work = None
+
+    def act_env(self, env_batch, out: torch.Tensor) -> torch.Tensor:
+        """The action of every env of a ``DeviceEnvBatch`` into out (int32 [N]); one decision of the move counter."""
+        from runtime import kernels as K
+
+        if self._work is None or self._work[0] != env_batch.num_envs or self._work[1].device != env_batch.device:
+            need = K.plan2_work_bytes(env_batch.num_envs, self.candidates, self.deals,
+                                      host=env_batch.device.type == "cpu")
+            self._work = (env_batch.num_envs, torch.empty(max(need, 8), dtype=torch.uint8, device=env_batch.device))
+        env_batch.plan2_values(self.rows, self.candidates, self.deals, TwoHandPlanAgent.deal_seed(self.seed, self.moves),
+                               stream=self.stream, depth=self.depth, out={"action": out}, work=self._work[1])
+        self.moves += 1
+        return out
+
+    def select_action(self, observation: Dict[str, Any], deterministic: bool = True) -> Tuple[int, Dict[str, Any]]:
+        raise NotImplementedError("PopulationTwoHandAgent plays a DeviceEnvBatch (act_env); for one game use "
+                                  "TwoHandPlanAgent / TwoHandShapeAgent")
+
+    def update(self, *args, **kwargs) -> Dict[str, float]:
+        return {}
+
+    def save(self, path: str) -> None:
+        raise NotImplementedError("a population has no single weights file; save the TwoHandPlanAgent of one row")
+
+    def load(self, path: str) -> None:
+        raise NotImplementedError("a population has no single weights file; load a TwoHandPlanAgent")
+
+
 class RandomAgent(BaseAgent):
     """Uniform random legal play: the Philox policy of ``bb_random_actions`` (bb_step_out.next_action), keyed
     by ``seed`` and counting one step per call.  ``safe=True`` (``act_env`` only) draws from the hand-safe actions

@@ -1030,12 +1030,47 @@ class PPOAgent(BaseAgent):
         return stats
 
     @staticmethod
-    def search_labeller(weights, depth: int):
+    def search_labeller(weights, depth: int, two_hand: Optional[Dict[str, int]] = None):
         """The call that labels a minibatch with the teacher's values: label(board, hand, combo, q) writes q int64
         [n, 192] in place.  Weights that name a shape term (``L.TERM_FIELDS``) other than 0 are searched by
         ``K.plan_values_ext`` under one shared row, made once where the positions are; any other weights by
-        ``K.plan_values`` under the eight, the call made before the shape terms existed."""
+        ``K.plan_values`` under the eight, the call made before the shape terms existed.
+
+        ``two_hand`` ({"candidates", "deals", "seed"}; seed defaults to 0): the two-hand teacher.  label writes
+        ``K.plan2_values``' q2 in place of q -- Q2 of the ``candidates`` best first moves, INT64_MIN for every other
+        action -- under one shared row of twelve, with a workspace kept per device and batch size, stream id = row,
+        and the deals of the labeller's t-th call keyed by ``TwoHandPlanAgent.deal_seed(seed, t)``.  The distill and
+        guided losses leave an INT64_MIN entry outside the target's support (csrc/bb_distill.hip: ``qv != INT64_MIN``;
+        ``distill_loss_torch`` in this module alike), so the teacher's distribution lives on the candidates alone and
+        no kernel changes.  Q2 is a sum over ``deals`` hands: a tau that suited q is ``deals`` times too sharp."""
         from runtime import lib as L
+
+        if two_hand is not None:
+            from agents.greedy import TwoHandPlanAgent
+
+            unknown = set(two_hand) - {"candidates", "deals", "seed"}
+            if unknown or "candidates" not in two_hand or "deals" not in two_hand:
+                raise ValueError(f"two_hand takes candidates, deals and (optionally) seed, not {sorted(two_hand)}")
+            cands, deals, seed = int(two_hand["candidates"]), int(two_hand["deals"]), int(two_hand.get("seed", 0))
+            if not 1 <= cands <= 192 or not 1 <= deals <= L.BB_REFILL_MAX_DEALS:
+                raise ValueError(f"two_hand: candidates must be 1..192 and deals 1..{L.BB_REFILL_MAX_DEALS}")
+            L.eval_weights(dict(weights))  # rejects unknown names
+            rows2, work2, calls = {}, {}, [0]
+
+            def label_two_hand(board, hand, combo, q):
+                dev, n = board.device, board.numel()
+                r = rows2.get(dev)
+                if r is None:
+                    r = rows2[dev] = K.eval_rows(dict(weights), device=dev)
+                w = work2.get((dev, n))
+                if w is None:
+                    need = K.plan2_work_bytes(n, cands, deals, host=dev.type == "cpu")
+                    w = work2[dev, n] = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
+                K.plan2_values(board, hand, r, cands, deals, TwoHandPlanAgent.deal_seed(seed, calls[0]), combo=combo,
+                               depth=depth, out={"q2": q}, work=w)
+                calls[0] += 1
+
+            return label_two_hand
 
         if isinstance(weights, dict) and any(int(weights.get(k, 0)) != 0 for k in L.TERM_FIELDS):
             L.eval_weights(weights)  # rejects unknown names
@@ -1058,13 +1093,14 @@ class PPOAgent(BaseAgent):
         return label
 
     def distill(self, buffer, weights, depth: int = 3, tau: float = 50.0, epochs: int = 1,
-                batch_size: Optional[int] = None) -> Dict[str, float]:
+                batch_size: Optional[int] = None, two_hand: Optional[Dict[str, int]] = None) -> Dict[str, float]:
         """Supervised epochs on the stored positions of ``buffer`` (PackedRolloutBuffer(positions=True)), labelled
         by the full-hand search: per minibatch one bb_plan_values_pos launch (``weights``, ``depth``; q only, into
         a scratch kept per minibatch size), the forward pass, the fused loss and the optimizer step, with no host
-        read inside the loop.  Returns the mean statistics under DISTILL_KEYS."""
+        read inside the loop.  ``two_hand``: the two-hand teacher of ``search_labeller``.  Returns the mean statistics
+        under DISTILL_KEYS."""
         bs = int(batch_size or self.config.batch_size)
-        label = self.search_labeller(weights, depth)
+        label = self.search_labeller(weights, depth, two_hand)
         acc = torch.zeros(6, dtype=torch.float32, device=self.device)
         n = 0
         for _ in range(int(epochs)):
@@ -1148,8 +1184,9 @@ class PPOAgent(BaseAgent):
                                  self.network.training))
 
     def update_guided(self, buffer, last_values, weights, depth: int, tau: float, coefs,
-                      batch_size: Optional[int] = None, epochs: Optional[int] = None) -> Dict[str, float]:
-        """``update`` with the search in the loss: GAE as ``update``, then per minibatch of ``buffer``
+                      batch_size: Optional[int] = None, epochs: Optional[int] = None,
+                      two_hand: Optional[Dict[str, int]] = None) -> Dict[str, float]:
+        """``update`` with the search in the loss (``two_hand``: the two-hand teacher of ``search_labeller``): GAE as ``update``, then per minibatch of ``buffer``
         (PackedRolloutBuffer(positions=True)) one bb_plan_values_pos launch (``weights``, ``depth``; q only,
         straight into the step's q buffer) and one ``guided_minibatch`` with ``coefs`` = (policy, value, entropy,
         distill) and ``tau``, over ``epochs`` passes (the config's num_epochs), with no host read inside the loop.
@@ -1159,7 +1196,7 @@ class PPOAgent(BaseAgent):
         if isinstance(last_values, np.ndarray):
             last_values = torch.from_numpy(last_values)
         buffer.compute_returns_and_advantages(last_values, cfg.gamma, cfg.gae_lambda)
-        label = self.search_labeller(weights, depth)
+        label = self.search_labeller(weights, depth, two_hand)
         coefs = (*(float(c) for c in coefs), float(tau))
         if len(coefs) != 5:
             raise ValueError("update_guided: coefs = (policy, value, entropy, distill)")

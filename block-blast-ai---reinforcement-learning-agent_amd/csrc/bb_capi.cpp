@@ -816,6 +816,36 @@ int bb_play_plan_pos(const bb_positions* pos, int32_t n, const int32_t* d_plan, 
   });
 }
 
+// The two-hand decision (plan_values_ext_kernel and the three plan2 kernels, csrc/bb_lookahead.hip): d_w, d_stream,
+// d_work and the outputs are device memory
+int64_t bb_plan2_work_bytes(int32_t n, int32_t candidates, int32_t deals) {
+  return bb_look_rules::plan2_work_bytes(n, candidates, deals);
+}
+
+int bb_plan2_values_pos(const bb_positions* pos, const uint64_t* d_stream, int32_t n, const bb_eval_weights* d_w,
+                        int64_t w_stride, int32_t depth, int32_t candidates, int32_t deals, uint64_t seed, void* d_work,
+                        int64_t work_bytes, const bb_plan2_out* out, void* stream) {
+  const char* rule =
+      bb_look_rules::plan2_values_pos(pos, n, d_w, w_stride, depth, candidates, deals, d_work, work_bytes, out);
+  if (!rule && n == 0) return BB_OK;  // accepted, and nothing to do
+  return look_pos_call("bb_plan2_values_pos", rule, [&] {
+    return launch_plan2_values(pos->board, pos->hand, pos->combo, d_stream, n, d_w, w_stride, depth, candidates, deals,
+                               seed, d_work, *out, (hipStream_t)stream);
+  });
+}
+
+int bb_plan2_values(bb_env* env, const uint64_t* d_stream, const bb_eval_weights* d_w, int64_t w_stride, int32_t depth,
+                    int32_t candidates, int32_t deals, uint64_t seed, void* d_work, int64_t work_bytes,
+                    const bb_plan2_out* out, void* stream) {
+  if (!env) return BB_ERR_ARG;
+  const char* rule =
+      bb_look_rules::plan2_values(env->n, d_w, w_stride, depth, candidates, deals, d_work, work_bytes, out);
+  return look_env_call(env, "bb_plan2_values", rule, [&] {
+    return launch_plan2_values(env->d.board, env->d.hand, env->d.combo, d_stream, env->n, d_w, w_stride, depth,
+                               candidates, deals, seed, d_work, *out, (hipStream_t)stream);
+  });
+}
+
 int bb_masked_sample(const float* d_logits, const uint64_t* d_mask_bits, int32_t n, const float* d_uniform,
                      uint64_t seed, uint64_t step, uint64_t env_offset, int32_t deterministic,
                      const int64_t* d_action_in, int64_t* d_action, float* d_logp, float* d_entropy,

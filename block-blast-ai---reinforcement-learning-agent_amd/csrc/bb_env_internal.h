@@ -135,6 +135,12 @@ hipError_t launch_plan_values_ext(const uint64_t* board, const uint32_t* hand, c
 hipError_t launch_refill_values_ext(const uint64_t* board, const int32_t* combo, const uint64_t* stream_id, int n,
                                     const bb_eval_weights* rows, int64_t w_stride, int depth, int deals, uint64_t seed,
                                     const bb_refill_values_out& out, hipStream_t s);
+// the two-hand decision (bb_lookahead.hip): n > 0, candidates 1..192, deals 1..1024, depth 1..3; work holds at least
+// bb_look_rules::plan2_work_bytes(n, candidates, deals) bytes; the outputs of bb_plan2_out, not all NULL
+hipError_t launch_plan2_values(const uint64_t* board, const uint32_t* hand, const int32_t* combo,
+                               const uint64_t* stream_id, int n, const bb_eval_weights* rows, int64_t w_stride,
+                               int depth, int candidates, int deals, uint64_t seed, void* work,
+                               const bb_plan2_out& out, hipStream_t s);
 // a plan played to its leaf (bb_lookahead.hip): n > 0, plan [n][3], the outputs [n], not all NULL
 hipError_t launch_play_plan(const uint64_t* board, const uint32_t* hand, const int32_t* combo, int n,
                             const int32_t* plan, const bb_play_plan_out& out, hipStream_t s);

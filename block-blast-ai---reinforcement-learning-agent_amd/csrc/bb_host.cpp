@@ -686,38 +686,138 @@ void refill_values_ext_host(const uint64_t* board, const int32_t* combo, const u
   }
 }
 
+// One plan played to its leaf (bbvec.h bb_play_plan_pos): the state reached, the lines and score summed, the status word
+struct Leaf {
+  uint64_t board;
+  uint32_t hand;
+  int combo;
+  int32_t lines;
+  int64_t score;
+  uint32_t status;
+};
+Leaf play_plan_one(uint64_t B, uint32_t h, int cb, const int32_t* plan) {
+  Leaf f{B, h, cb, 0, 0, 0u};
+  for (int k = 0; k < 3; ++k) {
+    const int32_t act = plan[k];
+    if (act < 0) break;  // a ply not played
+    const After a = act < 192 ? eval_action(f.board, f.hand, f.combo, act) : After{};
+    if (!a.legal) {
+      f.status |= BB_PLAY_ILLEGAL;
+      break;
+    }
+    f.board = a.board;
+    f.hand = hand_use(f.hand, act >> 6);
+    f.combo = a.combo1;
+    f.lines += a.lines;
+    f.score += a.gained;
+    f.status = (uint32_t)(k + 1) | (a.dead ? BB_PLAY_DEAD : 0u) | (a.refill ? BB_PLAY_REFILL : 0u);
+  }
+  return f;
+}
+
 // bbvec.h bb_play_plan_pos (the host twin of play_plan_kernel)
 void play_plan_host(const uint64_t* board, const uint32_t* hand, const int32_t* combo, int32_t n, const int32_t* plan,
                     const bb_play_plan_out& out) {
 #pragma omp parallel for schedule(static)
   for (int32_t i = 0; i < n; ++i) {
-    uint64_t B = board[i];
-    uint32_t h = hand[i];
-    int cb = combo ? combo[i] : 0;
-    int32_t lines = 0;
-    int64_t score = 0;
-    uint32_t status = 0;
-    for (int k = 0; k < 3; ++k) {
-      const int32_t act = plan[3 * (size_t)i + k];
-      if (act < 0) break;  // a ply not played
-      const After a = act < 192 ? eval_action(B, h, cb, act) : After{};
-      if (!a.legal) {
-        status |= BB_PLAY_ILLEGAL;
-        break;
-      }
-      B = a.board;
-      h = hand_use(h, act >> 6);
-      cb = a.combo1;
-      lines += a.lines;
-      score += a.gained;
-      status = (uint32_t)(k + 1) | (a.dead ? BB_PLAY_DEAD : 0u) | (a.refill ? BB_PLAY_REFILL : 0u);
+    const Leaf f = play_plan_one(board[i], hand[i], combo ? combo[i] : 0, &plan[3 * (size_t)i]);
+    if (out.board) out.board[i] = f.board;
+    if (out.hand) out.hand[i] = f.hand;
+    if (out.combo) out.combo[i] = f.combo;
+    if (out.lines) out.lines[i] = f.lines;
+    if (out.score) out.score[i] = f.score;
+    if (out.status) out.status[i] = (int32_t)f.status;
+  }
+}
+
+// bbvec.h bb_plan2_values (the host twin of plan_values_ext_kernel and the three plan2 kernels): steps 1-3 over the
+// roots, step 4 over the (root, candidate, deal) triples, steps 5-6 over the roots.  Everything in between lives in the
+// caller's workspace, carved as the HIP backend carves it (bb_look_rules.h Plan2Layout); nothing is allocated.
+void plan2_values_host(const uint64_t* board, const uint32_t* hand, const int32_t* combo, const uint64_t* stream_id,
+                       int32_t n, const bb_eval_weights* rows, int64_t w_stride, int depth, int32_t K, int32_t deals,
+                       uint64_t seed, void* work, const bb_plan2_out& out) {
+  const R::Plan2Layout lay(n, K, deals);
+  char* base = static_cast<char*>(work);
+  int64_t* q = reinterpret_cast<int64_t*>(base + lay.q);
+  uint64_t* leaf_board = reinterpret_cast<uint64_t*>(base + lay.board);
+  int64_t* moved = reinterpret_cast<int64_t*>(base + lay.moved);
+  int64_t* value = out.value ? out.value : reinterpret_cast<int64_t*>(base + lay.value);
+  int32_t* rest = reinterpret_cast<int32_t*>(base + lay.rest);
+  int32_t* leaf_combo = reinterpret_cast<int32_t*>(base + lay.combo);
+  int32_t* cand = out.cand ? out.cand : reinterpret_cast<int32_t*>(base + lay.cand);
+  int32_t* status = out.status ? out.status : reinterpret_cast<int32_t*>(base + lay.status);
+  const bb_plan_values_out pv{q, rest, nullptr, nullptr};
+
+  // ---- steps 1-3: the values, the candidates by rank, their leaves
+#pragma omp parallel for schedule(dynamic, 1)
+  for (int32_t i = 0; i < n; ++i) {
+    const bb_eval_weights w = rows[(int64_t)i * w_stride];
+    const int cb = combo ? combo[i] : 0;
+    if (shaped(w))
+      plan_values_one(board[i], hand[i], cb, (size_t)i, w, depth, pv);
+    else
+      plan_values_one(board[i], hand[i], cb, (size_t)i, w.base, depth, pv);
+    const int64_t* qi = q + (size_t)i * 192;
+    const int32_t* ri = rest + (size_t)i * 192;
+    int32_t legal = 0;
+    for (int a = 0; a < 192; ++a) {
+      if (qi[a] == INT64_MIN) continue;  // never a candidate
+      ++legal;
+      int32_t rank = 0;  // the place of a in a stable descending sort
+      for (int b = 0; b < 192; ++b) rank += qi[b] > qi[a] || (qi[b] == qi[a] && b < a);
+      if (rank >= K) continue;
+      const int r2 = ri[a] & 0xFF, r3 = (ri[a] >> 8) & 0xFF;
+      const int32_t plan[3] = {a, r2 == 0xFF ? -1 : r2, r3 == 0xFF ? -1 : r3};
+      const Leaf f = play_plan_one(board[i], hand[i], cb, plan);
+      const size_t c = (size_t)i * K + (size_t)rank;
+      cand[c] = a;
+      leaf_board[c] = f.board;
+      leaf_combo[c] = f.combo;
+      moved[c] = (int64_t)w.base.lines * f.lines + (int64_t)w.base.score * f.score;
+      status[c] = (int32_t)f.status;
     }
-    if (out.board) out.board[i] = B;
-    if (out.hand) out.hand[i] = h;
-    if (out.combo) out.combo[i] = cb;
-    if (out.lines) out.lines[i] = lines;
-    if (out.score) out.score[i] = score;
-    if (out.status) out.status[i] = (int32_t)status;
+    for (int32_t r = legal; r < K; ++r) cand[(size_t)i * K + r] = status[(size_t)i * K + r] = -1;
+  }
+
+  // ---- step 4: one (root, candidate, deal) triple per iteration, under the root's row and stream id
+  const int64_t triples = (int64_t)n * K * deals;
+#pragma omp parallel for schedule(dynamic, 1)
+  for (int64_t t = 0; t < triples; ++t) {
+    const int64_t c = t / deals, j = t % deals, i = c / K;
+    if (status[c] < 0 || !((uint32_t)status[c] & BB_PLAY_REFILL)) {
+      value[t] = 0;
+      continue;
+    }
+    const bb_eval_weights w = rows[i * w_stride];
+    int32_t attempts;
+    const uint32_t dealt = refill_deal(leaf_board[c], seed, stream_id ? stream_id[i] : (uint64_t)i, j, attempts);
+    value[t] = shaped(w) ? refill_search(leaf_board[c], dealt, leaf_combo[c], depth, w, w.base.dead)
+                         : refill_search(leaf_board[c], dealt, leaf_combo[c], depth, w.base, w.base.dead);
+  }
+
+  // ---- steps 5-6: Q2 and the choice, ties to the lower action
+#pragma omp parallel for schedule(static)
+  for (int32_t i = 0; i < n; ++i) {
+    int64_t* q2 = out.q2 ? out.q2 + (size_t)i * 192 : nullptr;
+    if (q2)
+      for (int a = 0; a < 192; ++a) q2[a] = INT64_MIN;
+    int64_t best = INT64_MIN;
+    int32_t best_a = 192;
+    for (int32_t r = 0; r < K; ++r) {
+      const size_t c = (size_t)i * K + (size_t)r;
+      const int32_t a = cand[c];
+      if (a < 0) continue;
+      int64_t x;
+      if ((uint32_t)status[c] & BB_PLAY_REFILL) {
+        x = (int64_t)deals * moved[c];
+        for (int32_t j = 0; j < deals; ++j) x += value[c * deals + (size_t)j];
+      } else {
+        x = (int64_t)deals * q[(size_t)i * 192 + (size_t)a];
+      }
+      if (q2) q2[a] = x;
+      if (x > best || (x == best && a < best_a)) best = x, best_a = a;
+    }
+    if (out.action) out.action[i] = best_a == 192 ? 0 : best_a;
   }
 }
 
@@ -1203,6 +1303,35 @@ int bb_play_plan_pos(const bb_positions* pos, int32_t n, const int32_t* d_plan, 
   (void)stream;
   if (int rc = refused(nullptr, "bb_play_plan_pos", R::play_plan_pos(pos, n, d_plan, out))) return rc;
   play_plan_host(pos->board, pos->hand, pos->combo, n, d_plan, *out);
+  return BB_OK;
+}
+
+int64_t bb_plan2_work_bytes(int32_t n, int32_t candidates, int32_t deals) {
+  return R::plan2_work_bytes(n, candidates, deals);
+}
+
+int bb_plan2_values_pos(const bb_positions* pos, const uint64_t* d_stream, int32_t n, const bb_eval_weights* d_w,
+                        int64_t w_stride, int32_t depth, int32_t candidates, int32_t deals, uint64_t seed, void* d_work,
+                        int64_t work_bytes, const bb_plan2_out* out, void* stream) {
+  (void)stream;
+  if (int rc = refused(nullptr, "bb_plan2_values_pos",
+                       R::plan2_values_pos(pos, n, d_w, w_stride, depth, candidates, deals, d_work, work_bytes, out)))
+    return rc;
+  plan2_values_host(pos->board, pos->hand, pos->combo, d_stream, n, d_w, w_stride, depth, candidates, deals, seed,
+                    d_work, *out);
+  return BB_OK;
+}
+
+int bb_plan2_values(bb_env* env, const uint64_t* d_stream, const bb_eval_weights* d_w, int64_t w_stride, int32_t depth,
+                    int32_t candidates, int32_t deals, uint64_t seed, void* d_work, int64_t work_bytes,
+                    const bb_plan2_out* out, void* stream) {
+  (void)stream;
+  if (!env) return BB_ERR_ARG;
+  if (int rc = refused(env, "bb_plan2_values",
+                       R::plan2_values(env->n, d_w, w_stride, depth, candidates, deals, d_work, work_bytes, out)))
+    return rc;
+  plan2_values_host(env->board.data(), env->hand.data(), env->combo.data(), d_stream, env->n, d_w, w_stride, depth,
+                    candidates, deals, seed, d_work, *out);
   return BB_OK;
 }
 

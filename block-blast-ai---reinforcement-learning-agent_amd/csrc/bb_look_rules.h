@@ -1,4 +1,4 @@
-// bb_look_rules.h -- the argument rules of the twenty-seven lookahead entry points of include/bbvec.h, one copy for
+// bb_look_rules.h -- the argument rules of the twenty-nine lookahead entry points of include/bbvec.h, one copy for
 // both backends (csrc/bb_capi.cpp and csrc/bb_host.cpp).  Plain C++, nothing from HIP.
 //
 // Each function returns the rule an argument set breaks, as the text that follows "<entry point>: " in
@@ -8,8 +8,8 @@
 // Asymmetries that are part of the ABI as it stands: bb_afterstates_pos, bb_greedy_actions(_each)_pos and
 // bb_plan_actions(_each)_pos refuse n == 0 and answer every broken rule with one text; bb_plan_values_pos accepts n == 0
 // (and does nothing) and names the rule that broke, and so do bb_safe_mask_pos, bb_refill_census_pos,
-// bb_refill_values_pos, bb_play_plan_pos, bb_board_terms_pos, bb_plan_actions_ext_pos, bb_plan_values_ext_pos and
-// bb_refill_values_ext_pos.
+// bb_refill_values_pos, bb_play_plan_pos, bb_board_terms_pos, bb_plan_actions_ext_pos, bb_plan_values_ext_pos,
+// bb_refill_values_ext_pos and bb_plan2_values_pos.
 #pragma once
 #include <stdint.h>
 
@@ -191,6 +191,53 @@ inline const char* refill_values_ext_pos(const uint64_t* board, int32_t n, const
   if (!board) return "board is NULL";
   if (n < 0) return "n is negative";
   return refill_values_ext(d_w, w_stride, depth, deals, out);
+}
+
+// the two-hand decision (bb_plan2_values): the workspace of n positions, K candidates and `deals` deals as byte
+// offsets, the 8-byte arrays first.  Both backends carve the caller's scratch with it, and bb_plan2_work_bytes is
+// its `bytes`.
+struct Plan2Layout {
+  int64_t q, board, moved, value, rest, combo, cand, status, bytes;
+  Plan2Layout(int64_t n, int64_t k, int64_t deals) {
+    int64_t at = 0;
+    q = at, at += n * 192 * 8;            // int64  [n][192]
+    board = at, at += n * k * 8;          // uint64 [n][K]
+    moved = at, at += n * k * 8;          // int64  [n][K]
+    value = at, at += n * k * deals * 8;  // int64  [n][K][deals]
+    rest = at, at += n * 192 * 4;         // int32  [n][192]
+    combo = at, at += n * k * 4;          // int32  [n][K]
+    cand = at, at += n * k * 4;           // int32  [n][K]
+    status = at, at += n * k * 4;         // int32  [n][K]
+    bytes = (at + 7) & ~(int64_t)7;
+  }
+};
+inline bool bad_plan2_sizes(int32_t n, int32_t candidates, int32_t deals) {
+  return n < 0 || candidates < 1 || candidates > 192 || deals < 1 || deals > BB_REFILL_MAX_DEALS;
+}
+inline int64_t plan2_work_bytes(int32_t n, int32_t candidates, int32_t deals) {
+  return bad_plan2_sizes(n, candidates, deals) ? -1 : Plan2Layout(n, candidates, deals).bytes;
+}
+// n: the positions of the _pos form, the handle's envs of the handle form
+inline const char* plan2_values(int32_t n, const bb_eval_weights* d_w, int64_t w_stride, int32_t depth,
+                                int32_t candidates, int32_t deals, const void* d_work, int64_t work_bytes,
+                                const bb_plan2_out* out) {
+  if (n < 0) return "n is negative";
+  if (!d_w) return "weight rows are NULL";
+  if (w_stride != 0 && w_stride != 1) return "w_stride must be 0 or 1";
+  if (!out) return "out is NULL";
+  if (!out->action && !out->q2 && !out->cand && !out->status && !out->value) return "all five outputs are NULL";
+  if (bad_depth(depth)) return "depth must be 1..3";
+  if (candidates < 1 || candidates > 192) return "candidates must be 1..192";
+  if (deals < 1 || deals > BB_REFILL_MAX_DEALS) return "deals must be 1..1024";
+  if (!d_work) return "d_work is NULL";
+  if (work_bytes < plan2_work_bytes(n, candidates, deals)) return "work_bytes is below bb_plan2_work_bytes";
+  return nullptr;
+}
+inline const char* plan2_values_pos(const bb_positions* pos, int32_t n, const bb_eval_weights* d_w, int64_t w_stride,
+                                    int32_t depth, int32_t candidates, int32_t deals, const void* d_work,
+                                    int64_t work_bytes, const bb_plan2_out* out) {
+  if (no_positions(pos)) return "positions (board, hand) are NULL";
+  return plan2_values(n, d_w, w_stride, depth, candidates, deals, d_work, work_bytes, out);
 }
 
 }  // namespace bb_look_rules

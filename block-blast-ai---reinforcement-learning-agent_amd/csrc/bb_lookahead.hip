@@ -16,6 +16,7 @@
 #include <stdint.h>
 
 #include "bb_env_internal.h"
+#include "bb_look_rules.h"
 
 namespace bb {
 
@@ -1124,6 +1125,229 @@ play_plan_kernel(LookTable t, LookPos pos, int n, const int32_t* __restrict__ pl
   }
 }
 
+// ---------------------------------------------------------------------------
+// The two-hand decision (bbvec.h bb_plan2_values): three kernels behind a plan_values_ext_kernel launch that wrote
+// q [n][192] and rest [n][192] into the caller's workspace.  Everything between the launches lives in that workspace
+// (Plan2Work below); nothing is read back by the host.
+//
+//   plan2_candidates_kernel  one wave (one workgroup of 64) per position.  The 192 q go into LDS; lane l ranks its
+//       three actions l, l + 64, l + 128 by counting, 192 broadcast reads each:
+//       rank(a) = #{b : q[b] > q[a] or (q[b] == q[a] and b < a)}, the place of a in a stable descending sort.  Every
+//       legal action is above INT64_MIN, so the legal ones hold the ranks 0..L-1.  A lane whose action is legal with
+//       rank < K plays (a, decoded rest[a]) with eval_action and writes slot `rank` of the position: cand, the leaf's
+//       board and combo, its move terms under the root's row and play_plan_kernel's status word.  Slots L..K-1 get
+//       cand = status = -1.  The slots differ by lane, so the piece table is copied to LDS once per workgroup, as
+//       play_plan_kernel does.  Trip bounds: 192 compares, 3 actions, 3 plies.
+//   plan2_deal_kernel  one workgroup of four waves per (position, candidate, deal) triple; above the grid cap the
+//       workgroups stride over the triples, (i, k * deals + j) advancing by the grid size as two digits, without a
+//       64-bit division.  A candidate that is absent or whose leaf is no refill gets value 0 from thread 0 and the
+//       workgroup goes on before it meets a barrier (the status word is read at a uniform index: one answer for the
+//       workgroup).  Otherwise refill_deal and refill_search<W> as refill_values_ext_kernel calls them, on the leaf's
+//       board and combo under the root's row and stream id.  Trip bounds: those of refill_values_ext_kernel.
+//   plan2_pick_kernel  one wave (one workgroup of 64) per position.  Lane l takes the candidates l, l + 64, l + 128:
+//       Q2 = deals * moved + sum of the dealt values for a refill leaf, deals * q[a] for any other, staged in an LDS
+//       row of 192 that starts as INT64_MIN; the lanes' best (Q2, action) are joined by shuffles under take_better
+//       (the larger value, then the lower action -- not the lower rank) and the row is stored, 64 consecutive
+//       elements per store.  Trip bounds: 3 candidates a lane, `deals` values each.
+// No atomics, no inline assembly, nothing between workgroups.
+// ---------------------------------------------------------------------------
+constexpr int kPlan2Block = 64;                  // candidates and pick: one wave is one workgroup
+constexpr int64_t kPlan2DealMaxGrid = 1 << 14;   // more triples than this: the workgroups stride over them
+
+struct Plan2Work {   // the workspace as launch_plan2_values carves it (bb_look_rules.h Plan2Layout holds the offsets)
+  int64_t* q;        // [n][192]
+  uint64_t* board;   // [n][K] the leaf's board
+  int64_t* moved;    // [n][K] w.base.lines * lines + w.base.score * score over the plies played
+  int64_t* value;    // [n][K][deals] (the caller's own array when it asked for one)
+  int32_t* rest;     // [n][192]
+  int32_t* combo;    // [n][K] the leaf's combo
+  int32_t* cand;     // [n][K] (the caller's own array when it asked for one)
+  int32_t* status;   // [n][K] (the caller's own array when it asked for one)
+};
+
+__global__ void __launch_bounds__(kPlan2Block)
+plan2_candidates_kernel(LookTable t, LookPos pos, int n, const bb_eval_weights* __restrict__ rows, int64_t w_stride,
+                        int K, Plan2Work wk) {
+  __shared__ LookTable s_t;
+  __shared__ int64_t s_q[BB_ACTIONS];
+  {
+    const uint64_t* src = reinterpret_cast<const uint64_t*>(&t);
+    uint64_t* dst = reinterpret_cast<uint64_t*>(&s_t);
+    for (int k = (int)threadIdx.x; k < kPieces * kRowWords; k += kPlan2Block) dst[k] = src[k];
+  }
+  const int lane = (int)threadIdx.x;
+  for (int64_t i = blockIdx.x; i < (int64_t)n; i += gridDim.x) {
+    __syncthreads();  // the table is in place; the last position's q have been read by every lane
+    int64_t qa[kHand];
+#pragma unroll
+    for (int s = 0; s < kHand; ++s) {
+      qa[s] = wk.q[i * BB_ACTIONS + (int64_t)(s * 64 + lane)];
+      s_q[s * 64 + lane] = qa[s];
+    }
+    __syncthreads();
+    int rank[kHand] = {0, 0, 0};
+#pragma unroll 4
+    for (int b = 0; b < BB_ACTIONS; ++b) {
+      const int64_t qb = s_q[b];  // one address for the wave: a broadcast read
+#pragma unroll
+      for (int s = 0; s < kHand; ++s) rank[s] += (int)(qb > qa[s] || (qb == qa[s] && b < s * 64 + lane));
+    }
+    int legal = 0;  // L: the legal actions hold the ranks 0..L-1
+#pragma unroll
+    for (int s = 0; s < kHand; ++s) legal += __popcll(__ballot(qa[s] != INT64_MIN));
+    const int32_t lines_w = rows[i * w_stride].base.lines, score_w = rows[i * w_stride].base.score;
+#pragma unroll 1
+    for (int s = 0; s < kHand; ++s) {
+      // selects, not qa[s] / rank[s]: an array indexed by a loop counter that is not unrolled would live in scratch
+      const int64_t qs = s == 0 ? qa[0] : (s == 1 ? qa[1] : qa[2]);
+      const int slot = s == 0 ? rank[0] : (s == 1 ? rank[1] : rank[2]);
+      if (qs == INT64_MIN || slot >= K) continue;
+      const int a1 = s * 64 + lane;
+      const int32_t rest = wk.rest[i * BB_ACTIONS + (int64_t)a1];
+      const int r2 = rest & 0xFF, r3 = (rest >> 8) & 0xFF;
+      const int a2 = r2 == 0xFF ? -1 : r2, a3 = r3 == 0xFF ? -1 : r3;
+      uint64_t B = pos.board[i];
+      uint32_t hand = pos.hand[i];
+      int combo = pos.combo ? pos.combo[i] : 0;
+      int64_t moved = 0;
+      uint32_t status = 0u;
+      bool go = true;
+#pragma unroll 1
+      for (int k = 0; k < kHand; ++k) {  // play_plan_kernel's plies
+        const int act = k == 0 ? a1 : (k == 1 ? a2 : a3);
+        go = go && act >= 0;
+        if (!go) continue;
+        const int p = act >> 6;
+        if (p >= kHand) {  // not an action
+          status |= BB_PLAY_ILLEGAL;
+          go = false;
+          continue;
+        }
+        const After a = eval_action(s_t, B, hand, combo, p, act & 63);
+        if (!a.legal) {
+          status |= BB_PLAY_ILLEGAL;
+          go = false;
+          continue;
+        }
+        B = a.board;
+        hand = hand_use(hand, p);
+        combo = a.combo1;
+        moved += (int64_t)lines_w * a.lines + (int64_t)score_w * a.gained;
+        status = (uint32_t)(k + 1) | (a.dead ? BB_PLAY_DEAD : 0u) | (a.refill ? BB_PLAY_REFILL : 0u);
+      }
+      const int64_t o = i * (int64_t)K + (int64_t)slot;  // slot < K
+      wk.cand[o] = a1;
+      wk.board[o] = B;
+      wk.combo[o] = combo;
+      wk.moved[o] = moved;
+      wk.status[o] = (int32_t)status;
+    }
+    for (int r = legal + lane; r < K; r += kPlan2Block) {  // the absent candidates
+      wk.cand[i * (int64_t)K + (int64_t)r] = -1;
+      wk.status[i * (int64_t)K + (int64_t)r] = -1;
+    }
+  }
+}
+
+__global__ void __launch_bounds__(kPlanBlock)
+plan2_deal_kernel(LookTable t, const uint64_t* __restrict__ stream_id, int n, int K, int m,
+                  const bb_eval_weights* __restrict__ rows, int64_t w_stride, int depth, uint64_t seed,
+                  const int32_t* __restrict__ leaf_status, const uint64_t* __restrict__ leaf_board,
+                  const int32_t* __restrict__ leaf_combo, int64_t* __restrict__ value) {
+  __shared__ PlanRecord s_rec[kPlanRecords];
+  __shared__ int s_cnt[kHand];
+  __shared__ int64_t s_v[kPlanWaves];
+  __shared__ uint32_t s_deal[2][kPlanWaves];
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int cell = (int)(threadIdx.x & 63u);
+  // two digits as in refill_values_ext_kernel: the root i, and kj = k * m + j of radix K * m <= 196,608; the grid size
+  // is added digit by digit, and k, j come back from kj by one 32-bit division a triple
+  const uint32_t um = (uint32_t)m, ukm = (uint32_t)K * um;
+  const uint32_t gi = gridDim.x / ukm, gkj = gridDim.x - gi * ukm;   // the stride in (i, kj)
+  int64_t i = (int64_t)(blockIdx.x / ukm);
+  uint32_t kj = blockIdx.x - (uint32_t)i * ukm;
+  while (i < (int64_t)n) {
+    const uint32_t k = kj / um, j = kj - k * um;
+    const int64_t c = i * (int64_t)K + (int64_t)k;
+    const int64_t o = i * (int64_t)ukm + (int64_t)kj;
+    const int32_t status = (int32_t)uniform32((uint32_t)leaf_status[c]);
+    if (status < 0 || !((uint32_t)status & BB_PLAY_REFILL)) {  // the workgroup's answer: no barrier is met on this side
+      if (threadIdx.x == 0) value[o] = 0;
+    } else {
+    const uint64_t B = uniform64(leaf_board[c]);
+    const int combo = (int)uniform32((uint32_t)leaf_combo[c]);
+    const uint64_t idx = stream_id ? uniform64(stream_id[i]) : (uint64_t)i;  // the root's: one stream for its candidates
+    const bb_eval_weights w = load_eval_weights(rows, i * w_stride);       // the root's row
+    const bool shaped = (w.perimeter | w.room3 | w.room5 | w.fits) != 0;     // scalar: one answer for the workgroup
+
+    uint32_t ids;
+    int attempts;
+    refill_deal(t, B, seed, idx, j, wave, cell, s_deal, ids, attempts);
+    const Position P{B, ids, combo};
+    int64_t best;
+    if (shaped)
+      best = refill_search(t, P, w, depth, wave, cell, s_rec, s_cnt);
+    else
+      best = refill_search(t, P, w.base, depth, wave, cell, s_rec, s_cnt);
+    if (cell == 0) s_v[wave] = best;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+      for (int v = 1; v < kPlanWaves; ++v) best = s_v[v] > best ? s_v[v] : best;
+      value[o] = best == INT64_MIN ? (int64_t)w.base.dead : best;  // no legal first move
+    }
+    // no barrier here, as in refill_values_ext_kernel: a triple that is skipped touches no LDS at all
+    }
+
+    kj += gkj;
+    i += (int64_t)gi;
+    if (kj >= ukm) {
+      kj -= ukm;
+      ++i;
+    }
+  }
+}
+
+__global__ void __launch_bounds__(kPlan2Block)
+plan2_pick_kernel(int n, int K, int m, Plan2Work wk, int32_t* __restrict__ action, int64_t* __restrict__ q2) {
+  __shared__ int64_t s_q2[BB_ACTIONS];
+  const int lane = (int)threadIdx.x;
+  for (int64_t i = blockIdx.x; i < (int64_t)n; i += gridDim.x) {
+#pragma unroll
+    for (int s = 0; s < kHand; ++s) s_q2[s * 64 + lane] = INT64_MIN;
+    __syncthreads();
+    int64_t v = INT64_MIN;  // below every Q2 (see greedy_kernel): a lane without a candidate never wins
+    int act = BB_ACTIONS;
+    for (int r = lane; r < K; r += kPlan2Block) {  // at most three candidates a lane
+      const int64_t c = i * (int64_t)K + (int64_t)r;
+      const int a = wk.cand[c];
+      if (a < 0) continue;
+      int64_t x;
+      if ((uint32_t)wk.status[c] & BB_PLAY_REFILL) {
+        x = (int64_t)m * wk.moved[c];
+        for (int j = 0; j < m; ++j) x += wk.value[c * (int64_t)m + (int64_t)j];
+      } else {
+        x = (int64_t)m * wk.q[i * BB_ACTIONS + (int64_t)a];
+      }
+      s_q2[a] = x;  // the candidates of a position are distinct actions
+      take_better(v, act, x, a);
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+      const int64_t v2 = __shfl_xor(v, d, 64);
+      const int act2 = __shfl_xor(act, d, 64);
+      take_better(v, act, v2, act2);
+    }
+    __syncthreads();
+    if (action && lane == 0) action[i] = act == BB_ACTIONS ? 0 : act;
+    if (q2) {
+#pragma unroll
+      for (int s = 0; s < kHand; ++s) q2[i * BB_ACTIONS + (int64_t)(s * 64 + lane)] = s_q2[s * 64 + lane];
+    }
+    __syncthreads();  // the row is rewritten by the workgroup's next position
+  }
+}
+
 const LookTable& look_table() {
   static const LookTable t = [] {
     LookTable x;
@@ -1239,6 +1463,45 @@ hipError_t launch_refill_values_ext(const uint64_t* board, const int32_t* combo,
   const dim3 grid((unsigned)(pairs < kRefillMaxGrid ? pairs : kRefillMaxGrid));
   hipLaunchKernelGGL(refill_values_ext_kernel, grid, dim3(kPlanBlock), 0, s, look_table(), cols, n, deals, rows,
                      w_stride, depth, seed, out);
+  return hipGetLastError();
+}
+
+// bbvec.h bb_plan2_values: four launches on one stream, each reading what the one before wrote into the workspace
+hipError_t launch_plan2_values(const uint64_t* board, const uint32_t* hand, const int32_t* combo,
+                               const uint64_t* stream_id, int n, const bb_eval_weights* rows, int64_t w_stride,
+                               int depth, int candidates, int deals, uint64_t seed, void* work,
+                               const bb_plan2_out& out, hipStream_t s) {
+  const bb_look_rules::Plan2Layout lay(n, candidates, deals);
+  char* base = static_cast<char*>(work);
+  Plan2Work wk;
+  wk.q = reinterpret_cast<int64_t*>(base + lay.q);
+  wk.board = reinterpret_cast<uint64_t*>(base + lay.board);
+  wk.moved = reinterpret_cast<int64_t*>(base + lay.moved);
+  wk.value = out.value ? out.value : reinterpret_cast<int64_t*>(base + lay.value);
+  wk.rest = reinterpret_cast<int32_t*>(base + lay.rest);
+  wk.combo = reinterpret_cast<int32_t*>(base + lay.combo);
+  wk.cand = out.cand ? out.cand : reinterpret_cast<int32_t*>(base + lay.cand);
+  wk.status = out.status ? out.status : reinterpret_cast<int32_t*>(base + lay.status);
+
+  const LookPos pos{board, hand, combo, nullptr};
+  const bb_plan_values_out pv{wk.q, wk.rest, nullptr, nullptr};
+  hipLaunchKernelGGL(plan_values_ext_kernel, plan_grid(n), dim3(kPlanBlock), 0, s, look_table(), pos, n, rows, w_stride,
+                     depth, pv);
+  hipError_t st = hipGetLastError();
+  if (st != hipSuccess) return st;
+  const dim3 wave_grid((unsigned)((int64_t)n < kPlanMaxGrid ? (int64_t)n : kPlanMaxGrid));
+  hipLaunchKernelGGL(plan2_candidates_kernel, wave_grid, dim3(kPlan2Block), 0, s, look_table(), pos, n, rows, w_stride,
+                     candidates, wk);
+  st = hipGetLastError();
+  if (st != hipSuccess) return st;
+  const int64_t triples = (int64_t)n * candidates * deals;
+  const dim3 deal_grid((unsigned)(triples < kPlan2DealMaxGrid ? triples : kPlan2DealMaxGrid));
+  hipLaunchKernelGGL(plan2_deal_kernel, deal_grid, dim3(kPlanBlock), 0, s, look_table(), stream_id, n, candidates,
+                     deals, rows, w_stride, depth, seed, wk.status, wk.board, wk.combo, wk.value);
+  st = hipGetLastError();
+  if (st != hipSuccess) return st;
+  hipLaunchKernelGGL(plan2_pick_kernel, wave_grid, dim3(kPlan2Block), 0, s, n, candidates, deals, wk, out.action,
+                     out.q2);
   return hipGetLastError();
 }
 

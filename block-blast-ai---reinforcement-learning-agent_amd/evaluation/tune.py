@@ -32,7 +32,7 @@ from typing import Callable, Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from agents.greedy import DEFAULT_WEIGHTS, PopulationPlanAgent
+from agents.greedy import DEFAULT_WEIGHTS, PopulationPlanAgent, PopulationTwoHandAgent
 from runtime import kernels as K
 from runtime import lib as L
 
@@ -45,15 +45,24 @@ EXTRAS = ("expected_losses", "survival", "min_solvable_fraction", "refills")  # 
 
 
 def _play_population(weight_dicts: Sequence[Dict[str, int]], games: int, moves: int, seed: int, depth: int, device,
-                     census: bool = False):
+                     census: bool = False, two_hand: Optional[Dict[str, int]] = None):
     """(scores, lengths, extras), int64 [P, G] each: env c * G + g plays candidate c on the piece stream seeded
-    seed + g.  extras: None, or with census the EXTRAS of ``evaluate_agent(census=True)`` as [P, G] tensors."""
+    seed + g.  extras: None, or with census the EXTRAS of ``evaluate_agent(census=True)`` as [P, G] tensors.
+    ``two_hand`` ({"candidates", "deals"}): the population is played by a ``PopulationTwoHandAgent`` under rows of
+    twelve, env e with stream id e % G -- the candidates of a game meet the same dealt hands -- and the deals keyed by
+    ``seed``: row c is what ``two_hand_agent_class(w_c)(w_c, depth, candidates, deals, seed)`` scores on the G games."""
     p, g = len(weight_dicts), int(games)
-    if any(set(w) & set(L.TERM_FIELDS) for w in weight_dicts):  # a shape weight is named: rows of twelve
+    if two_hand is not None:
         rows = K.eval_rows(list(weight_dicts)).repeat_interleave(g, dim=0)
+        agent = PopulationTwoHandAgent(rows, depth=depth, candidates=int(two_hand["candidates"]),
+                                       deals=int(two_hand["deals"]), seed=seed,
+                                       stream=torch.arange(p * g, dtype=torch.int64) % g, device=device)
+    elif any(set(w) & set(L.TERM_FIELDS) for w in weight_dicts):  # a shape weight is named: rows of twelve
+        rows = K.eval_rows(list(weight_dicts)).repeat_interleave(g, dim=0)
+        agent = PopulationPlanAgent(rows, depth=depth, device=device)
     else:
         rows = K.weight_rows(list(weight_dicts)).repeat_interleave(g, dim=0)
-    agent = PopulationPlanAgent(rows, depth=depth, device=device)
+        agent = PopulationPlanAgent(rows, depth=depth, device=device)
     res = evaluate_agent(agent, num_episodes=p * g, seeds=[seed + e % g for e in range(p * g)], max_moves=int(moves),
                          **({"census": True} if census else {}))
     extras = None
@@ -65,7 +74,7 @@ def _play_population(weight_dicts: Sequence[Dict[str, int]], games: int, moves: 
 
 
 def evaluate_population(weight_dicts: Sequence[Dict[str, int]], games: int, moves: int, seed: int, depth: int = 3,
-                        device=None, census: bool = False):
+                        device=None, census: bool = False, two_hand: Optional[Dict[str, int]] = None):
     """The final score of every (candidate, game): int64 [P, G] on the CPU.  One ``DeviceEnvBatch`` of P * G envs
     without auto-reset; candidate c, game g is seeded ``seed + g`` -- common random numbers: every candidate sees the
     same G piece streams, so candidates differ by their play alone.  The accounting is ``evaluate_agent``'s: the
@@ -76,8 +85,11 @@ def evaluate_population(weight_dicts: Sequence[Dict[str, int]], games: int, move
     census=True: returns (scores, extras), extras holding float64 [P, G] tensors "expected_losses", "survival",
     "min_solvable_fraction" and an int64 "refills" (``evaluation.evaluate.census_summary``).  The envs of a population
     run without auto-reset and start together, so every live game refills on the same moves: one
-    ``bb_refill_census`` launch per three moves over all P * G boards, finished games masked."""
-    scores, _, extras = _play_population(weight_dicts, games, moves, seed, depth, device, census)
+    ``bb_refill_census`` launch per three moves over all P * G boards, finished games masked.  ``two_hand``
+    ({"candidates", "deals"}): the two-hand agents instead (``PopulationTwoHandAgent``, one ``bb_plan2_values`` call per
+    move); row c then equals the ``scores`` of ``evaluate_agent`` of ``two_hand_agent_class(w)(w, depth, candidates,
+    deals, seed)`` on the same seeds."""
+    scores, _, extras = _play_population(weight_dicts, games, moves, seed, depth, device, census, two_hand)
     return (scores, extras) if census else scores
 
 
@@ -140,11 +152,11 @@ def _dict_of(theta, fields: Sequence[str] = L.GREEDY_FIELDS) -> Dict[str, int]:
 
 
 def _agent_depth(agent: str, depth: int) -> int:
-    if agent not in ("plan", "greedy"):
-        raise ValueError(f"agent must be 'plan' or 'greedy', not {agent!r}")
-    if agent == "plan" and int(depth) not in (1, 2, 3):
+    if agent not in ("plan", "greedy", "plan2"):
+        raise ValueError(f"agent must be 'plan', 'plan2' or 'greedy', not {agent!r}")
+    if agent != "greedy" and int(depth) not in (1, 2, 3):
         raise ValueError(f"depth must be 1, 2 or 3, not {depth}")
-    return int(depth) if agent == "plan" else 0  # 0: PopulationPlanAgent's one-ply greedy kernel
+    return int(depth) if agent != "greedy" else 0  # 0: PopulationPlanAgent's one-ply greedy kernel
 
 
 def _extras_means(extras: Dict[str, torch.Tensor], c: int) -> Dict[str, float]:
@@ -157,13 +169,14 @@ def _extras_means(extras: Dict[str, torch.Tensor], c: int) -> Dict[str, float]:
 
 
 def compare(weight_dicts: Sequence[Dict[str, int]], games: int, moves: int, seed: int, depth: int = 3,
-            device=None, census: bool = False) -> List[dict]:
+            device=None, census: bool = False, two_hand: Optional[Dict[str, int]] = None) -> List[dict]:
     """Several weight sets on the same ``games`` piece streams (seeds seed + g), one population call: per set the mean
     score, the mean score per move (each game's score over its own moves) and its standard error over the games, and
     the number of games that ended before the ``moves`` cut.  census=True adds four columns: expected_losses (the
     hazards of all the set's refills summed over its games -- the number of games the census expects the dealer to
-    have lost, beside ended_before_cut), survival (mean), min_solvable_fraction (lowest) and refills (mean)."""
-    scores, lengths, extras = _play_population(weight_dicts, games, moves, seed, depth, device, census)
+    have lost, beside ended_before_cut), survival (mean), min_solvable_fraction (lowest) and refills (mean).
+    ``two_hand``: as ``evaluate_population``."""
+    scores, lengths, extras = _play_population(weight_dicts, games, moves, seed, depth, device, census, two_hand)
     return _compare_records(weight_dicts, scores, lengths, extras, games, moves)
 
 
@@ -205,8 +218,13 @@ def tune(agent: str = "plan", depth: int = 3, population: int = 64, games: int =
          generations: int = 30, elite_frac: float = 0.25, seed: int = 1, init: Optional[Dict[str, int]] = None,
          fixed: Sequence[str] = ("dead",), device=None, output: Optional[str] = None, log: Optional[str] = None,
          sigma0: float = 300.0, scale: float = 1000, sigma_floor: float = 10, holdout_games: int = 32,
-         fitness: str = "score", horizon: Optional[int] = None, terms: Sequence[str] = ()) -> dict:
-    """CEM over the weights of ``HandPlanAgent(depth)`` (agent "plan") or ``GreedyAgent`` (agent "greedy").
+         fitness: str = "score", horizon: Optional[int] = None, terms: Sequence[str] = (), candidates: int = 8,
+         deals: int = 16) -> dict:
+    """CEM over the weights of ``HandPlanAgent(depth)`` (agent "plan"), ``GreedyAgent`` (agent "greedy") or the two-hand
+    agent (agent "plan2": ``TwoHandPlanAgent`` / ``TwoHandShapeAgent`` with ``candidates`` and ``deals``, the population
+    played by ``PopulationTwoHandAgent``, env e on stream id e % games, every generation's deals keyed by its game seed,
+    the held-out comparison played the same way; ``output`` then writes {"agent": "plan2", "depth", "candidates",
+    "deals", "seed", "weights"}, which ``TwoHandPlanAgent.load`` reads, and the final record names both numbers).
 
     Fitness is a candidate's mean final score over ``games`` games of at most ``moves`` moves
     (``evaluate_population``).  Generation k plays the seeds ``seed + k * games + g``: fresh for each generation,
@@ -237,8 +255,14 @@ def tune(agent: str = "plan", depth: int = 3, population: int = 64, games: int =
     terms = tuple(terms)
     if set(terms) - set(L.TERM_FIELDS) or len(set(terms)) != len(terms):
         raise ValueError(f"terms must be distinct names of {L.TERM_FIELDS}, not {list(terms)}")
-    if terms and agent != "plan":
-        raise ValueError("terms need agent 'plan': the one-ply greedy kernel has no extended form")
+    if terms and agent == "greedy":
+        raise ValueError("terms need agent 'plan' or 'plan2': the one-ply greedy kernel has no extended form")
+    two_hand = None
+    if agent == "plan2":
+        if not 1 <= int(candidates) <= 192 or not 1 <= int(deals) <= L.BB_REFILL_MAX_DEALS:
+            raise ValueError(f"candidates must be 1..192 and deals 1..{L.BB_REFILL_MAX_DEALS}, not {candidates}, {deals}")
+        two_hand = {"candidates": int(candidates), "deals": int(deals)}
+    th = {"two_hand": two_hand} if two_hand else {}
     fields = L.GREEDY_FIELDS + tuple(k for k in L.TERM_FIELDS if k in terms)
     priced = fitness == "survival"
     horizon = int(moves) if horizon is None else int(horizon)
@@ -261,9 +285,9 @@ def tune(agent: str = "plan", depth: int = 3, population: int = 64, games: int =
     def objective(cand: np.ndarray, k: int) -> np.ndarray:
         sets = [_dict_of(c, fields) for c in cand]
         if not priced:
-            scores = evaluate_population(sets, games, moves, seed + k * games, eval_depth, device)
+            scores = evaluate_population(sets, games, moves, seed + k * games, eval_depth, device, **th)
             return scores.double().mean(dim=1).numpy()
-        scores, lengths, extras = _play_population(sets, games, moves, seed + k * games, eval_depth, device, True)
+        scores, lengths, extras = _play_population(sets, games, moves, seed + k * games, eval_depth, device, True, **th)
         extras_log[k] = {key: extras[key].double().mean(dim=1).tolist() for key in EXTRAS}
         return survival_fitness(scores, lengths, extras["survival"], horizon).numpy()
 
@@ -272,9 +296,9 @@ def tune(agent: str = "plan", depth: int = 3, population: int = 64, games: int =
     final_theta = np.rint(normalise(history[-1]["mean"] if history else mean0, free, scale)).astype(np.int64)
     weights = _dict_of(final_theta, fields)
     held = compare([init, weights], holdout_games, moves, seed + HOLDOUT_SEED_OFFSET, eval_depth, device,
-                   **({"census": True} if priced else {}))
+                   **({"census": True} if priced else {}), **th)
     host = device is not None and torch.device(device).type == "cpu"
-    final = {"record": "final", "agent": agent, "depth": int(depth) if agent == "plan" else None, "weights": weights,
+    final = {"record": "final", "agent": agent, "depth": int(depth) if agent != "greedy" else None, "weights": weights,
              "init": init, "fixed": list(fixed),
              "holdout": {"seed0": seed + HOLDOUT_SEED_OFFSET, "games": holdout_games, "moves": moves,
                          "init": held[0], "tuned": held[1]},
@@ -287,10 +311,15 @@ def tune(agent: str = "plan", depth: int = 3, population: int = 64, games: int =
         final["fitness"], final["horizon"] = fitness, horizon
     if terms:
         final["settings"]["terms"] = list(fields[len(L.GREEDY_FIELDS):])
+    if two_hand:
+        final["settings"].update(two_hand)
     if output:
         doc = {"agent": agent, "weights": weights}
         if agent == "plan":
             doc = {"agent": agent, "depth": int(depth), "weights": weights}
+        if agent == "plan2":
+            doc = {"agent": agent, "depth": int(depth), "candidates": int(candidates), "deals": int(deals),
+                   "seed": int(seed), "weights": weights}
         with open(output, "w") as f:
             json.dump(doc, f, indent=2)
     if log:
@@ -318,7 +347,7 @@ def tune(agent: str = "plan", depth: int = 3, population: int = 64, games: int =
 def main() -> None:
     ap = argparse.ArgumentParser(description="Tune the search agents' weights by the cross-entropy method")
     ap.add_argument("--agent", choices=("plan", "greedy", "plan2"), default="plan",
-                    help="plan2 (--compare only): the two-hand agent, a sampled look past the refill")
+                    help="plan2: the two-hand agent, a sampled look past the refill")
     ap.add_argument("--candidates", type=int, default=8, help="--agent plan2: first moves looked past the refill (untuned)")
     ap.add_argument("--deals", type=int, default=16, help="--agent plan2: next hands dealt per candidate (untuned)")
     ap.add_argument("--depth", type=int, choices=(1, 2, 3), default=3, help="--agent plan: moves searched ahead")
@@ -342,7 +371,7 @@ def main() -> None:
                     help="survival: the score discounted by the census' probability of surviving --horizon moves")
     ap.add_argument("--horizon", type=int, default=None, help="--fitness survival: moves to survive (default --moves)")
     ap.add_argument("--terms", type=str, default=None,
-                    help="--agent plan: shape terms to tune beside the eight, comma-separated names of "
+                    help="--agent plan / plan2: shape terms to tune beside the eight, comma-separated names of "
                          "perimeter,room3,room5,fits (they start at 0)")
     args = ap.parse_args()
     if args.compare:
@@ -365,13 +394,12 @@ def main() -> None:
             rec["more"] = [{"file": os.path.basename(p), **r} for p, r in zip(args.compare[1:], res[2:])]
         print(json.dumps(rec))
         return
-    if args.agent == "plan2":
-        ap.error("--agent plan2 is for --compare: the tuner's fitness does not look past the refill")
     final = tune(agent=args.agent, depth=args.depth, population=args.population, games=args.games, moves=args.moves,
                  generations=args.generations, elite_frac=args.elite_frac, seed=args.seed,
                  device=args.device, output=args.output, log=args.log, holdout_games=args.holdout_games,
                  **({"fitness": args.fitness, "horizon": args.horizon} if args.fitness != "score" else {}),
-                 **({"terms": [t for t in args.terms.split(",") if t]} if args.terms else {}))
+                 **({"terms": [t for t in args.terms.split(",") if t]} if args.terms else {}),
+                 **({"candidates": args.candidates, "deals": args.deals} if args.agent == "plan2" else {}))
     print(json.dumps(final))
 
 

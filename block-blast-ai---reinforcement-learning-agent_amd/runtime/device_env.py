@@ -440,6 +440,27 @@ class DeviceEnvBatch:
                 "bb_refill_values_ext", self.handle, self.lib)
         return out
 
+    def plan2_values(self, rows: torch.Tensor, candidates: int, deals: int, seed: int,
+                     stream: Optional[torch.Tensor] = None, depth: int = 3, want=("action",),
+                     out: Optional[dict] = None, work: Optional[torch.Tensor] = None) -> dict:
+        """bb_plan2_values on the live boards, hands and combos: the two-hand decision of every env in one
+        asynchronous call with no host read (``runtime.kernels.plan2_values`` names the steps and the outputs), env i
+        under rows[i] (or the one shared row) and stream id ``stream[i]`` (or i).  ``work``: uint8 scratch of at least
+        ``kernels.plan2_work_bytes(num_envs, candidates, deals)`` bytes on the env's device, allocated when None.
+        Reads the state and changes nothing, the piece stream included."""
+        from . import kernels as K
+
+        n = self.num_envs
+        K._refill_column("stream", stream, torch.int64, n, self.device)
+        stride = K._eval_rows("plan2_values", rows, n, self.device)
+        out, o, work, _ = K._plan2_args("plan2_values", self.lib, n, self.device, candidates, deals, depth, want, out,
+                                        work)
+        L.check(self.lib.bb_plan2_values(self.handle, _ptr(stream), _ptr(rows), stride, depth, candidates, deals,
+                                         int(seed) & (2 ** 64 - 1), _ptr(work), work.numel(), C.byref(o),
+                                         _stream(self.device)),
+                "bb_plan2_values", self.handle, self.lib)
+        return out
+
     # ------------------------------------------------------------ host copies
     def state(self) -> dict:
         n = self.num_envs

@@ -685,6 +685,83 @@ def unpack_rest(rest):
     return np.where((rest < 0) | (a2 == 0xFF), -1, a2), np.where((rest < 0) | (a3 == 0xFF), -1, a3)
 
 
+PLAN2_OUTPUTS = {"action": torch.int32, "q2": torch.int64, "cand": torch.int32, "status": torch.int32,
+                 "value": torch.int64}
+
+
+def plan2_work_bytes(n: int, candidates: int, deals: int, host: bool = False) -> int:
+    """bb_plan2_work_bytes: the scratch ``plan2_values`` needs for n positions, in bytes (both libraries give the same
+    figure; ``host`` picks the one asked).  The argument rules of the entry point, named."""
+    _plan2_sizes("plan2_work_bytes", candidates, deals, 1)
+    if not (isinstance(n, int) and n >= 0):
+        raise L.BBNativeError(f"plan2_work_bytes: n must be a non-negative int, not {n!r}")
+    return int((L.load_host() if host else L.load()).bb_plan2_work_bytes(n, candidates, deals))
+
+
+def _plan2_sizes(call: str, candidates, deals, depth) -> None:
+    if not (isinstance(candidates, int) and 1 <= candidates <= 192):
+        raise L.BBNativeError(f"{call}: candidates must be 1..192, not {candidates!r}")
+    if not (isinstance(deals, int) and 1 <= deals <= REFILL_MAX_DEALS):
+        raise L.BBNativeError(f"{call}: deals must be 1..{REFILL_MAX_DEALS}, not {deals!r}")
+    if not (isinstance(depth, int) and 1 <= depth <= 3):
+        raise L.BBNativeError(f"{call}: depth must be 1..3, not {depth!r}")
+
+
+def plan2_outputs(n: int, candidates: int, deals: int, device, want=("action",)) -> dict:
+    """Freshly allocated output tensors of ``plan2_values`` for the names in ``want``."""
+    unknown = set(want) - set(PLAN2_OUTPUTS)
+    if unknown:
+        raise L.BBNativeError(f"plan2_values: unknown outputs {sorted(unknown)}; they are {tuple(PLAN2_OUTPUTS)}")
+    shape = {"action": (n,), "q2": (n, 192), "cand": (n, candidates), "status": (n, candidates),
+             "value": (n, candidates, deals)}
+    return {k: torch.empty(shape[k], dtype=PLAN2_OUTPUTS[k], device=device) for k in want}
+
+
+def _plan2_args(call: str, lib, n: int, dev, candidates, deals, depth, want, out, work):
+    """The Python-side rules shared by ``plan2_values`` and ``DeviceEnvBatch.plan2_values``; returns (out dict,
+    struct, work tensor, bytes needed)."""
+    _plan2_sizes(call, candidates, deals, depth)
+    out = plan2_outputs(n, candidates, deals, dev, want) if out is None else out
+    table = {"action": ("action", torch.int32, 1), "q2": ("q2", torch.int64, 192),
+             "cand": ("cand", torch.int32, candidates), "status": ("status", torch.int32, candidates),
+             "value": ("value", torch.int64, candidates * deals)}
+    o = _look_out(L.Plan2Out, call, table, out, n, dev, shape="tensor of {numel} elements", at_least_one=True,
+                  known_only=True)
+    need = int(lib.bb_plan2_work_bytes(n, candidates, deals))
+    if work is None:
+        work = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
+    if not (isinstance(work, torch.Tensor) and work.dtype == torch.uint8 and work.device == dev
+            and work.is_contiguous() and work.data_ptr() % 8 == 0):
+        raise L.BBNativeError(f"{call}: work must be a contiguous, 8-byte aligned {torch.uint8} tensor on {dev}")
+    if work.numel() < need:
+        raise L.BBNativeError(f"{call}: work has {work.numel()} bytes, plan2_work_bytes asks for {need}")
+    return out, o, work, need
+
+
+def plan2_values(board: torch.Tensor, hand: torch.Tensor, rows: torch.Tensor, candidates: int, deals: int, seed: int,
+                 combo: Optional[torch.Tensor] = None, prev: Optional[torch.Tensor] = None,
+                 stream: Optional[torch.Tensor] = None, depth: int = 3, want=("action",),
+                 out: Optional[dict] = None, work: Optional[torch.Tensor] = None) -> dict:
+    """bb_plan2_values_pos: the two-hand decision of every position in one asynchronous call with no host read --
+    ``plan_values_ext``, the ``candidates`` best first moves, their leaves (``play_plan``), ``deals`` dealt next hands
+    behind every refill leaf (``refill_values_ext`` under the root's row, stream id ``stream[i]`` or i, Philox key
+    ``seed``) and the arg-max of Q2, ties to the lower action.  rows: int32 [1, 12] or [n, 12] (``eval_rows``).
+    Outputs (``want``, or the tensors of ``out`` written in place): "action" int32 [n]; "q2" int64 [n, 192]
+    (INT64_MIN outside the candidates); "cand" int32 [n, K] in rank order (-1 = absent); "status" int32 [n, K], the
+    leaf's ``play_plan`` status (-1 = absent); "value" int64 [n, K, deals] (0 where no deal was made).  ``work``: a
+    uint8 scratch tensor of at least ``plan2_work_bytes(n, candidates, deals)`` bytes where the positions are,
+    allocated when None; ``prev`` is checked like the other columns and not read."""
+    pos, n, dev = _positions(board, hand, combo, prev)
+    _refill_column("stream", stream, torch.int64, n, dev)
+    stride = _eval_rows("plan2_values", rows, n, dev)
+    lib, s = _look_lib(dev)
+    out, o, work, need = _plan2_args("plan2_values", lib, n, dev, candidates, deals, depth, want, out, work)
+    L.check(lib.bb_plan2_values_pos(C.byref(pos), _p(stream), n, _p(rows), stride, depth, candidates, deals,
+                                    int(seed) & (2 ** 64 - 1), _p(work), work.numel(), C.byref(o), s),
+            "bb_plan2_values_pos", lib=lib)
+    return out
+
+
 def mask_bits_to_bool(bits):
     """Mask words [n, 3] (int64 / uint64 bit patterns, torch or numpy) -> bool [n, 192]."""
     if isinstance(bits, torch.Tensor):

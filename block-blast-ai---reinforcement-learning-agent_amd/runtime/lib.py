@@ -179,6 +179,13 @@ class RefillValuesOut(C.Structure):
     _fields_ = [("hand", C.c_void_p), ("value", C.c_void_p), ("attempts", C.c_void_p)]
 
 
+class Plan2Out(C.Structure):
+    """bb_plan2_out: device arrays action i32 [n] / q2 i64 [n][192] / cand i32 [n][K] / status i32 [n][K] / value i64
+    [n][K][deals]; any may be NULL, not all five."""
+    _fields_ = [("action", C.c_void_p), ("q2", C.c_void_p), ("cand", C.c_void_p), ("status", C.c_void_p),
+                ("value", C.c_void_p)]
+
+
 class PlayPlanOut(C.Structure):
     """bb_play_plan_out: device arrays [n]; any may be NULL, not all six."""
     _fields_ = [("board", C.c_void_p), ("hand", C.c_void_p), ("combo", C.c_void_p), ("lines", C.c_void_p),
@@ -293,6 +300,11 @@ SIGNATURES = {
                                            C.POINTER(RefillValuesOut), _P]),
     "bb_refill_values_ext": (C.c_int, [_P, _P, _P, C.c_int64, _I32, _I32, _U64, C.POINTER(RefillValuesOut), _P]),
     "bb_play_plan_pos": (C.c_int, [C.POINTER(Positions), _I32, _P, C.POINTER(PlayPlanOut), _P]),
+    "bb_plan2_work_bytes": (C.c_int64, [_I32, _I32, _I32]),
+    "bb_plan2_values_pos": (C.c_int, [C.POINTER(Positions), _P, _I32, _P, C.c_int64, _I32, _I32, _I32, _U64, _P,
+                                      C.c_int64, C.POINTER(Plan2Out), _P]),
+    "bb_plan2_values": (C.c_int, [_P, _P, _P, C.c_int64, _I32, _I32, _I32, _U64, _P, C.c_int64,
+                                  C.POINTER(Plan2Out), _P]),
     "bb_masked_sample": (C.c_int, [_P, _P, _I32, _P, _U64, _U64, _U64, _I32, _P, _P, _P, _P, _P]),
     "bb_masked_sample_dstep": (C.c_int, [_P, _P, _I32, _U64, _P, _U64, _U64, _I32, _P, _P, _P, _P]),
     "bb_gae": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _F, _F, _P, _P, _P]),
@@ -361,7 +373,7 @@ HOST_SYMBOLS = ("bb_abi_version", "bb_build_id", "bb_create", "bb_destroy", "bb_
                 "bb_plan_values_pos", "bb_plan_values", "bb_safe_mask_pos", "bb_safe_mask",
                 "bb_refill_census_pos", "bb_refill_census", "bb_refill_values_pos", "bb_refill_values",
                 "bb_plan_values_ext_pos", "bb_plan_values_ext", "bb_refill_values_ext_pos", "bb_refill_values_ext",
-                "bb_play_plan_pos")
+                "bb_play_plan_pos", "bb_plan2_work_bytes", "bb_plan2_values_pos", "bb_plan2_values")
 
 _lib = None
 _host = None

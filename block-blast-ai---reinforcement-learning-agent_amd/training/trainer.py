@@ -307,6 +307,8 @@ def train(config: Dict[str, Any], resume_path: Optional[str] = None, seed: int =
         distill_args = dict(weights=dict(distill_cfg.get("weights") or DEFAULT_WEIGHTS),
                             depth=int(distill_cfg.get("depth", 3)), tau=float(distill_cfg.get("tau", 50.0)),
                             epochs=int(distill_cfg.get("epochs", 1)))
+        if distill_cfg.get("two_hand"):  # training.distill.two_hand: {candidates, deals[, seed]}, the two-hand teacher
+            distill_args["two_hand"] = dict(distill_cfg["two_hand"])
         if main:
             print(f"Distilling the full-hand search into the policy for the first {distill_updates} updates "
                   f"(training.distill: depth {distill_args['depth']}, tau {distill_args['tau']:g}, "
@@ -317,6 +319,8 @@ def train(config: Dict[str, Any], resume_path: Optional[str] = None, seed: int =
         search_args = dict(weights=dict(guide_cfg.get("weights") or distill_cfg.get("weights") or DEFAULT_WEIGHTS),
                            depth=int(guide_cfg.get("depth", distill_cfg.get("depth", 3))),
                            tau=float(guide_cfg.get("tau", distill_cfg.get("tau", 50.0))))
+        if guide_cfg.get("two_hand") or distill_cfg.get("two_hand"):  # training.guide.two_hand, else the distill block's
+            search_args["two_hand"] = dict(guide_cfg.get("two_hand") or distill_cfg["two_hand"])
         if main:
             sched = f"{guide_beta:g} -> {guide_final:g} over {guide_decay} updates" if guide_decay > 0 else f"{guide_beta:g}"
             print(f"Guiding PPO with the full-hand search (training.guide: beta {sched}, "
@@ -404,7 +408,8 @@ def train(config: Dict[str, Any], resume_path: Optional[str] = None, seed: int =
                 update_metrics = agent.update_guided(
                     roll.buffer, agent.values_device(roll.x), weights=distill_args["weights"],
                     depth=distill_args["depth"], tau=distill_args["tau"], coefs=(0.0, distill_value_coef, 0.0, 1.0),
-                    batch_size=local_batch, epochs=distill_args["epochs"])
+                    batch_size=local_batch, epochs=distill_args["epochs"],
+                    **({"two_hand": distill_args["two_hand"]} if "two_hand" in distill_args else {}))
             elif distilling:
                 update_metrics = agent.distill(roll.buffer, batch_size=local_batch, **distill_args)
             elif beta > 0:

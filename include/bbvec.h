@@ -72,7 +72,9 @@ extern "C" {
                                  bb_plan_actions_ext(_pos): four shape terms of a board (perimeter, room3, room5,
                                  fits) and the full-hand search with them added to every leaf's value;
                                  (additive, still 9) bb_plan_values_ext(_pos) and bb_refill_values_ext(_pos): the
-                                 per-action values and the dealt next-hand values under rows of bb_eval_weights */
+                                 per-action values and the dealt next-hand values under rows of bb_eval_weights;
+                                 (additive, still 9) bb_plan2_out with bb_plan2_values(_pos) and bb_plan2_work_bytes:
+                                 the two-hand decision (values, candidates, leaves, deals, choice) in one call */
 
 #define BB_OK 0
 #define BB_ERR_ARG (-1)
@@ -681,6 +683,62 @@ typedef struct bb_play_plan_out {
 } bb_play_plan_out;  /* device pointers (host pointers for libbbvec_host.so); any may be NULL, not all six */
 int bb_play_plan_pos(const bb_positions* pos, int32_t n, const int32_t* d_plan /* [n][3] */,
                      const bb_play_plan_out* out, void* stream);
+
+/* ---- the two-hand decision: one chance node behind the hand, in one call ---------------
+ * The search past the refill that agents/greedy.py TwoHandPlanAgent._decide composes from
+ * bb_plan_values_ext, a sort, bb_play_plan_pos and bb_refill_values_ext, with no host read
+ * in between.  Integers only; every output is defined over those entry points.  For
+ * position i with row w = d_w[i * w_stride] (rows as bb_plan_values_ext takes them):
+ *   1. q, rest = bb_plan_values_ext_pos under w and depth.
+ *   2. The candidates are the K actions with the largest q, ties to the lower action (a
+ *      stable descending sort); an action with q == INT64_MIN is never one, so fewer
+ *      legal actions give fewer candidates.
+ *   3. Candidate a's leaf is bb_play_plan_pos on (a, decoded rest[a]) from
+ *      (board, hand, combo).
+ *   4. A leaf with BB_PLAY_REFILL set gets
+ *        Q2[a] = deals * (w.base.lines * lines + w.base.score * score) + sum_j value_j
+ *      with value_j what bb_refill_values_ext_pos gives for (leaf board, leaf combo, stream
+ *      id d_stream ? d_stream[i] : i, seed, deal j) under the ROOT's row w.  All candidates
+ *      of a root share one stream id and so meet the same draws; two roots with the same
+ *      stream id share theirs.
+ *   5. Any other leaf (dead, or cut short by depth) keeps Q2[a] = deals * q[a].
+ *   6. action is the lowest action with the largest Q2, 0 when there is no candidate.
+ * Outputs:
+ *   action [n]            the decision
+ *   q2     [n][192]       Q2 of the candidates; INT64_MIN for every other action
+ *   cand   [n][K]         the candidates in rank order; -1 for an absent one
+ *   status [n][K]         bb_play_plan_pos' status word of the candidate's leaf; -1 if absent
+ *   value  [n][K][deals]  the dealt hands' values; 0 where no deal was made (absent
+ *                         candidate, or a leaf that is no refill)
+ * With the four shape weights of a row 0 the answers are those of the eight-weight calls
+ * under `base`.  d_work is caller-owned scratch of at least bb_plan2_work_bytes(n, K, deals)
+ * bytes, 8-byte aligned, in the memory of the position columns; its contents after the call
+ * are unspecified and the call allocates nothing.  bb_plan2_work_bytes is a host-side size
+ * query, negative for n < 0, candidates outside 1..192 or deals outside
+ * 1..BB_REFILL_MAX_DEALS.  n == 0 does nothing.  BB_ERR_ARG (the rule named in
+ * bb_last_error, before any HIP call) for NULL positions, n < 0, NULL rows, a w_stride that
+ * is not 0 or 1, a NULL out, all five outputs NULL, depth outside 1..3, candidates outside
+ * 1..192, deals outside 1..1024, a NULL d_work and work_bytes below the size query.  The
+ * handle form reads the live board, hand and combo columns (n is the handle's env count),
+ * changes nothing, the RNG included, and refuses a handle in BB_ERR_DEVICE / BB_ERR_STATE.
+ * Four launches on `stream`, asynchronous, no sync, no host read, 64-bit indexing,
+ * graph-capturable from the first call.  seed is passed by value: a captured graph replays
+ * the seed it was captured with, so every replay repeats its deals. */
+int64_t bb_plan2_work_bytes(int32_t n, int32_t candidates, int32_t deals);
+typedef struct bb_plan2_out {
+  int32_t* action;  /* [n]            the decision; 0 when the position has no legal action            */
+  int64_t* q2;      /* [n][192]       Q2 of the candidates; INT64_MIN for every other action           */
+  int32_t* cand;    /* [n][K]         the candidates in rank order; -1 for an absent one               */
+  int32_t* status;  /* [n][K]         bb_play_plan's status word of the candidate's leaf; -1 if absent */
+  int64_t* value;   /* [n][K][deals]  the dealt hands' values; 0 where no deal was made                */
+} bb_plan2_out;     /* device pointers (host pointers for libbbvec_host.so); any may be NULL, not all five */
+int bb_plan2_values_pos(const bb_positions* pos, const uint64_t* d_stream /* NULL = i */, int32_t n,
+                        const bb_eval_weights* d_w, int64_t w_stride, int32_t depth, int32_t candidates /* K */,
+                        int32_t deals, uint64_t seed, void* d_work, int64_t work_bytes, const bb_plan2_out* out,
+                        void* stream);
+int bb_plan2_values(bb_env* env, const uint64_t* d_stream, const bb_eval_weights* d_w, int64_t w_stride,
+                    int32_t depth, int32_t candidates, int32_t deals, uint64_t seed, void* d_work,
+                    int64_t work_bytes, const bb_plan2_out* out, void* stream);
 
 /* Fused masked-categorical tail of BlockBlastNetwork.get_action_and_value
  * (network.py:173-180, 210-262; Categorical clamp semantics of torch 2.10):
