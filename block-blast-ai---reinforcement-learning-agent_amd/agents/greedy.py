@@ -328,6 +328,47 @@ class TwoHandShapeAgent(TwoHandPlanAgent):
                                depth=self.depth)["value"]
 
 
+class PlayoutPlanAgent(TwoHandShapeAgent):
+    """``TwoHandShapeAgent`` with more than one chance node behind a refill leaf: step 4 values a candidate's leaf by
+    ``deals`` dealt playouts of ``hands`` hands each (``playout_values``: deal, search, play the plan found, deal again
+    under key seed + h) where the parent searches one dealt hand.  A playout's value is the move terms of the hands
+    it played out plus the search value of its last hand, so a board that takes one more hand well and then chokes
+    no longer looks like one that keeps taking hands.  Steps 1-3, 5 and 6 and Q2 = deals * moved + the sum of the
+    values are the parent's; the playouts always run under the twelve-weight row, which with the shape weights 0
+    gives the eight-weight answers.  With ``hands=1`` it plays what ``TwoHandShapeAgent`` plays.  The default
+    ``hands=2`` is untuned."""
+
+    def __init__(self, weights: Optional[Dict[str, int]] = None, depth: int = 3, candidates: int = 8, deals: int = 16,
+                 hands: int = 2, seed: int = 0, device=None):
+        super().__init__(weights, depth, candidates, deals, seed, device)
+        if not 1 <= int(hands) <= L.BB_PLAYOUT_MAX_HANDS:
+            raise ValueError(f"hands must be 1..{L.BB_PLAYOUT_MAX_HANDS}, not {hands}")
+        self.hands = int(hands)
+        self._rows12 = None  # the [1, 12] row of playout_values, made on first use where the boards are
+
+    def _refill_values(self, board, deals: int, seed: int, combo, stream) -> torch.Tensor:
+        from runtime import kernels as K
+
+        want = [int(self.weights.get(k, 0)) for k in L.EVAL_FIELDS]
+        if self._rows12 is None or self._rows12[0] != want or self._rows12[1].device != board.device:
+            self._rows12 = (want, K.eval_rows(self.weights, device=board.device))
+        return K.playout_values(board, self._rows12[1], deals, self.hands, seed, combo=combo, stream=stream,
+                                depth=self.depth)["value"]
+
+    def save(self, path: str) -> None:
+        with open(path, "w") as f:
+            json.dump({"agent": "playout", "depth": self.depth, "candidates": self.candidates, "deals": self.deals,
+                       "hands": self.hands, "seed": self.seed, "weights": self.weights}, f, indent=2)
+
+    def load(self, path: str) -> None:
+        super().load(path)
+        with open(path) as f:
+            hands = int(json.load(f).get("hands", self.hands))
+        if not 1 <= hands <= L.BB_PLAYOUT_MAX_HANDS:
+            raise ValueError(f"hands must be 1..{L.BB_PLAYOUT_MAX_HANDS}, not {hands}")
+        self.hands = hands
+
+
 def two_hand_agent_class(weights: Optional[Dict[str, int]]):
     """The two-hand agent for a weight set: ``TwoHandShapeAgent`` when it names a shape weight that is not 0,
     ``TwoHandPlanAgent`` otherwise (``evaluate.py --agent plan2``, ``tune.py --compare ... --agent plan2``)."""

@@ -846,6 +846,28 @@ int bb_plan2_values(bb_env* env, const uint64_t* d_stream, const bb_eval_weights
   });
 }
 
+// Dealt playouts (playout_values_kernel, csrc/bb_lookahead.hip): d_w, d_stream and the outputs are device memory
+int bb_playout_values_pos(const uint64_t* d_board, const int32_t* d_combo, const uint64_t* d_stream, int32_t n,
+                          const bb_eval_weights* d_w, int64_t w_stride, int32_t depth, int32_t playouts, int32_t hands,
+                          uint64_t seed, const bb_playout_out* out, void* stream) {
+  const char* rule = bb_look_rules::playout_values_pos(d_board, n, d_w, w_stride, depth, playouts, hands, out);
+  if (!rule && n == 0) return BB_OK;  // accepted, and nothing to do
+  return look_pos_call("bb_playout_values_pos", rule, [&] {
+    return launch_playout_values(d_board, d_combo, d_stream, n, d_w, w_stride, depth, playouts, hands, seed, *out,
+                                 (hipStream_t)stream);
+  });
+}
+
+int bb_playout_values(bb_env* env, const uint64_t* d_stream, const bb_eval_weights* d_w, int64_t w_stride,
+                      int32_t depth, int32_t playouts, int32_t hands, uint64_t seed, const bb_playout_out* out,
+                      void* stream) {
+  return look_env_call(
+      env, "bb_playout_values", bb_look_rules::playout_values(d_w, w_stride, depth, playouts, hands, out), [&] {
+        return launch_playout_values(env->d.board, env->d.combo, d_stream, env->n, d_w, w_stride, depth, playouts, hands,
+                                     seed, *out, (hipStream_t)stream);
+      });
+}
+
 int bb_masked_sample(const float* d_logits, const uint64_t* d_mask_bits, int32_t n, const float* d_uniform,
                      uint64_t seed, uint64_t step, uint64_t env_offset, int32_t deterministic,
                      const int64_t* d_action_in, int64_t* d_action, float* d_logp, float* d_entropy,

@@ -141,6 +141,11 @@ hipError_t launch_plan2_values(const uint64_t* board, const uint32_t* hand, cons
                                const uint64_t* stream_id, int n, const bb_eval_weights* rows, int64_t w_stride,
                                int depth, int candidates, int deals, uint64_t seed, void* work,
                                const bb_plan2_out& out, hipStream_t s);
+// the dealt playouts (bb_lookahead.hip): n > 0, playouts 1..1024, hands 1..256, depth 1..3; the outputs [n][playouts],
+// not all NULL
+hipError_t launch_playout_values(const uint64_t* board, const int32_t* combo, const uint64_t* stream_id, int n,
+                                 const bb_eval_weights* rows, int64_t w_stride, int depth, int playouts, int hands,
+                                 uint64_t seed, const bb_playout_out& out, hipStream_t s);
 // a plan played to its leaf (bb_lookahead.hip): n > 0, plan [n][3], the outputs [n], not all NULL
 hipError_t launch_play_plan(const uint64_t* board, const uint32_t* hand, const int32_t* combo, int n,
                             const int32_t* plan, const bb_play_plan_out& out, hipStream_t s);

@@ -821,6 +821,64 @@ void plan2_values_host(const uint64_t* board, const uint32_t* hand, const int32_
   }
 }
 
+// bbvec.h bb_playout_values (the host twin of playout_values_kernel): one (board, playout) pair per iteration; per hand
+// refill_deal under key seed + h, plan_dfs on the dealt hand (bb_plan_actions_ext's search) and play_plan_one on the
+// plan found, the board and the combo carried.
+template <class W>
+PlanBest playout_search(uint64_t B, uint32_t hand, int combo, int depth, const W& w) {
+  PlanBest best{INT64_MIN, {-1, -1, -1}, 0, false};
+  int32_t seq[3];
+  plan_dfs(B, hand, combo, depth, 0, 0, seq, w, best);
+  return best;
+}
+
+void playout_values_host(const uint64_t* board, const int32_t* combo, const uint64_t* stream_id, int32_t n,
+                         const bb_eval_weights* rows, int64_t w_stride, int depth, int32_t playouts, int32_t hands,
+                         uint64_t seed, const bb_playout_out& out) {
+  const int64_t pairs = (int64_t)n * playouts;
+#pragma omp parallel for schedule(dynamic, 1)  // the playouts end after different numbers of hands
+  for (int64_t k = 0; k < pairs; ++k) {
+    const int64_t i = k / playouts, j = k % playouts;
+    const uint64_t idx = stream_id ? stream_id[i] : (uint64_t)i;
+    const bb_eval_weights w = rows[i * w_stride];
+    uint64_t B = board[i];
+    int cb = combo ? combo[i] : 0;
+    int64_t moved = 0, score = 0, value = 0;
+    int32_t lines = 0, plies = 0, searched = 0;
+    uint32_t dealt = 0u, status = 0u;
+    for (int32_t h = 0; h < hands; ++h) {
+      int32_t attempts;
+      dealt = refill_deal(B, seed + (uint64_t)h, idx, j, attempts);
+      const PlanBest best = shaped(w) ? playout_search(B, dealt, cb, depth, w) : playout_search(B, dealt, cb, depth, w.base);
+      searched = h + 1;
+      if (!best.leaves) {  // no legal first move: nothing is played
+        value = moved + (int64_t)w.base.dead;
+        status = 0u;
+        break;
+      }
+      value = moved + best.value;
+      const Leaf f = play_plan_one(B, dealt, cb, best.plan);
+      B = f.board;
+      cb = f.combo;
+      lines += f.lines;
+      score += f.score;
+      plies += (int32_t)(f.status & BB_PLAY_PLIES);
+      status = f.status;
+      if (!(status & BB_PLAY_REFILL)) break;  // a dead leaf, or a plan cut short by depth < 3
+      moved += (int64_t)w.base.lines * f.lines + (int64_t)w.base.score * f.score;
+    }
+    if (out.value) out.value[k] = value;
+    if (out.score) out.score[k] = score;
+    if (out.lines) out.lines[k] = lines;
+    if (out.plies) out.plies[k] = plies;
+    if (out.hands) out.hands[k] = searched;
+    if (out.status) out.status[k] = (int32_t)status;
+    if (out.board) out.board[k] = B;
+    if (out.combo) out.combo[k] = cb;
+    if (out.hand) out.hand[k] = dealt;
+  }
+}
+
 }  // namespace
 
 #ifndef BB_BUILD_ID
@@ -1332,6 +1390,29 @@ int bb_plan2_values(bb_env* env, const uint64_t* d_stream, const bb_eval_weights
     return rc;
   plan2_values_host(env->board.data(), env->hand.data(), env->combo.data(), d_stream, env->n, d_w, w_stride, depth,
                     candidates, deals, seed, d_work, *out);
+  return BB_OK;
+}
+
+int bb_playout_values_pos(const uint64_t* d_board, const int32_t* d_combo, const uint64_t* d_stream, int32_t n,
+                          const bb_eval_weights* d_w, int64_t w_stride, int32_t depth, int32_t playouts, int32_t hands,
+                          uint64_t seed, const bb_playout_out* out, void* stream) {
+  (void)stream;
+  if (int rc = refused(nullptr, "bb_playout_values_pos",
+                       R::playout_values_pos(d_board, n, d_w, w_stride, depth, playouts, hands, out)))
+    return rc;
+  playout_values_host(d_board, d_combo, d_stream, n, d_w, w_stride, depth, playouts, hands, seed, *out);
+  return BB_OK;
+}
+
+int bb_playout_values(bb_env* env, const uint64_t* d_stream, const bb_eval_weights* d_w, int64_t w_stride,
+                      int32_t depth, int32_t playouts, int32_t hands, uint64_t seed, const bb_playout_out* out,
+                      void* stream) {
+  (void)stream;
+  if (!env) return BB_ERR_ARG;
+  if (int rc = refused(env, "bb_playout_values", R::playout_values(d_w, w_stride, depth, playouts, hands, out)))
+    return rc;
+  playout_values_host(env->board.data(), env->combo.data(), d_stream, env->n, d_w, w_stride, depth, playouts, hands,
+                      seed, *out);
   return BB_OK;
 }
 

@@ -1,4 +1,4 @@
-// bb_look_rules.h -- the argument rules of the twenty-nine lookahead entry points of include/bbvec.h, one copy for
+// bb_look_rules.h -- the argument rules of the thirty-one lookahead entry points of include/bbvec.h, one copy for
 // both backends (csrc/bb_capi.cpp and csrc/bb_host.cpp).  Plain C++, nothing from HIP.
 //
 // Each function returns the rule an argument set breaks, as the text that follows "<entry point>: " in
@@ -9,7 +9,7 @@
 // bb_plan_actions(_each)_pos refuse n == 0 and answer every broken rule with one text; bb_plan_values_pos accepts n == 0
 // (and does nothing) and names the rule that broke, and so do bb_safe_mask_pos, bb_refill_census_pos,
 // bb_refill_values_pos, bb_play_plan_pos, bb_board_terms_pos, bb_plan_actions_ext_pos, bb_plan_values_ext_pos,
-// bb_refill_values_ext_pos and bb_plan2_values_pos.
+// bb_refill_values_ext_pos, bb_plan2_values_pos and bb_playout_values_pos.
 #pragma once
 #include <stdint.h>
 
@@ -238,6 +238,27 @@ inline const char* plan2_values_pos(const bb_positions* pos, int32_t n, const bb
                                     int64_t work_bytes, const bb_plan2_out* out) {
   if (no_positions(pos)) return "positions (board, hand) are NULL";
   return plan2_values(n, d_w, w_stride, depth, candidates, deals, d_work, work_bytes, out);
+}
+
+// the dealt playouts (bb_playout_values): the rules of bb_refill_values_ext with playouts for deals, and the hand count
+inline const char* playout_values(const bb_eval_weights* d_w, int64_t w_stride, int32_t depth, int32_t playouts,
+                                  int32_t hands, const bb_playout_out* out) {
+  if (!d_w) return "weight rows are NULL";
+  if (w_stride != 0 && w_stride != 1) return "w_stride must be 0 or 1";
+  if (!out) return "out is NULL";
+  if (!out->value && !out->score && !out->lines && !out->plies && !out->hands && !out->status && !out->board &&
+      !out->combo && !out->hand)
+    return "all nine outputs are NULL";
+  if (bad_depth(depth)) return "depth must be 1..3";
+  if (playouts < 1 || playouts > BB_REFILL_MAX_DEALS) return "playouts must be 1..1024";
+  if (hands < 1 || hands > BB_PLAYOUT_MAX_HANDS) return "hands must be 1..256";
+  return nullptr;
+}
+inline const char* playout_values_pos(const uint64_t* board, int32_t n, const bb_eval_weights* d_w, int64_t w_stride,
+                                      int32_t depth, int32_t playouts, int32_t hands, const bb_playout_out* out) {
+  if (!board) return "board is NULL";
+  if (n < 0) return "n is negative";
+  return playout_values(d_w, w_stride, depth, playouts, hands, out);
 }
 
 }  // namespace bb_look_rules

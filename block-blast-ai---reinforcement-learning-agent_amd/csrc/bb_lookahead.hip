@@ -1065,6 +1065,147 @@ refill_values_ext_kernel(LookTable t, RefillCols cols, int n, int m, const bb_ev
 }
 
 // ---------------------------------------------------------------------------
+// Dealt playouts (bbvec.h bb_playout_values): refill_values_ext_kernel's pair, carried on for `hands` hands.  For
+// (board i, playout j): deal under key seed + h, search the dealt hand, play the plan found, deal again on the board
+// reached -- the plan agent under a counter-based dealer, the board held by the workgroup from the first deal to the
+// last ply.
+//
+// refill_values_ext_kernel's frame: one workgroup of four waves per (board, playout) pair, the same two-digit stride
+// above kRefillMaxGrid, the row read per pair into scalar registers, the `shaped` branch the workgroup's.  Inside the
+// pair loop, per hand:
+//   deal    refill_deal as it stands, its key seed + h (unsigned: it wraps mod 2^64).
+//   search  plan_search<W> on either side of the branch, plan_wave_join, and lane 0 of each wave posts its (value, key)
+//           in s_v / s_key.
+//   join    after one barrier EVERY lane reads the four slots and joins them under take_plan, so the whole workgroup
+//           holds the same (value, key), told to be uniform: the plan is in scalar registers.
+//   play    the up to three plies of the key with eval_action on workgroup-uniform arguments (every lane computes the
+//           same afterstate; the piece rows are scalar loads).  The state reached goes back into scalar registers.
+// "No legal first move", "the leaf is no refill" and "this was the last hand" are therefore one answer for the
+// workgroup: all four waves leave the hand loop together, and every barrier inside refill_deal and plan_compact is met
+// by all of them.  Thread 0 stores the nine outputs once per pair.
+//
+// LDS reuse.  s_v / s_key are written by the lanes 0 before the join barrier and read by every lane after it; nothing
+// else reads them.  Their next writes come
+//   across hands   after the next hand's refill_deal (its first round always runs and has a barrier) and the two
+//                  barriers of plan_compact;
+//   across pairs   the same: the next pair opens with refill_deal;
+//   on the early exit with no legal first move   the same again: the break leads to the stores and the next pair's
+//                  refill_deal, or out of the kernel.
+// A wave reaches any of those barriers only after its own reads of the slots, which precede them in program order, so
+// the first barrier of the next refill_deal separates every read from the next write.  s_deal, s_cnt and s_rec are
+// used as refill_values_ext_kernel uses them; between a hand's last read of them and the next hand's first write lies
+// at least the join barrier.
+// Trip bounds: `hands` <= 256 times (25 rounds, 3 first pieces, 64 pair trips; <= 192 records, 3 slots, 64 mask bits;
+// 3 plies).  No atomics, no inline assembly, nothing between workgroups.
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(kPlanBlock)
+playout_values_kernel(LookTable t, RefillCols cols, int n, int m, const bb_eval_weights* __restrict__ rows,
+                      int64_t w_stride, int depth, int hands, uint64_t seed, bb_playout_out out) {
+  __shared__ PlanRecord s_rec[kPlanRecords];
+  __shared__ int s_cnt[kHand];
+  __shared__ int64_t s_v[kPlanWaves];
+  __shared__ uint32_t s_key[kPlanWaves];
+  __shared__ uint32_t s_deal[2][kPlanWaves];
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int cell = (int)(threadIdx.x & 63u);
+  const uint32_t um = (uint32_t)m;                                   // 1..1024
+  const uint32_t gi = gridDim.x / um, gj = gridDim.x - gi * um;      // the stride in (i, j)
+  int64_t i = (int64_t)(blockIdx.x / um);
+  uint32_t j = blockIdx.x - (uint32_t)i * um;
+  while (i < (int64_t)n) {
+    uint64_t B = uniform64(cols.board[i]);
+    int combo = (int)uniform32(cols.combo ? (uint32_t)cols.combo[i] : 0u);
+    const uint64_t idx = cols.stream ? uniform64(cols.stream[i]) : (uint64_t)i;
+    const bb_eval_weights w = load_eval_weights(rows, i * w_stride);  // every playout of board i: board i's row
+    const bool shaped = (w.perimeter | w.room3 | w.room5 | w.fits) != 0;  // scalar: one answer for the workgroup
+
+    int64_t moved = 0, score = 0, value = 0;
+    int lines = 0, plies = 0, searched = 0;
+    uint32_t ids = 0u, status = 0u;
+#pragma unroll 1
+    for (int h = 0; h < hands; ++h) {
+      // ---- the deal
+      int attempts;
+      refill_deal(t, B, seed + (uint64_t)h, idx, j, wave, cell, s_deal, ids, attempts);
+
+      // ---- the search of the dealt hand (plan_ext_kernel's two sides)
+      const Position P{B, ids, combo};
+      int64_t best = INT64_MIN;  // below every legal value (see greedy_kernel)
+      uint32_t best_key = kPlanNoKey;
+      int leaves = 0;
+      if (shaped)
+        plan_search(t, P, w, depth, wave, cell, s_rec, s_cnt, best, best_key, leaves);
+      else
+        plan_search(t, P, w.base, depth, wave, cell, s_rec, s_cnt, best, best_key, leaves);
+      plan_wave_join(best, best_key, leaves);
+      if (cell == 0) {
+        s_v[wave] = best;
+        s_key[wave] = best_key;
+      }
+      __syncthreads();
+
+      // ---- the join, by every lane: one (value, key) for the workgroup
+      best = s_v[0];
+      best_key = s_key[0];
+#pragma unroll
+      for (int k = 1; k < kPlanWaves; ++k) take_plan(best, best_key, s_v[k], s_key[k]);
+      best = (int64_t)uniform64((uint64_t)best);
+      best_key = uniform32(best_key);
+      searched = h + 1;
+      if (best_key == kPlanNoKey) {  // no legal first move: nothing is played
+        value = moved + (int64_t)w.base.dead;
+        status = 0u;
+        break;
+      }
+      value = moved + best;
+
+      // ---- the plan played (play_plan_kernel's plies; every entry is legal: the search placed it)
+      uint32_t hand = ids;
+      int64_t m_h = 0;
+#pragma unroll 1
+      for (int k = 0; k < kHand; ++k) {
+        const uint32_t act = (best_key >> (16 - 8 * k)) & 0xFFu;
+        if (act == 0xFFu) break;  // a ply not played
+        const int p = (int)(act >> 6);
+        const After a = eval_action(t, B, hand, combo, p, (int)(act & 63u));
+        B = uniform64(a.board);
+        hand = hand_use(hand, p);
+        combo = (int)uniform32((uint32_t)a.combo1);
+        const int l = (int)uniform32((uint32_t)a.lines);
+        const int64_t g = (int64_t)uniform64((uint64_t)(int64_t)a.gained);
+        lines += l;
+        score += g;
+        ++plies;
+        m_h += (int64_t)w.base.lines * l + (int64_t)w.base.score * g;
+        status = uniform32((uint32_t)(k + 1) | (a.dead ? BB_PLAY_DEAD : 0u) | (a.refill ? BB_PLAY_REFILL : 0u));
+      }
+      if (!(status & BB_PLAY_REFILL)) break;  // a dead leaf, or a plan cut short by depth < 3
+      moved += m_h;  // used by the next hand alone: the last hand's value is already in place
+    }
+
+    if (threadIdx.x == 0) {
+      const int64_t o = i * (int64_t)m + (int64_t)j;
+      if (out.value) out.value[o] = value;
+      if (out.score) out.score[o] = score;
+      if (out.lines) out.lines[o] = lines;
+      if (out.plies) out.plies[o] = plies;
+      if (out.hands) out.hands[o] = searched;
+      if (out.status) out.status[o] = (int32_t)status;
+      if (out.board) out.board[o] = B;
+      if (out.combo) out.combo[o] = combo;
+      if (out.hand) out.hand[o] = ids;
+    }
+
+    j += gj;
+    i += (int64_t)gi;
+    if (j >= um) {
+      j -= um;
+      ++i;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // A plan played to its leaf (bbvec.h bb_play_plan_pos): one lane per position, up to three one-ply moves
 // (eval_action, the move of every kernel above).  The pieces differ from lane to lane, so the table is copied into
 // LDS once per workgroup, as census_kernel does.  Trip bound: 3 plies.  No atomics, no inline assembly.
@@ -1502,6 +1643,17 @@ hipError_t launch_plan2_values(const uint64_t* board, const uint32_t* hand, cons
   if (st != hipSuccess) return st;
   hipLaunchKernelGGL(plan2_pick_kernel, wave_grid, dim3(kPlan2Block), 0, s, n, candidates, deals, wk, out.action,
                      out.q2);
+  return hipGetLastError();
+}
+
+hipError_t launch_playout_values(const uint64_t* board, const int32_t* combo, const uint64_t* stream_id, int n,
+                                 const bb_eval_weights* rows, int64_t w_stride, int depth, int playouts, int hands,
+                                 uint64_t seed, const bb_playout_out& out, hipStream_t s) {
+  const RefillCols cols{board, combo, stream_id};
+  const int64_t pairs = (int64_t)n * playouts;
+  const dim3 grid((unsigned)(pairs < kRefillMaxGrid ? pairs : kRefillMaxGrid));
+  hipLaunchKernelGGL(playout_values_kernel, grid, dim3(kPlanBlock), 0, s, look_table(), cols, n, playouts, rows,
+                     w_stride, depth, hands, seed, out);
   return hipGetLastError();
 }
 

@@ -17,6 +17,8 @@ fused one-ply kernel); every other agent goes through ``act_device`` as before.
 
 ``--agent plan2`` is ``TwoHandPlanAgent``: the full-hand search with a sampled look past the refill
 (``--candidates`` first moves, ``--deals`` dealt next hands each, ``bb_refill_values``; both defaults are untuned).
+``--agent playout`` is ``PlayoutPlanAgent``: the same with every deal carried on for ``--hands`` hands
+(``bb_playout_values``: deal, search, play the plan, deal again; the default 2 is untuned).
 
 ``--safe-mask`` (off by default) restricts the policy to hand-safe actions: the legal moves after which the rest of
 the hand can still be placed in some order (``bb_plan_values``' safe words, from ``bb_safe_mask``: one more launch per move).  For
@@ -234,15 +236,18 @@ def print_results(results: Dict[str, Any]) -> None:
 def main() -> None:
     """evaluate.py:119-184 (same flags)."""
     ap = argparse.ArgumentParser(description="Evaluate Block Blast AI")
-    ap.add_argument("--agent", choices=("ppo", "greedy", "plan", "plan2", "random"), default="ppo",
+    ap.add_argument("--agent", choices=("ppo", "greedy", "plan", "plan2", "playout", "random"), default="ppo",
                     help="ppo: the checkpoint's policy; greedy / plan / plan2 / random: the untrained baselines "
                          "(plan: exhaustive search over the whole hand; plan2: that search with a sampled look past "
-                         "the refill, dealt next hands searched below its best first moves)")
+                         "the refill, dealt next hands searched below its best first moves; playout: plan2 with "
+                         "every deal played on for --hands hands)")
     ap.add_argument("--depth", type=int, choices=(1, 2, 3), default=3, help="--agent plan / plan2: moves searched ahead")
     ap.add_argument("--candidates", type=int, default=8,
                     help="--agent plan2: first moves looked past the refill (untuned default)")
     ap.add_argument("--deals", type=int, default=16,
-                    help="--agent plan2: next hands dealt per candidate (untuned default)")
+                    help="--agent plan2 / playout: next hands dealt per candidate (untuned default)")
+    ap.add_argument("--hands", type=int, default=2,
+                    help="--agent playout: hands dealt, searched and played per playout (untuned default)")
     ap.add_argument("--checkpoint", type=str, default=None, help="required for --agent ppo")
     ap.add_argument("--episodes", type=int, default=100)
     ap.add_argument("--deterministic", action="store_true")
@@ -273,7 +278,7 @@ def main() -> None:
         agent.load(args.checkpoint)
         print(f"Loaded model from {args.checkpoint}")
     else:
-        from agents.greedy import GreedyAgent, HandPlanAgent, RandomAgent, two_hand_agent_class
+        from agents.greedy import GreedyAgent, HandPlanAgent, PlayoutPlanAgent, RandomAgent, two_hand_agent_class
 
         if args.agent == "plan":
             agent = HandPlanAgent(device=args.device)
@@ -283,15 +288,21 @@ def main() -> None:
                 with open(args.weights) as f:
                     named = json.load(f).get("weights")
             agent = two_hand_agent_class(named)(seed=args.seed, device=args.device)
+        elif args.agent == "playout":
+            agent = PlayoutPlanAgent(seed=args.seed, device=args.device)
         else:
             agent = (GreedyAgent(device=args.device) if args.agent == "greedy"
                      else RandomAgent(device=args.device, safe=args.safe_mask))
         if args.weights:
             agent.load(args.weights)
-        if args.agent in ("plan", "plan2"):
+        if args.agent in ("plan", "plan2", "playout"):
             agent.depth = args.depth
-        if args.agent == "plan2":  # the command line decides, as it does for --depth
+        if args.agent in ("plan2", "playout"):  # the command line decides, as it does for --depth
             agent.candidates, agent.deals = args.candidates, args.deals
+        if args.agent == "playout":
+            if not 1 <= args.hands <= 256:
+                ap.error("--hands must be 1..256")
+            agent.hands = args.hands
         print(f"Baseline agent: {args.agent}" + (" (hand-safe actions)" if getattr(agent, "safe", False) else ""))
     res = evaluate_agent(agent, num_episodes=args.episodes, deterministic=args.deterministic, render=args.render,
                          seed=args.seed, max_moves=args.max_moves, safe_mask=args.safe_mask,

@@ -13,7 +13,10 @@ per move serves the whole population, every env with the weights of its candidat
                          probability of surviving ``horizon`` moves; writes the agents' weights JSON and a JSONL log
 ``compare``              score per move of several weight sets on shared held-out games
 ``compare_two_hand``     the same records with every set played by a ``TwoHandPlanAgent`` (``--compare ... --agent
-                         plan2 --candidates K --deals M``; both defaults, 8 and 16, are untuned)
+                         plan2 --candidates K --deals M``; both defaults, 8 and 16, are untuned), or with ``--agent
+                         playout --hands H`` by a ``PlayoutPlanAgent`` (H untuned as well)
+``playout_scores``       whole games of the plan agent under a counter-based dealer, every candidate and game in one
+                         ``bb_playout_values`` launch; ``tune(engine="playout")`` takes a generation's fitness from it
 
 Every default below (population 64, 8 games, 300 moves, 30 generations, elite fraction 0.25, sigma0 300, scale 1000,
 sigma floor 10, 32 held-out games, ``dead`` fixed, and for ``fitness="survival"`` the form score * survival **
@@ -193,16 +196,23 @@ def _compare_records(weight_dicts, scores, lengths, extras, games: int, moves: i
 
 
 def compare_two_hand(weight_dicts: Sequence[Dict[str, int]], games: int, moves: int, seed: int, depth: int = 3,
-                     candidates: int = 8, deals: int = 16, device=None, census: bool = False) -> List[dict]:
+                     candidates: int = 8, deals: int = 16, device=None, census: bool = False,
+                     hands: Optional[int] = None) -> List[dict]:
     """``compare`` with every weight set played by a ``TwoHandPlanAgent(depth, candidates, deals)`` (``--agent
     plan2``): the same games (seeds seed + g) and the same records.  The agent takes one weight set, so the sets are
     played one after another, ``games`` envs each, and every agent's deals are keyed by ``seed``.  A set that names a
-    shape weight other than 0 is played by a ``TwoHandShapeAgent``."""
-    from agents.greedy import two_hand_agent_class
+    shape weight other than 0 is played by a ``TwoHandShapeAgent``.  ``hands`` (``--agent playout --hands H``): every
+    set is played by a ``PlayoutPlanAgent`` of that many hands per dealt playout instead."""
+    from agents.greedy import PlayoutPlanAgent, two_hand_agent_class
 
     rows = []
     for w in weight_dicts:
-        agent = two_hand_agent_class(w)(w, depth=depth, candidates=candidates, deals=deals, seed=seed, device=device)
+        if hands is not None:
+            agent = PlayoutPlanAgent(w, depth=depth, candidates=candidates, deals=deals, hands=int(hands), seed=seed,
+                                     device=device)
+        else:
+            agent = two_hand_agent_class(w)(w, depth=depth, candidates=candidates, deals=deals, seed=seed,
+                                            device=device)
         rows.append(evaluate_agent(agent, num_episodes=int(games), seeds=[seed + g for g in range(int(games))],
                                    max_moves=int(moves), **({"census": True} if census else {})))
     scores = torch.tensor([r["scores"] for r in rows], dtype=torch.int64)
@@ -214,12 +224,34 @@ def compare_two_hand(weight_dicts: Sequence[Dict[str, int]], games: int, moves: 
     return _compare_records(weight_dicts, scores, lengths, extras, games, moves)
 
 
+def playout_scores(rows: torch.Tensor, games: int, hands: int, seed: int, depth: int = 3, device=None):
+    """Whole games of the plan agent under a counter-based dealer, all in one ``bb_playout_values`` launch: from N
+    empty boards, board i under rows[i] (int32 [N, 12], ``runtime.kernels.eval_rows``), ``games`` playouts of up to
+    ``hands`` hands each, stream id 0 for every board -- candidate i's game g meets the hands candidate j's game g
+    meets, as long as both accept them (common random numbers).  Game g of every candidate is dealt hand h as deal g
+    under Philox key seed + h.  Returns (score, plies, status), int64 / int32 / int32 [N, games] where the rows were
+    moved to (``device``, default the GPU): the score and the plies played when the game stopped, and the last hand's
+    status word (``K.PLAY_REFILL`` set: the game outlived all ``hands`` hands).  The dealer is not the env's: a hand is
+    the first of 100 Philox draws that can be placed in some order (``refill_values``), never an env's PCG64 stream,
+    so these scores rank candidates and are not the scores ``evaluate_population`` reports."""
+    from runtime.device_env import resolve_device
+
+    dev = resolve_device(device)
+    rows = rows.to(dev).contiguous()
+    n = rows.shape[0]
+    board = torch.zeros(n, dtype=torch.int64, device=dev)
+    stream = torch.zeros(n, dtype=torch.int64, device=dev)
+    out = K.playout_values(board, rows, int(games), int(hands), seed, stream=stream, depth=int(depth),
+                           want=("score", "plies", "status"))
+    return out["score"], out["plies"], out["status"]
+
+
 def tune(agent: str = "plan", depth: int = 3, population: int = 64, games: int = 8, moves: int = 300,
          generations: int = 30, elite_frac: float = 0.25, seed: int = 1, init: Optional[Dict[str, int]] = None,
          fixed: Sequence[str] = ("dead",), device=None, output: Optional[str] = None, log: Optional[str] = None,
          sigma0: float = 300.0, scale: float = 1000, sigma_floor: float = 10, holdout_games: int = 32,
          fitness: str = "score", horizon: Optional[int] = None, terms: Sequence[str] = (), candidates: int = 8,
-         deals: int = 16) -> dict:
+         deals: int = 16, engine: str = "env") -> dict:
     """CEM over the weights of ``HandPlanAgent(depth)`` (agent "plan"), ``GreedyAgent`` (agent "greedy") or the two-hand
     agent (agent "plan2": ``TwoHandPlanAgent`` / ``TwoHandShapeAgent`` with ``candidates`` and ``deals``, the population
     played by ``PopulationTwoHandAgent``, env e on stream id e % games, every generation's deals keyed by its game seed,
@@ -249,7 +281,23 @@ def tune(agent: str = "plan", depth: int = 3, population: int = 64, games: int =
     ``terms``: names of ``L.TERM_FIELDS`` (perimeter, room3, room5, fits) to add to the searched vector (agent "plan"
     only: the search with them is ``bb_plan_actions_ext``).  They start at init's value, 0 by default, and share
     sigma0 and the normalisation with the eight; the dicts of the records then carry them and the settings name
-    them.  With no terms every record, candidate and random draw is what it was."""
+    them.  With no terms every record, candidate and random draw is what it was.
+
+    ``engine="playout"`` (agent "plan", fitness "score"): a generation's fitness is the row mean of
+    ``playout_scores`` -- every candidate's ``games`` games of hands = ceil(moves / 3) hands in one launch, under the
+    counter-based dealer and keyed by ``TwoHandPlanAgent.deal_seed(seed, k)`` for generation k -- where the default
+    engine "env" plays the envs move by move.  The held-out comparison is played by the envs either way, and the final
+    record's settings name the engine and the hands.  What the engine does to the weights found is unmeasured."""
+    if engine not in ("env", "playout"):
+        raise ValueError(f"engine must be 'env' or 'playout', not {engine!r}")
+    playout_hands = 0
+    if engine == "playout":
+        if agent != "plan" or fitness != "score":
+            raise ValueError("engine 'playout' plays the plan agent for its score: agent 'plan', fitness 'score'")
+        playout_hands = -(-int(moves) // 3)
+        if not 1 <= playout_hands <= L.BB_PLAYOUT_MAX_HANDS:
+            raise ValueError(f"engine 'playout': hands must be 1..{L.BB_PLAYOUT_MAX_HANDS}, not ceil({moves} / 3) = "
+                             f"{playout_hands}")
     if fitness not in ("score", "survival"):
         raise ValueError(f"fitness must be 'score' or 'survival', not {fitness!r}")
     terms = tuple(terms)
@@ -284,6 +332,12 @@ def tune(agent: str = "plan", depth: int = 3, population: int = 64, games: int =
 
     def objective(cand: np.ndarray, k: int) -> np.ndarray:
         sets = [_dict_of(c, fields) for c in cand]
+        if playout_hands:
+            from agents.greedy import TwoHandPlanAgent
+
+            score, _, _ = playout_scores(K.eval_rows(sets), games, playout_hands,
+                                         TwoHandPlanAgent.deal_seed(seed, k), eval_depth, device)
+            return score.double().mean(dim=1).cpu().numpy()
         if not priced:
             scores = evaluate_population(sets, games, moves, seed + k * games, eval_depth, device, **th)
             return scores.double().mean(dim=1).numpy()
@@ -313,6 +367,8 @@ def tune(agent: str = "plan", depth: int = 3, population: int = 64, games: int =
         final["settings"]["terms"] = list(fields[len(L.GREEDY_FIELDS):])
     if two_hand:
         final["settings"].update(two_hand)
+    if playout_hands:
+        final["settings"].update(engine=engine, hands=playout_hands)
     if output:
         doc = {"agent": agent, "weights": weights}
         if agent == "plan":
@@ -346,8 +402,13 @@ def tune(agent: str = "plan", depth: int = 3, population: int = 64, games: int =
 
 def main() -> None:
     ap = argparse.ArgumentParser(description="Tune the search agents' weights by the cross-entropy method")
-    ap.add_argument("--agent", choices=("plan", "greedy", "plan2"), default="plan",
-                    help="plan2: the two-hand agent, a sampled look past the refill")
+    ap.add_argument("--agent", choices=("plan", "greedy", "plan2", "playout"), default="plan",
+                    help="plan2: the two-hand agent, a sampled look past the refill; playout (--compare only): the "
+                         "same with --hands dealt hands per playout")
+    ap.add_argument("--hands", type=int, default=2, help="--compare --agent playout: hands per dealt playout (untuned)")
+    ap.add_argument("--engine", choices=("env", "playout"), default="env",
+                    help="playout: a generation's fitness from one bb_playout_values launch (agent plan, hands = "
+                         "ceil(moves / 3) <= 256) instead of the envs played move by move")
     ap.add_argument("--candidates", type=int, default=8, help="--agent plan2: first moves looked past the refill (untuned)")
     ap.add_argument("--deals", type=int, default=16, help="--agent plan2: next hands dealt per candidate (untuned)")
     ap.add_argument("--depth", type=int, choices=(1, 2, 3), default=3, help="--agent plan: moves searched ahead")
@@ -379,27 +440,33 @@ def main() -> None:
         for path in args.compare:
             with open(path) as f:
                 others.append(json.load(f)["weights"])
-        if args.agent == "plan2":
+        if args.agent in ("plan2", "playout"):
             res = compare_two_hand([dict(DEFAULT_WEIGHTS), *others], args.games, args.moves, args.seed, args.depth,
-                                   args.candidates, args.deals, args.device, **({"census": True} if args.census else {}))
+                                   args.candidates, args.deals, args.device, **({"census": True} if args.census else {}),
+                                   **({"hands": args.hands} if args.agent == "playout" else {}))
         else:
             res = compare([dict(DEFAULT_WEIGHTS), *others], args.games, args.moves, args.seed,
                           _agent_depth(args.agent, args.depth), args.device,
                           **({"census": True} if args.census else {}))
         rec = {"record": "compare", "seed0": args.seed, "games": args.games, "moves": args.moves,
                "agent": args.agent, "depth": args.depth, "init": res[0], "other": res[1]}
-        if args.agent == "plan2":
+        if args.agent in ("plan2", "playout"):
             rec.update(candidates=args.candidates, deals=args.deals)
+        if args.agent == "playout":
+            rec.update(hands=args.hands)
         if len(res) > 2:
             rec["more"] = [{"file": os.path.basename(p), **r} for p, r in zip(args.compare[1:], res[2:])]
         print(json.dumps(rec))
         return
+    if args.agent == "playout":
+        ap.error("--agent playout is offered with --compare; to tune through playouts use --agent plan --engine playout")
     final = tune(agent=args.agent, depth=args.depth, population=args.population, games=args.games, moves=args.moves,
                  generations=args.generations, elite_frac=args.elite_frac, seed=args.seed,
                  device=args.device, output=args.output, log=args.log, holdout_games=args.holdout_games,
                  **({"fitness": args.fitness, "horizon": args.horizon} if args.fitness != "score" else {}),
                  **({"terms": [t for t in args.terms.split(",") if t]} if args.terms else {}),
-                 **({"candidates": args.candidates, "deals": args.deals} if args.agent == "plan2" else {}))
+                 **({"candidates": args.candidates, "deals": args.deals} if args.agent == "plan2" else {}),
+                 **({"engine": args.engine} if args.engine != "env" else {}))
     print(json.dumps(final))
 
 

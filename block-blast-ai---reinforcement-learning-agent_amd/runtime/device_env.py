@@ -461,6 +461,23 @@ class DeviceEnvBatch:
                 "bb_plan2_values", self.handle, self.lib)
         return out
 
+    def playout_values(self, rows: torch.Tensor, playouts: int, hands: int, seed: int,
+                       stream: Optional[torch.Tensor] = None, depth: int = 3, want=("value",),
+                       out: Optional[dict] = None) -> dict:
+        """bb_playout_values on the live boards and combos: ``playouts`` dealt playouts of ``hands`` hands per env in
+        one launch (``runtime.kernels.playout_values`` names the steps and the outputs), every playout of env i under
+        rows[i] (or the one shared row) and stream id ``stream[i]`` (or i).  Reads the state and changes nothing, the
+        piece stream included."""
+        from . import kernels as K
+
+        K._refill_column("stream", stream, torch.int64, self.num_envs, self.device)
+        out, o = K._playout_args(playouts, hands, depth, out, self.num_envs, self.device, want)
+        stride = K._eval_rows("playout_values", rows, self.num_envs, self.device)
+        L.check(self.lib.bb_playout_values(self.handle, _ptr(stream), _ptr(rows), stride, depth, playouts, hands,
+                                           int(seed) & (2 ** 64 - 1), C.byref(o), _stream(self.device)),
+                "bb_playout_values", self.handle, self.lib)
+        return out
+
     # ------------------------------------------------------------ host copies
     def state(self) -> dict:
         n = self.num_envs

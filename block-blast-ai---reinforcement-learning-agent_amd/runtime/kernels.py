@@ -639,6 +639,65 @@ def refill_values_ext(board: torch.Tensor, rows: torch.Tensor, deals: int, seed:
     return out
 
 
+PLAYOUT_MAX_HANDS = L.BB_PLAYOUT_MAX_HANDS
+PLAYOUT_OUTPUTS = {"value": torch.int64, "score": torch.int64, "lines": torch.int32, "plies": torch.int32,
+                   "hands": torch.int32, "status": torch.int32, "board": torch.int64, "combo": torch.int32,
+                   "hand": torch.int32}
+
+
+def playout_outputs(n: int, playouts: int, dev, want=("value",)) -> dict:
+    """Fresh [n, playouts] output tensors for ``playout_values`` (board int64 and hand int32 hold the bit patterns of
+    the u64 board and the u32 hand word)."""
+    unknown = set(want) - set(PLAYOUT_OUTPUTS)
+    if unknown:
+        raise L.BBNativeError(f"playout_values: unknown outputs {sorted(unknown)}; they are {tuple(PLAYOUT_OUTPUTS)}")
+    return {k: torch.empty((n, playouts), dtype=PLAYOUT_OUTPUTS[k], device=dev) for k in want}
+
+
+def _playout_args(playouts, hands, depth, out, n, dev, want=("value",)):
+    """The Python-side rules shared by ``playout_values`` and ``DeviceEnvBatch.playout_values``; returns (out dict,
+    struct), the dict freshly allocated from ``want`` when ``out`` is None."""
+    if not (isinstance(playouts, int) and 1 <= playouts <= REFILL_MAX_DEALS):
+        raise L.BBNativeError(f"playout_values: playouts must be 1..{REFILL_MAX_DEALS}, not {playouts!r}")
+    if not (isinstance(hands, int) and 1 <= hands <= PLAYOUT_MAX_HANDS):
+        raise L.BBNativeError(f"playout_values: hands must be 1..{PLAYOUT_MAX_HANDS}, not {hands!r}")
+    if not (isinstance(depth, int) and 1 <= depth <= 3):
+        raise L.BBNativeError(f"playout_values: depth must be 1..3, not {depth!r}")
+    out = playout_outputs(n, playouts, dev, want) if out is None else out
+    table = {k: (k, dt, playouts) for k, dt in PLAYOUT_OUTPUTS.items()}
+    return out, _look_out(L.PlayoutOut, "playout_values", table, out, n, dev, at_least_one=True, known_only=True)
+
+
+def playout_values(board: torch.Tensor, rows: torch.Tensor, playouts: int, hands: int, seed: int,
+                   combo: Optional[torch.Tensor] = None, stream: Optional[torch.Tensor] = None, depth: int = 3,
+                   want=("value",), out: Optional[dict] = None) -> dict:
+    """bb_playout_values_pos: ``playouts`` dealt playouts of ``hands`` hands per board in one launch -- deal (the law
+    of ``refill_values``, Philox key seed + h for hand h), search (``plan_actions_ext``), play the plan found
+    (``play_plan``, the combo carried), deal again on the board reached; a playout stops at a hand with no legal first
+    move, at a leaf that is no refill, or after the last hand (bbvec.h "dealt playouts").  board, combo, stream and
+    rows as ``refill_values_ext`` takes them: every playout of board i runs under rows[i] (or the one shared row)
+    and stream id stream[i] (or i).  Returns a dict of the outputs named in ``want`` (or the tensors of ``out``,
+    written in place), each [n, playouts]: "value" int64 (the move terms of every earlier hand plus the last search's
+    value; with hands == 1 ``refill_values_ext``'s value), "score" int64, "lines", "plies" int32 summed over every ply
+    played, "hands" int32 the hands searched, "status" int32 the last hand's ``play_plan`` status word (0: no legal
+    first move; PLAY_REFILL set: survived every hand), "board" int64, "combo" int32 after the last ply, "hand" int32
+    the last hand dealt."""
+    if not (isinstance(board, torch.Tensor) and board.dtype == torch.int64 and board.dim() == 1
+            and board.is_contiguous()):
+        raise L.BBNativeError("playout_values: board must be a contiguous torch.int64 tensor of shape [n]")
+    n, dev = board.numel(), board.device
+    _refill_column("combo", combo, torch.int32, n, dev)
+    _refill_column("stream", stream, torch.int64, n, dev)
+    stride = _eval_rows("playout_values", rows, n, dev)
+    out, o = _playout_args(playouts, hands, depth, out, n, dev, want)
+    if n == 0:  # an empty tensor has no storage to point at; the entry point would do nothing either
+        return out
+    lib, s = _look_lib(dev)
+    L.check(lib.bb_playout_values_pos(_p(board), _p(combo), _p(stream), n, _p(rows), stride, depth, playouts, hands,
+                                      int(seed) & (2 ** 64 - 1), C.byref(o), s), "bb_playout_values_pos", lib=lib)
+    return out
+
+
 PLAY_PLAN_OUTPUTS = {"board": torch.int64, "hand": torch.int32, "combo": torch.int32, "lines": torch.int32,
                      "score": torch.int64, "status": torch.int32}
 PLAY_PLIES, PLAY_DEAD, PLAY_REFILL, PLAY_ILLEGAL = L.BB_PLAY_PLIES, L.BB_PLAY_DEAD, L.BB_PLAY_REFILL, L.BB_PLAY_ILLEGAL

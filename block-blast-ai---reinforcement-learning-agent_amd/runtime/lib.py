@@ -24,6 +24,7 @@ BB_ACTIONS = 192
 BB_NUM_PIECES = 37
 BB_NUM_HANDS = 50653  # 37^3 ordered hands
 BB_REFILL_MAX_DEALS = 1024
+BB_PLAYOUT_MAX_HANDS = 256
 BB_PLAY_PLIES, BB_PLAY_DEAD, BB_PLAY_REFILL, BB_PLAY_ILLEGAL = 3, 4, 8, 16  # bb_play_plan_out.status
 
 
@@ -186,6 +187,14 @@ class Plan2Out(C.Structure):
                 ("value", C.c_void_p)]
 
 
+class PlayoutOut(C.Structure):
+    """bb_playout_out: device arrays value i64 / score i64 / lines i32 / plies i32 / hands i32 / status i32 / board
+    u64 / combo i32 / hand u32, each [n][playouts]; any may be NULL, not all nine."""
+    _fields_ = [("value", C.c_void_p), ("score", C.c_void_p), ("lines", C.c_void_p), ("plies", C.c_void_p),
+                ("hands", C.c_void_p), ("status", C.c_void_p), ("board", C.c_void_p), ("combo", C.c_void_p),
+                ("hand", C.c_void_p)]
+
+
 class PlayPlanOut(C.Structure):
     """bb_play_plan_out: device arrays [n]; any may be NULL, not all six."""
     _fields_ = [("board", C.c_void_p), ("hand", C.c_void_p), ("combo", C.c_void_p), ("lines", C.c_void_p),
@@ -305,6 +314,9 @@ SIGNATURES = {
                                       C.c_int64, C.POINTER(Plan2Out), _P]),
     "bb_plan2_values": (C.c_int, [_P, _P, _P, C.c_int64, _I32, _I32, _I32, _U64, _P, C.c_int64,
                                   C.POINTER(Plan2Out), _P]),
+    "bb_playout_values_pos": (C.c_int, [_P, _P, _P, _I32, _P, C.c_int64, _I32, _I32, _I32, _U64,
+                                        C.POINTER(PlayoutOut), _P]),
+    "bb_playout_values": (C.c_int, [_P, _P, _P, C.c_int64, _I32, _I32, _I32, _U64, C.POINTER(PlayoutOut), _P]),
     "bb_masked_sample": (C.c_int, [_P, _P, _I32, _P, _U64, _U64, _U64, _I32, _P, _P, _P, _P, _P]),
     "bb_masked_sample_dstep": (C.c_int, [_P, _P, _I32, _U64, _P, _U64, _U64, _I32, _P, _P, _P, _P]),
     "bb_gae": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _F, _F, _P, _P, _P]),
@@ -373,7 +385,8 @@ HOST_SYMBOLS = ("bb_abi_version", "bb_build_id", "bb_create", "bb_destroy", "bb_
                 "bb_plan_values_pos", "bb_plan_values", "bb_safe_mask_pos", "bb_safe_mask",
                 "bb_refill_census_pos", "bb_refill_census", "bb_refill_values_pos", "bb_refill_values",
                 "bb_plan_values_ext_pos", "bb_plan_values_ext", "bb_refill_values_ext_pos", "bb_refill_values_ext",
-                "bb_play_plan_pos", "bb_plan2_work_bytes", "bb_plan2_values_pos", "bb_plan2_values")
+                "bb_play_plan_pos", "bb_plan2_work_bytes", "bb_plan2_values_pos", "bb_plan2_values",
+                "bb_playout_values_pos", "bb_playout_values")
 
 _lib = None
 _host = None

@@ -74,7 +74,9 @@ extern "C" {
                                  (additive, still 9) bb_plan_values_ext(_pos) and bb_refill_values_ext(_pos): the
                                  per-action values and the dealt next-hand values under rows of bb_eval_weights;
                                  (additive, still 9) bb_plan2_out with bb_plan2_values(_pos) and bb_plan2_work_bytes:
-                                 the two-hand decision (values, candidates, leaves, deals, choice) in one call */
+                                 the two-hand decision (values, candidates, leaves, deals, choice) in one call;
+                                 (additive, still 9) bb_playout_out with bb_playout_values(_pos): the plan agent
+                                 played for several dealt hands past the refill, in one launch */
 
 #define BB_OK 0
 #define BB_ERR_ARG (-1)
@@ -739,6 +741,66 @@ int bb_plan2_values_pos(const bb_positions* pos, const uint64_t* d_stream /* NUL
 int bb_plan2_values(bb_env* env, const uint64_t* d_stream, const bb_eval_weights* d_w, int64_t w_stride,
                     int32_t depth, int32_t candidates, int32_t deals, uint64_t seed, void* d_work,
                     int64_t work_bytes, const bb_plan2_out* out, void* stream);
+
+/* ---- dealt playouts: several hands past the refill, in one launch -------------------------
+ * The plan agent played for `hands` hands under a counter-based dealer: deal, search, play the
+ * plan found, deal again.  Integers only; every output is defined over bb_refill_values_ext,
+ * bb_plan_actions_ext_pos and bb_play_plan_pos.  Rows, w_stride, d_combo and d_stream as
+ * bb_refill_values_ext(_pos) takes them; every playout of board i runs under board i's row
+ * d_w[i * w_stride] and stream id idx = d_stream ? d_stream[i] : i.  For board i and playout
+ * j < playouts:
+ *   1. (B, combo) = (board[i], combo[i]), moved = 0.
+ *   2. For h = 0 .. hands-1:
+ *      deal    the hand that bb_refill_values' law deals as deal j on B under stream id idx
+ *              and key (seed + h) mod 2^64: the same counters, the same 100 draws, the same
+ *              acceptance.  Hand 0 is bit for bit bb_refill_values_ext's deal j.
+ *      search  value_h, plan_h = bb_plan_actions_ext_pos on (B, that hand, combo) under the
+ *              row and depth.  No legal first move: value_h = (int64)w.base.dead, nothing is
+ *              played, and the playout ends with status 0.
+ *      play    plan_h as bb_play_plan_pos plays it, the combo carried: B, combo, lines, score
+ *              and plies advance; m_h = w.base.lines * lines_h + w.base.score * score_h.
+ *      go on   if that call's status word has BB_PLAY_REFILL and h < hands-1, moved += m_h and
+ *              the next hand is dealt; otherwise the playout stops (a dead leaf, a plan cut
+ *              short by depth < 3, the last hand).
+ *   3. Outputs, each [n][playouts]:
+ *      value   moved + value_last: the move terms of every earlier hand plus the last search's
+ *              value.  With hands == 1 this is bb_refill_values_ext's value.
+ *      score, lines, plies  summed over every ply played
+ *      hands   hands searched, 1..hands
+ *      status  the last hand's bb_play_plan_pos status word, 0 if it had no legal first move;
+ *              BB_PLAY_REFILL set: the playout survived all `hands` hands
+ *      board, combo  after the last ply played
+ *      hand    the last hand dealt, in bb_refill_values_out.hand's format
+ * Two playouts with the same stream id and j meet the same draws (common random numbers).
+ * Started from empty boards with one row per board this plays whole games of the plan agent.
+ * depth is 1..3, playouts 1..1024, hands 1..BB_PLAYOUT_MAX_HANDS; n == 0 does nothing.
+ * BB_ERR_ARG (the rule named in bb_last_error, before any HIP call) for a NULL board, n < 0,
+ * NULL rows, a w_stride that is not 0 or 1, a NULL out, all nine outputs NULL, depth outside
+ * 1..3, playouts outside 1..1024 and hands outside 1..256.  The handle form reads the live
+ * board and combo columns and changes nothing, the RNG included, and refuses a handle in
+ * BB_ERR_DEVICE / BB_ERR_STATE.  One launch, asynchronous on `stream`, no allocation, no sync,
+ * no host read (graph-capturable from the first call; seed is passed by value, so a captured
+ * graph repeats its deals); indexing is 64-bit. */
+#define BB_PLAYOUT_MAX_HANDS 256
+typedef struct bb_playout_out {
+  int64_t*  value;   /* [n][playouts] moved + the last search's value                              */
+  int64_t*  score;   /* [n][playouts] score_gained over every ply played (combo carried)           */
+  int32_t*  lines;   /* [n][playouts] lines cleared over every ply played                          */
+  int32_t*  plies;   /* [n][playouts] plies played                                                 */
+  int32_t*  hands;   /* [n][playouts] hands searched, 1..hands                                     */
+  int32_t*  status;  /* [n][playouts] the last hand's play-plan status word; 0: no legal first move */
+  uint64_t* board;   /* [n][playouts] after the last ply played                                    */
+  int32_t*  combo;   /* [n][playouts] after the last ply played                                    */
+  uint32_t* hand;    /* [n][playouts] the last hand dealt: ids a | b<<6 | c<<12                    */
+} bb_playout_out;    /* device pointers (host pointers for libbbvec_host.so); any may be NULL, not all nine */
+int bb_playout_values_pos(const uint64_t* d_board, const int32_t* d_combo /* NULL = 0 */,
+                          const uint64_t* d_stream /* NULL = i */, int32_t n, const bb_eval_weights* d_w,
+                          int64_t w_stride, int32_t depth, int32_t playouts, int32_t hands, uint64_t seed,
+                          const bb_playout_out* out, void* stream);
+/* the same for the handle's live boards and combos ([N][playouts] outputs) */
+int bb_playout_values(bb_env* env, const uint64_t* d_stream, const bb_eval_weights* d_w, int64_t w_stride,
+                      int32_t depth, int32_t playouts, int32_t hands, uint64_t seed, const bb_playout_out* out,
+                      void* stream);
 
 /* Fused masked-categorical tail of BlockBlastNetwork.get_action_and_value
  * (network.py:173-180, 210-262; Categorical clamp semantics of torch 2.10):
